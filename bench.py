@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- formal_sol_gamma_matrices iterations/second on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nlambda 10240] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nlambda 10240] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json north star): FAL-C, 82 depths, H(6) + Ca II(6) active, 5 mu-angles, fp64,
 Bezier3 short characteristics, wavelength grid densified to ~10 240 points per GPU.  One step =
@@ -18,14 +18,21 @@ rank's (dJMax, idx) riding in its tail.
   --scaling strong the 10 240-wavelength grid is split over the N ranks; `value` = whole-problem iterations/s.
 `allreduce_us` is the mean host time per step spent issuing the collective (N > 1).
 
-Beside the headline line's fields: `parity_checked` / `max_rel_err` compare a first iteration of the GPU path with
-the first iteration of the `cpu_baseline` leg on identical inputs; `aux` carries the other BASELINE configs, each
-with its own roofline block (not part of the metric): C3 the PRD sub-iteration, C4 a 512-column fused 1.5D batch,
-C5 the 256 x 82 2D iteration.  `--no-aux` skips them, `--aux-only NAME` runs just one (profiling).
+A plain run sets up, warms up, times exactly K steps and prints the headline line; nothing else.
+`--dump-outputs DIR` then writes what the last timed step computed (J, I, Gamma, Rij, Rji as a caller of the device-resident
+step downloads them, and dJMax) as DIR/<name>.npy in float64, on rank 0 (J and I: its own wavelengths); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+`--full` adds everything else, after the timed steps: the `roofline` block (HIP events around the sweep launches of the
+timed steps), the weak-scaling figure (N > 1, `--no-weak` skips it), `cpu_baseline` and `parity_checked` / `max_rel_err`,
+which compare a first iteration of the GPU path with the first iteration of the `cpu_baseline` leg on identical inputs
+(`--no-cpu-baseline` skips them), and `aux`: stat_equil timings and the other BASELINE configs, each with its own roofline
+block (not part of the metric): C3 the PRD sub-iteration, C4 a 512-column fused 1.5D batch, C5 the 256 x 82 2D iteration.
+`--no-aux` skips them, `--aux-only NAME` runs just one (profiling).
 
 `--mode columns` is BASELINE configs[3] as a run of its own: `--columns` (512) perturbed FAL-C columns PER GPU, rank r owning
 columns r, r + N, ... of the seeded set as one fused batch, no collective; value = column-iterations/s over all ranks.  With
-N > 1 the default (lambda) line carries a short form of it as aux.C4_columns.
+N > 1 the default (lambda) line of a `--full` run carries a short form of it as aux.C4_columns.
 
 Prints ONE JSON line on rank 0.
 """
@@ -72,7 +79,17 @@ def parse():
                     help="torch.distributed backend for N > 1 ('nccl' = RCCL, one rank per GPU; 'gloo' with --share-gpu "
                          'exercises the sharded path with several ranks on ONE GPU)')
     ap.add_argument('--share-gpu', action='store_true', help='every rank uses device 0 (functional check only)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure the roofline, weak scaling (N > 1), the CPU baseline with the parity '
+                         'check and the aux entries (a plain run only times the headline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float64, rank 0)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and (args.mode != 'lambda' or args.aux_only):
+        ap.error('--dump-outputs writes the outputs of the default (lambda) run')
+    return args
 
 
 PREWARM = int(os.environ.get('LWHIP_BENCH_PREWARM', '200'))  # untimed steps before the warm-up steps (clock settle; see main)
@@ -121,6 +138,23 @@ def snapshot(prob):
             out[f'Rij{ia}_{kr}'] = t.Rij.copy()
             out[f'Rji{ia}_{kr}'] = t.Rji.copy()
     return out
+
+
+DUMP_LIMIT_BYTES = 60 << 20   # what --dump-outputs may write in all, .npy headers aside (under 64 MB)
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as <path>/<name>.npy in float64.  Past `limit` bytes in all, every array is cut to a
+    fixed, seeded sample of its flattened elements (sorted indices, the same on every run), in proportion to its size."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, a.size * (limit - 8 * len(arrays)) // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def rel_err(a, b):
@@ -681,6 +715,7 @@ def main():
     import torch
     import torch.distributed as dist
 
+    from lightweaver_amd import _abi as abi
     from lightweaver_amd.context import Context
     from lightweaver_amd.distributed import ShardedIteration, shard_bounds
     from lightweaver_amd.harness import models
@@ -747,7 +782,8 @@ def main():
         step()
     for _ in range(args.warmup):
         step()
-    ctx.profile_enable(int(os.environ.get('LWHIP_BENCH_PROF', '4')))   # HIP events around every 4th sweep launch
+    if args.full:
+        ctx.profile_enable(int(os.environ.get('LWHIP_BENCH_PROF', '4')))   # HIP events around every 4th sweep launch
     it.allreduce_s = 0.0
     if world > 1:
         dist.barrier()
@@ -765,74 +801,81 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    sweep_ms, nlaunch = ctx.sweep_time()
     sweep_kind = ctx.sweep_kind()
-    ctx.profile_enable(False)
-    alg_bytes = ctx.algorithmic_bytes()
-    alg_flops = algorithmic_flops(prob, la0, la1)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the device-resident step gets when it downloads the results of the last timed step
+        ctx.download(abi.ALL_OUTPUTS)
+        outputs = snapshot(prob)
+        outputs['J'], outputs['I'] = outputs['J'][la0:la1], outputs['I'][la0:la1]
+        outputs['dJMax'] = [up.dJMax]
+        dump_outputs(args.dump_outputs, outputs)
 
-    # N > 1, strong: the weak-scaling figure beside it (every rank keeps --nlambda wavelengths: shard-iterations/s)
-    weak = None
-    if world > 1 and args.scaling == 'strong' and not args.no_weak:
+    weak, aux = None, {}
+    if args.full:
+        sweep_ms, nlaunch = ctx.sweep_time()
+        ctx.profile_enable(False)
+        alg_bytes = ctx.algorithmic_bytes()
+        alg_flops = algorithmic_flops(prob, la0, la1)
+
+        # N > 1, strong: the weak-scaling figure beside it (every rank keeps --nlambda wavelengths: shard-iterations/s)
+        if world > 1 and args.scaling == 'strong' and not args.no_weak:
+            ctx.close()
+            probW = models.throughput_grid(NlambdaTarget=args.nlambda * world, Nrays=5, computeProfiles=False)
+            bW = shard_bounds(probW, world)
+            ctx = Context(probW, device=local_rank, laStart=bW[rank], laEnd=bW[rank + 1], stream=stream.cuda_stream,
+                          worldSize=world, worldRank=rank)
+            ctx.compute_profiles(deviceResident=True)
+            itW = ShardedIteration(ctx, world, rank)
+            gc.collect()
+            gc.disable()
+            for _ in range(PREWARM + args.warmup):
+                itW.formal_sol_gamma_matrices(deviceResident=True)
+            dist.barrier()
+            torch.cuda.synchronize()
+            tw = time.perf_counter()
+            for _ in range(args.steps):
+                itW.formal_sol_gamma_matrices(deviceResident=True)
+            dist.barrier()
+            torch.cuda.synchronize()
+            ew = torch.tensor([time.perf_counter() - tw], dtype=torch.float64, device='cuda')
+            gc.enable()
+            dist.all_reduce(ew, op=dist.ReduceOp.MAX)
+            weak = {'weak_shard_iters_per_s': world * args.steps / float(ew.item()), 'weak_ms_per_step': 1e3 * float(ew.item()) / args.steps,
+                    'weak_Nlambda_total': probW.Nlambda}
+
+        # not part of the metric ("report stat_eq time separately"): the population solve, and the other
+        # BASELINE configs
+        if world == 1:
+            aux['stat_eq_ms'] = timed(lambda: ctx.stat_equil(deviceResident=True), 20, torch)
+
+            # what an iterate_ctx_se loop pays per iteration: the formal solution, then stat_equil of every atom, each with its result
+            # on the host (lightweaver/iterate_ctx.py:157-176; device-resident)
+            def se_iteration():
+                ctx.formal_sol_gamma_matrices(deviceResident=True)
+                ctx.stat_equil(deviceResident=True)
+            aux['iterate_se_ms'] = timed(se_iteration, 100, torch)
         ctx.close()
-        probW = models.throughput_grid(NlambdaTarget=args.nlambda * world, Nrays=5, computeProfiles=False)
-        bW = shard_bounds(probW, world)
-        ctx = Context(probW, device=local_rank, laStart=bW[rank], laEnd=bW[rank + 1], stream=stream.cuda_stream,
-                      worldSize=world, worldRank=rank)
-        ctx.compute_profiles(deviceResident=True)
-        itW = ShardedIteration(ctx, world, rank)
-        gc.collect()
-        gc.disable()
-        for _ in range(PREWARM + args.warmup):
-            itW.formal_sol_gamma_matrices(deviceResident=True)
-        dist.barrier()
-        torch.cuda.synchronize()
-        tw = time.perf_counter()
-        for _ in range(args.steps):
-            itW.formal_sol_gamma_matrices(deviceResident=True)
-        dist.barrier()
-        torch.cuda.synchronize()
-        ew = torch.tensor([time.perf_counter() - tw], dtype=torch.float64, device='cuda')
-        gc.enable()
-        dist.all_reduce(ew, op=dist.ReduceOp.MAX)
-        weak = {'weak_shard_iters_per_s': world * args.steps / float(ew.item()), 'weak_ms_per_step': 1e3 * float(ew.item()) / args.steps,
-                'weak_Nlambda_total': probW.Nlambda}
-
-    # not part of the metric ("report stat_eq time separately"): the population solve, and the other
-    # BASELINE configs
-    aux = {}
-    if world == 1:
-        aux['stat_eq_ms'] = timed(lambda: ctx.stat_equil(deviceResident=True), 20, torch)
-
-        # what an iterate_ctx_se loop pays per iteration: the formal solution, then stat_equil of every atom, each with its result
-        # on the host (lightweaver/iterate_ctx.py:157-176; device-resident)
-        def se_iteration():
-            ctx.formal_sol_gamma_matrices(deviceResident=True)
-            ctx.stat_equil(deviceResident=True)
-        aux['iterate_se_ms'] = timed(se_iteration, 100, torch)
-    ctx.close()
-    if world > 1 and not args.no_aux:
-        # the split that scales by construction, beside the strong-scaling headline: every rank its own fused batch of columns
-        try:
-            cc = run_columns(args, rank, world, local_rank, stream, torch, dist, models, steps=10, warmup=2)
-            cc.pop('elapsed')
-            cc['config'] = (f"C4: {cc['columns_total']} perturbed FALC columns over {world} GPUs, {cc['columns_per_gpu']} per GPU, "
-                            'no collective (python bench.py --gpus N --mode columns is the full run)')
-            aux['C4_columns'] = cc
-        except Exception as e:
-            aux['C4_columns'] = {'failed': repr(e)}
-    if world == 1 and not args.no_aux:
-        for key, (name, fn) in AUX.items():
+        if world > 1 and not args.no_aux:
+            # the split that scales by construction, beside the strong-scaling headline: every rank its own fused batch of columns
             try:
-                aux[name] = fn(args, local_rank, stream.cuda_stream, torch, models)
-            except Exception as e:   # a side measurement must never break the bench line
-                aux[name] = {'failed': repr(e)}
+                cc = run_columns(args, rank, world, local_rank, stream, torch, dist, models, steps=10, warmup=2)
+                cc.pop('elapsed')
+                cc['config'] = (f"C4: {cc['columns_total']} perturbed FALC columns over {world} GPUs, {cc['columns_per_gpu']} per GPU, "
+                                'no collective (python bench.py --gpus N --mode columns is the full run)')
+                aux['C4_columns'] = cc
+            except Exception as e:
+                aux['C4_columns'] = {'failed': repr(e)}
+        if world == 1 and not args.no_aux:
+            for key, (name, fn) in AUX.items():
+                try:
+                    aux[name] = fn(args, local_rank, stream.cuda_stream, torch, models)
+                except Exception as e:   # a side measurement must never break the bench line
+                    aux[name] = {'failed': repr(e)}
+    ctx.close()
 
     if rank == 0:
         per_step = world if args.scaling == 'weak' else 1
         value = per_step * args.steps / elapsed
-        achieved = alg_bytes / (sweep_ms * 1e-3) / 1e9 if sweep_ms > 0 else 0.0
-        traffic, traffic_src = profiled_traffic(sweep_kind) if (world == 1 and args.nlambda == 10240) else (None, None)
         out = {
             'metric': 'formal_sol_gamma_matrices iters/sec',
             'value': value,
@@ -857,7 +900,14 @@ def main():
                 'parallelism': f'lambda-shard x{world}' if world > 1 else 'single GPU',
                 'final_dJMax': up.dJMax,
             },
-            'roofline': {
+        }
+        out['config']['sweep'] = sweep_kind
+        if world > 1:
+            out['allreduce_us'] = allreduce_us
+        if args.full:
+            achieved = alg_bytes / (sweep_ms * 1e-3) / 1e9 if sweep_ms > 0 else 0.0
+            traffic, traffic_src = profiled_traffic(sweep_kind) if (world == 1 and args.nlambda == 10240) else (None, None)
+            out['roofline'] = {
                 'bound': 'hbm',
                 'kernel': ('lanesweep_kernel (depth-across-lanes sweep)' if sweep_kind == 'lanes'
                            else 'raymarch_kernel (ray-column march with the fused post-pass)'),
@@ -886,56 +936,52 @@ def main():
                     'attainable_source': 'tools/micro/issue_bench.hip: one fp64 FMA per 8.5 / 6.9 clocks per SIMD at 2 / 4 '
                                          'wavefronts per SIMD (profiles/r04_lanesweep.md)',
                 },
-            },
-        }
-        out['config']['sweep'] = sweep_kind
-        if world > 1:
-            out['allreduce_us'] = allreduce_us
-        if weak:
-            out.update(weak)
-        mv = aux.get('moving_1d')
-        if isinstance(mv, dict) and isinstance(mv.get('roofline'), dict):
-            out['roofline']['frac_general'] = mv['roofline']['frac']
-            out['roofline']['kernel_ms_general'] = mv['roofline']['kernel_ms']
-        out['roofline']['algorithmic_bytes_note'] = (
-            'SURVEY 8(d) counts phi of both directions of every angle; on this static atmosphere the lane sweep reads ONE '
-            "direction's phi for one-line tiles (ray pairs), so `achieved` is an upper bound on the bytes the kernel moves: "
-            'frac_general (aux.moving_1d: the same grid with a velocity field, both directions read) is the number a moving '
-            'atmosphere gets')
-        for name in ('fixed_order', 'realistic_1d', 'moving_1d'):
-            if isinstance(aux.get(name), dict) and 'ms_per_step' in aux[name]:
-                aux[name]['ratio_to_headline'] = aux[name]['ms_per_step'] / out['ms_per_step']
-        if aux:
-            out['aux'] = aux
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                single = prob.copy()
-                models.compute_profiles_host(single)   # the CPU leg needs phi on the host
-                out['cpu_baseline'], par = cpu_baseline(single, args.cpu_seconds)
-                # parity at the timed size: the HIP path's first iteration (+ stat_equil) on the same inputs
-                gpu_first = gpu_first_iteration(single, local_rank, stream.cuda_stream)
+            }
+            if weak:
+                out.update(weak)
+            mv = aux.get('moving_1d')
+            if isinstance(mv, dict) and isinstance(mv.get('roofline'), dict):
+                out['roofline']['frac_general'] = mv['roofline']['frac']
+                out['roofline']['kernel_ms_general'] = mv['roofline']['kernel_ms']
+            out['roofline']['algorithmic_bytes_note'] = (
+                'SURVEY 8(d) counts phi of both directions of every angle; on this static atmosphere the lane sweep reads ONE '
+                "direction's phi for one-line tiles (ray pairs), so `achieved` is an upper bound on the bytes the kernel moves: "
+                'frac_general (aux.moving_1d: the same grid with a velocity field, both directions read) is the number a moving '
+                'atmosphere gets')
+            for name in ('fixed_order', 'realistic_1d', 'moving_1d'):
+                if isinstance(aux.get(name), dict) and 'ms_per_step' in aux[name]:
+                    aux[name]['ratio_to_headline'] = aux[name]['ms_per_step'] / out['ms_per_step']
+            if aux:
+                out['aux'] = aux
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    single = prob.copy()
+                    models.compute_profiles_host(single)   # the CPU leg needs phi on the host
+                    out['cpu_baseline'], par = cpu_baseline(single, args.cpu_seconds)
+                    # parity at the timed size: the HIP path's first iteration (+ stat_equil) on the same inputs
+                    gpu_first = gpu_first_iteration(single, local_rank, stream.cuda_stream)
 
-                def group_errs(x, ref):
-                    errs = {}
-                    for k, r in ref.items():
-                        grp = ''.join(ch for ch in k.split('_')[0] if not ch.isdigit())
-                        errs[grp] = max(errs.get(grp, 0.0), rel_err(x[k], r))
-                    return errs
-                errs = group_errs(gpu_first, par['first'])
-                tol = {k: (1e-8 if k == 'n' else PARITY_TOL) for k in errs}
-                out['max_rel_err'] = max(errs.values())
-                out['parity_checked'] = bool(all(errs[k] <= tol[k] for k in errs))
-                out['parity'] = {'against': par['name'], 'rel_err': errs,
-                                 'tolerance': {'one_iteration': PARITY_TOL, 'n_after_stat_equil': 1e-8},
-                                 'what': 'first formal_sol_gamma_matrices + stat_equil from identical inputs, '
-                                         f'{prob.Nlambda} wavelengths'}
-                if par['simd_first'] is not None:
-                    out['parity']['reference_simd_vs_scalar'] = {
-                        'scheme': par['simd_name'], 'rel_err': group_errs(par['simd_first'], par['first'])}
-            except Exception as e:  # the baseline must never break the bench line
-                out['cpu_baseline'] = {'value': None, 'unit': 'iters/s', 'cores': 0, 'kind': 'port',
-                                       'sample': f'failed: {e!r}'}
-                out['parity_checked'] = False
+                    def group_errs(x, ref):
+                        errs = {}
+                        for k, r in ref.items():
+                            grp = ''.join(ch for ch in k.split('_')[0] if not ch.isdigit())
+                            errs[grp] = max(errs.get(grp, 0.0), rel_err(x[k], r))
+                        return errs
+                    errs = group_errs(gpu_first, par['first'])
+                    tol = {k: (1e-8 if k == 'n' else PARITY_TOL) for k in errs}
+                    out['max_rel_err'] = max(errs.values())
+                    out['parity_checked'] = bool(all(errs[k] <= tol[k] for k in errs))
+                    out['parity'] = {'against': par['name'], 'rel_err': errs,
+                                     'tolerance': {'one_iteration': PARITY_TOL, 'n_after_stat_equil': 1e-8},
+                                     'what': 'first formal_sol_gamma_matrices + stat_equil from identical inputs, '
+                                             f'{prob.Nlambda} wavelengths'}
+                    if par['simd_first'] is not None:
+                        out['parity']['reference_simd_vs_scalar'] = {
+                            'scheme': par['simd_name'], 'rel_err': group_errs(par['simd_first'], par['first'])}
+                except Exception as e:  # the baseline must never break the bench line
+                    out['cpu_baseline'] = {'value': None, 'unit': 'iters/s', 'cores': 0, 'kind': 'port',
+                                           'sample': f'failed: {e!r}'}
+                    out['parity_checked'] = False
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

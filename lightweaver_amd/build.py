@@ -134,9 +134,12 @@ def _lint_cached(path):
 def build_plugin(force=False, verbose=False):
     """The Lightweaver iteration-scheme plugin (fs_iteration_fns_provider).  It is compiled against
     the Lightweaver headers, so it is only (re)built where they are present; elsewhere a prebuilt
-    copy (it travels with the tree) is used as is."""
+    copy is used as is: the one in place, or the one the oracle build keeps under oracle/_ref."""
     src = os.path.join(CSRC, 'plugin', 'lwhip_plugin.cpp')
     if not os.path.exists(src) or not os.path.exists(os.path.join(REF_SRC, 'Lightweaver.hpp')):
+        carried = os.path.join(ROOT, 'oracle', '_ref', os.path.basename(PLUGIN))   # (oracle/Makefile keeps a copy there)
+        if not os.path.exists(PLUGIN) and os.path.exists(carried):
+            shutil.copy2(carried, PLUGIN)
         return PLUGIN if os.path.exists(PLUGIN) else None
     deps = [src, os.path.join(ROOT, 'include', 'lwhip.h')]
     build_hip()

@@ -1,6 +1,6 @@
-"""bench.py's output contract (what the round driver parses): ONE JSON line on rank 0 with the headline metric, the
-roofline block of the dominant kernel measured live with HIP events, the CPU baseline and the parity check at the timed
-size.  Runs bench.py as a child process on the GPU box (short: 5 timed steps, 2 s of CPU baseline, one aux entry)."""
+"""bench.py's output contract (what the round driver parses): ONE JSON line on rank 0 with the headline metric; with --full
+also the roofline block of the dominant kernel measured live with HIP events, the CPU baseline and the parity check at the
+timed size.  Runs bench.py as a child process on the GPU box (short: 5 timed steps, 2 s of CPU baseline, no aux entry)."""
 import json
 import os
 import subprocess
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_contract(gpu):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '5', '--warmup', '2',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '5', '--warmup', '2',
                           '--cpu-seconds', '2', '--no-aux'], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
@@ -44,6 +44,63 @@ def test_bench_line_contract(gpu):
     for k in ('J', 'I', 'Gamma', 'Rij', 'Rji'):
         assert par['rel_err'][k] <= 1e-9, (k, par['rel_err'][k])
     assert par['rel_err']['n'] <= 1e-8
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(gpu, tmp_path):
+    """A plain run times the headline and nothing else; --dump-outputs writes what the last timed step computed, the same on
+    every run with the same arguments (to rounding, where the default mode sums with atomics)."""
+    import numpy as np
+    from helpers import rel_err
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / f'run{run}'
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2',
+                              '--dump-outputs', str(d_out)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d['metric'] == 'formal_sol_gamma_matrices iters/sec' and d['unit'] == 'iters/s' and d['higher_is_better'] is True
+        assert d['dtype'] == 'f64' and d['steps'] == 7 and d['warmup'] == 2 and d['n_gpus'] == 1
+        assert d['value'] == pytest.approx(1e3 / d['ms_per_step'], rel=1e-9) and d['ms_per_step'] > 0.0
+        for key in ('roofline', 'cpu_baseline', 'parity_checked', 'aux'):
+            assert key not in d, key
+        files = sorted(p.name for p in d_out.iterdir())
+        assert {'J.npy', 'I.npy', 'Gamma0.npy', 'Gamma1.npy', 'dJMax.npy'} <= set(files), files
+        assert any(f.startswith('Rij') for f in files) and any(f.startswith('Rji') for f in files)
+        assert sum((d_out / f).stat().st_size for f in files) <= 64 * 10**6
+        arrays = {f: np.load(d_out / f) for f in files}
+        assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in arrays.values())
+        nla = d['config']['Nlambda_total']
+        assert arrays['J.npy'].shape == (nla, 82) and arrays['I.npy'].shape == (nla, 5)
+        assert arrays['J.npy'].max() > 0.0 and arrays['dJMax.npy'][0] == d['config']['final_dJMax']
+        dumps.append(arrays)
+    # J, I and dJMax are bit-identical from run to run; Gamma and the rates are summed with atomics in the default mode (the
+    # fixed-order mode is the bit-reproducible one), so they agree to rounding
+    for f, a in dumps[0].items():
+        if f in ('J.npy', 'I.npy', 'dJMax.npy'):
+            assert np.array_equal(a, dumps[1][f]), f
+        else:
+            assert rel_err(dumps[1][f], a) <= 1e-13, (f, rel_err(dumps[1][f], a))
+
+
+def test_dump_outputs_samples_past_the_limit(tmp_path):
+    """Past the size limit every output keeps a fixed, seeded sample of its elements, in proportion to its size."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {'J': np.arange(5000.0).reshape(100, 50), 'n': np.arange(10, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / 'whole'), arrays)
+    assert np.array_equal(np.load(tmp_path / 'whole' / 'J.npy'), arrays['J'])
+    assert np.load(tmp_path / 'whole' / 'n.npy').dtype == np.float64
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), arrays, limit=4000)
+    J = np.load(tmp_path / 'a' / 'J.npy')
+    n = np.load(tmp_path / 'a' / 'n.npy')
+    assert J.nbytes + n.nbytes <= 4000 and J.size > 100 * n.size
+    assert np.all(np.diff(J) > 0) and np.isin(J, arrays['J']).all()
+    assert np.array_equal(J, np.load(tmp_path / 'b' / 'J.npy')) and np.array_equal(n, np.load(tmp_path / 'b' / 'n.npy'))
 
 
 def test_rank_launch_command_shape():
