@@ -157,11 +157,12 @@ void stream_release_shared(int device, hipStream_t s)
         }
 }
 
-// ---- page-locked host memory out of slabs ---------------------------------------------------------------------------------
+// ---- page-locked host memory: the one pool -------------------------------------------------------------------------------
 // hipHostMalloc takes ~3 ms when 16 threads create columns (two per context -- the host block and the upload stage -- were 20 %
-// of a batch's set-up).  Blocks up to 512 KB are cut from 4 MB slabs (mapped, coherent: device-visible at the same offset of
-// the slab's device pointer); larger ones are slabs of their own.  A released block waits in a list of its rounded size for the
-// next request of that size; slabs live until the process ends.
+// of a batch's set-up).  Blocks up to 512 KB are cut from 4 MB slabs of their kind (mapped: host-mapped and coherent, device-
+// visible at the same offset of the slab's device pointer; else plain page-locked copy memory); larger ones are slabs of their
+// own.  A released block waits in a list of its kind and rounded size for the next request of that size; slabs live until the
+// process ends.
 namespace
 {
 struct PinnedSlab
@@ -169,12 +170,13 @@ struct PinnedSlab
     unsigned char* host = nullptr;
     unsigned char* dev = nullptr;
     size_t cap = 0, used = 0;
+    bool mapped = false;
 };
 struct PinnedPool
 {
     std::mutex m;
     std::vector<PinnedSlab> slabs;
-    std::map<size_t, std::vector<std::pair<void*, void*>>> freeBySize;
+    std::map<std::pair<bool, size_t>, std::vector<std::pair<void*, void*>>> freeBySize;
 };
 PinnedPool& pinned_pool(int device)
 {
@@ -189,12 +191,12 @@ PinnedPool& pinned_pool(int device)
 constexpr size_t PINNED_SLAB = (size_t)4 << 20, PINNED_SMALL = (size_t)512 << 10;
 inline size_t pinned_round(size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; }
 }
-void* pinned_acquire(int device, size_t bytes, void** devPtr)
+void* pinned_acquire(int device, size_t bytes, void** devPtr, bool mapped)
 {
     const size_t sz = pinned_round(bytes);
     PinnedPool& pool = pinned_pool(device);
     std::lock_guard<std::mutex> g(pool.m);
-    auto it = pool.freeBySize.find(sz);
+    auto it = pool.freeBySize.find({ mapped, sz });
     if (it != pool.freeBySize.end() && !it->second.empty())
     {
         const auto pr = it->second.back();
@@ -206,7 +208,7 @@ void* pinned_acquire(int device, size_t bytes, void** devPtr)
     PinnedSlab* slab = nullptr;
     if (sz <= PINNED_SMALL)
         for (auto& sl : pool.slabs)
-            if (sl.cap == PINNED_SLAB && sl.used + sz <= sl.cap)
+            if (sl.cap == PINNED_SLAB && sl.mapped == mapped && sl.used + sz <= sl.cap)
             {
                 slab = &sl;
                 break;
@@ -215,8 +217,9 @@ void* pinned_acquire(int device, size_t bytes, void** devPtr)
     {
         PinnedSlab sl;
         sl.cap = sz <= PINNED_SMALL ? PINNED_SLAB : sz;
-        if (hipHostMalloc((void**)&sl.host, sl.cap, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess
-            || hipHostGetDevicePointer((void**)&sl.dev, sl.host, 0) != hipSuccess)
+        sl.mapped = mapped;
+        if (hipHostMalloc((void**)&sl.host, sl.cap, mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault) != hipSuccess
+            || (mapped && hipHostGetDevicePointer((void**)&sl.dev, sl.host, 0) != hipSuccess))
         {
             (void)hipGetLastError();
             if (sl.host)
@@ -228,7 +231,7 @@ void* pinned_acquire(int device, size_t bytes, void** devPtr)
     }
     void* h = slab->host + slab->used;
     if (devPtr)
-        *devPtr = slab->dev + slab->used;
+        *devPtr = slab->dev ? slab->dev + slab->used : nullptr;
     slab->used += sz;
     return h;
 }
@@ -238,54 +241,100 @@ void pinned_release(int device, void* p, size_t bytes)
         return;
     PinnedPool& pool = pinned_pool(device);
     std::lock_guard<std::mutex> g(pool.m);
-    void* dev = nullptr;
     for (const auto& sl : pool.slabs)
         if ((unsigned char*)p >= sl.host && (unsigned char*)p < sl.host + sl.cap)
-            dev = sl.dev + ((unsigned char*)p - sl.host);
-    pool.freeBySize[pinned_round(bytes)].emplace_back(p, dev);
+        {
+            void* dev = sl.dev ? sl.dev + ((unsigned char*)p - sl.host) : nullptr;
+            pool.freeBySize[{ sl.mapped, pinned_round(bytes) }].emplace_back(p, dev);
+            return;
+        }
+}
+
+hipError_t PinnedBlock::reserve(int dev_, size_t need, hipStream_t s, bool mapped)
+{
+    if (!host || bytes < need)
+    {
+        release();
+        host = (unsigned char*)pinned_acquire(dev_, need, (void**)&dev, mapped);
+        if (!host)
+            return hipErrorOutOfMemory;
+        bytes = need;
+        device = dev_;
+    }
+    stream = s;
+    return hipSuccess;
+}
+void PinnedBlock::release()
+{
+    if (!host)
+        return;
+    (void)hipStreamSynchronize(stream); // (a queued copy or kernel may still read or write it)
+    pinned_release(device, host, bytes);
+    host = dev = nullptr;
+    bytes = 0;
 }
 
 // ---- gathered uploads of a batch column's creation (H2DBatch, lwhip_host.h) -----------------------------------------------
+// The stage comes out of the pinned pool, the device inbox out of a per-device pool of its own.
 namespace
 {
 constexpr size_t H2D_BATCH_CAP = (size_t)24 << 20;
-struct H2DPair
+std::mutex g_inboxMutex;
+std::map<int, std::vector<unsigned char*>>& h2d_inboxes()
 {
-    unsigned char* host = nullptr;
-    unsigned char* inbox = nullptr;
-};
-std::mutex g_h2dMutex;
-std::map<int, std::vector<H2DPair>>& h2d_pairs()
-{
-    static std::map<int, std::vector<H2DPair>>* m = new std::map<int, std::vector<H2DPair>>();
+    static std::map<int, std::vector<unsigned char*>>* m = new std::map<int, std::vector<unsigned char*>>();
     return *m;
 }
 }
+bool H2DBatch::open(int dev, hipStream_t s)
+{
+    device = dev;
+    {
+        std::lock_guard<std::mutex> g(g_inboxMutex);
+        auto& v = h2d_inboxes()[device];
+        if (!v.empty())
+        {
+            inbox = v.back();
+            v.pop_back();
+        }
+    }
+    if (!inbox && hipMalloc((void**)&inbox, H2D_BATCH_CAP) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        inbox = nullptr;
+        return false;
+    }
+    if (stage.reserve(device, H2D_BATCH_CAP, s) != hipSuccess)
+    {
+        close();
+        return false;
+    }
+    return true;
+}
 bool H2DBatch::add(void* dst, const void* src, size_t bytes)
 {
-    if (!host || bytes == 0)
+    if (!stage.host || bytes == 0)
         return bytes == 0;
     const size_t nRec = (bytes + H2D_CHUNK - 1) / H2D_CHUNK;
     auto need = [&](size_t nMore) { return ((used + 15) & ~(size_t)15) + bytes + 16 + (recs.size() + nMore) * sizeof(H2DRec); };
-    if (need(nRec) > cap)
+    if (need(nRec) > stage.bytes)
     {
-        if (flush() != hipSuccess || need(nRec) > cap)
+        if (flush() != hipSuccess || need(nRec) > stage.bytes)
             return false; // (larger than the stage: the ordinary copy)
     }
     if (inFlight)
     {
         // the stage is being read by the copy of the previous flush
-        if (hipStreamSynchronize(stream) != hipSuccess)
+        if (hipStreamSynchronize(stage.stream) != hipSuccess)
             return false;
         inFlight = false;
     }
     used = (used + 15) & ~(size_t)15;
-    std::memcpy(host + used, src, bytes);
+    std::memcpy(stage.host + used, src, bytes);
     for (size_t o = 0; o < bytes; o += H2D_CHUNK)
         recs.push_back(H2DRec{ (unsigned long long)(uintptr_t)dst + o, (unsigned long long)(used + o),
                                (unsigned long long)std::min<size_t>(H2D_CHUNK, bytes - o) });
     used += bytes;
-    ++copies;
     return true;
 }
 hipError_t H2DBatch::flush()
@@ -293,76 +342,36 @@ hipError_t H2DBatch::flush()
     if (recs.empty())
         return hipSuccess;
     const size_t recsOff = (used + 15) & ~(size_t)15;
-    std::memcpy(host + recsOff, recs.data(), recs.size() * sizeof(H2DRec));
+    std::memcpy(stage.host + recsOff, recs.data(), recs.size() * sizeof(H2DRec));
     const size_t total = recsOff + recs.size() * sizeof(H2DRec);
-    hipError_t e = hipMemcpyAsync(inbox, host, total, hipMemcpyHostToDevice, stream);
+    hipError_t e = hipMemcpyAsync(inbox, stage.host, total, hipMemcpyHostToDevice, stage.stream);
     if (e == hipSuccess)
-        e = launch_h2d_scatter(inbox, recsOff, (int)recs.size(), stream);
+        e = launch_h2d_scatter(inbox, recsOff, (int)recs.size(), stage.stream);
     recs.clear();
     used = 0;
     inFlight = true;
     return e;
 }
-namespace
+hipError_t H2DBatch::finish()
 {
-// open for the duration of one borrower's lwhip_create: the stage / inbox pair comes out of a per-device pool
-struct H2DBatchScope
+    if (!stage.host)
+        return hipSuccess;
+    const hipError_t e = flush();
+    const hipError_t e2 = hipStreamSynchronize(stage.stream);
+    inFlight = false;
+    return e != hipSuccess ? e : e2;
+}
+void H2DBatch::close()
 {
-    H2DBatch b;
-    int device = 0;
-    bool open = false;
-    void begin(int dev, hipStream_t stream)
-    {
-        device = dev;
-        H2DPair pr;
-        {
-            std::lock_guard<std::mutex> g(g_h2dMutex);
-            auto& v = h2d_pairs()[dev];
-            if (!v.empty())
-            {
-                pr = v.back();
-                v.pop_back();
-            }
-        }
-        if (!pr.host)
-        {
-            if (hipHostMalloc((void**)&pr.host, H2D_BATCH_CAP, hipHostMallocDefault) != hipSuccess
-                || hipMalloc((void**)&pr.inbox, H2D_BATCH_CAP) != hipSuccess)
-            {
-                (void)hipGetLastError();
-                if (pr.host)
-                    (void)hipHostFree(pr.host);
-                return; // (no batch: the ordinary copies)
-            }
-        }
-        b.host = pr.host;
-        b.inbox = pr.inbox;
-        b.cap = H2D_BATCH_CAP;
-        b.stream = stream;
-        h2d_batch() = &b;
-        open = true;
-    }
-    // what was gathered goes out; the stage is free again when the stream has drained
-    hipError_t finish()
-    {
-        if (!open)
-            return hipSuccess;
-        hipError_t e = b.flush();
-        const hipError_t e2 = hipStreamSynchronize(b.stream);
-        b.inFlight = false;
-        return e != hipSuccess ? e : e2;
-    }
-    ~H2DBatchScope()
-    {
-        if (!open)
-            return;
-        h2d_batch() = nullptr;
-        if (b.inFlight || !b.recs.empty())
-            (void)hipStreamSynchronize(b.stream); // (an error path: nothing of the stage may still be in flight)
-        std::lock_guard<std::mutex> g(g_h2dMutex);
-        h2d_pairs()[device].push_back(H2DPair{ b.host, b.inbox });
-    }
-};
+    stage.release(); // (waits for the stream: the inbox is free then too)
+    recs.clear();
+    used = 0;
+    inFlight = false;
+    if (!inbox)
+        return;
+    std::lock_guard<std::mutex> g(g_inboxMutex);
+    h2d_inboxes()[device].push_back(inbox);
+    inbox = nullptr;
 }
 
 int host_block_init(lwhip_context* c)
@@ -377,9 +386,9 @@ int host_block_init(lwhip_context* c)
     const size_t nChange = (size_t)2 * std::max(nActive, 1) * (size_t)stat_eq_blocks(std::max((int)c->prob.Nspace, 1), std::min(maxNl, 64)) + 16;
     c->hostBlockBytes = HB_CHANGE + nChange * sizeof(double);
     unsigned char* dev = nullptr;
-    c->hostBlock = (unsigned char*)pinned_acquire(c->device, c->hostBlockBytes, (void**)&dev);
+    c->hostBlock = (unsigned char*)pinned_acquire(c->device, c->hostBlockBytes, (void**)&dev, true);
     if (!c->hostBlock || !dev)
-        return fail(LWHIP_ERR_DEVICE, "lwhip_create: hipHostMalloc of the context's host block failed");
+        return fail(LWHIP_ERR_DEVICE, "lwhip_create: no page-locked memory for the context's host block");
     std::memset(c->hostBlock, 0, c->hostBlockBytes);
     std::memcpy(c->hostBlock + HB_CANARY, &HB_CANARY_WORD, sizeof HB_CANARY_WORD);
     c->tailMapped = (double*)(c->hostBlock + HB_TAIL);
@@ -401,7 +410,7 @@ int host_block_init(lwhip_context* c)
     return LWHIP_OK;
 }
 
-// (the destructor has waited for the stream and the null stream)
+// (the destructor has waited for the stream)
 void host_block_release(lwhip_context* c)
 {
     if (!c->hostBlock)
@@ -488,20 +497,10 @@ int fingerprint_J_enqueue(lwhip_context* c)
     const size_t n = (size_t)c->Nla * c->Ns;
     const size_t nb = (n + LWHIP_FP_BLOCK - 1) / LWHIP_FP_BLOCK;
     if (c->fpSums.n < nb * 16)
-        HIP_TRY(c->fpSums.alloc(nb * 16));
-    if (c->fpPinnedN < nb * 16)
-    {
-        if (c->fpPinned)
-        {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            HIP_TRY(hipHostFree(c->fpPinned));
-        }
-        c->fpPinned = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&c->fpPinned, nb * 16 * sizeof(unsigned long long), hipHostMallocDefault));
-        c->fpPinnedN = nb * 16;
-    }
+        HIP_TRY(c->fpSums.alloc(c->mem, nb * 16));
+    HIP_TRY(c->fpPinned.reserve(c->device, nb * 16 * sizeof(unsigned long long), c->stream));
     HIP_TRY(launch_fp_blocks(c->J.p, n, c->fpSums.p, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->fpPinned, c->fpSums.p, nb * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->fpPinned.host, c->fpSums.p, nb * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     return LWHIP_OK;
 }
 // (after the stream has been waited for)
@@ -511,7 +510,7 @@ void fingerprint_J_fold(lwhip_context* c, const void* p)
     const size_t nb = (n + LWHIP_FP_BLOCK - 1) / LWHIP_FP_BLOCK;
     std::vector<uint64_t> hashes(nb);
     for (size_t b = 0; b < nb; ++b)
-        hashes[b] = lwhip_fp_block_fold((const uint64_t*)c->fpPinned + b * 16, std::min<size_t>(LWHIP_FP_BLOCK, n - b * LWHIP_FP_BLOCK),
+        hashes[b] = lwhip_fp_block_fold(c->fpPinned.as<const uint64_t>() + b * 16, std::min<size_t>(LWHIP_FP_BLOCK, n - b * LWHIP_FP_BLOCK),
                                         (uint64_t)(b * LWHIP_FP_BLOCK));
     c->fpJValue = lwhip_fp_array_fold(hashes.data(), nb, p, n);
     c->fpJPtr = p;
@@ -547,10 +546,10 @@ int lwhip_peer_window(lwhip_context* c, void** devPtr, size_t* bytes)
                 HIP_TRY(hipMalloc((void**)&c->peerWin, c->peerWinBytes));
             }
         }
-        HIP_TRY(hipMemset(c->peerWin, 0, c->peerWinBytes));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        HIP_TRY(c->peerArrive.alloc_zero(1));
-        HIP_TRY(hipStreamSynchronize(nullptr));
+        // (cleared before another rank can learn its address: lwhip_peer_export / the caller's exchange come after this call)
+        HIP_TRY(hipMemsetAsync(c->peerWin, 0, c->peerWinBytes, c->stream));
+        HIP_TRY(c->peerArrive.alloc_zero(c->mem, 1));
+        HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (devPtr)
         *devPtr = c->peerWin;
@@ -779,7 +778,11 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
     c->Nrays = prob->Nrays;
     c->Natom = prob->Natom;
 
+    // (declared before `bail`: the gathered upload, if one opens below, is closed while the context's stream is still its own)
+    DevArena arena;
+    H2DBatch h2d;
     auto bail = [&](int code) {
+        h2d.close();
         if (c->tablesFrom)
             c->tablesFrom->borrowers--;
         delete c;
@@ -817,18 +820,14 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
     }
     // One arena for everything a borrower allocates between here and the end of its first upload (DevArena, lwhip_host.h); the
     // owner counts what the same path takes in its own case.  (The structure tables that borrowers share are outside: see
-    // DevBuf::upload_or_borrow.)
-    DevArena arena;
-    const bool plainAllocs = DevBuf<double>::poison_on() || DevBuf<double>::sentinel_on() || std::getenv("LWHIP_TRACE_ALLOC") != nullptr;
+    // DevBuf::upload_or_borrow.)  Its clearing fill, like every fill and copy of the set-up, is queued on the context's stream.
+    const bool plainAllocs = poison_on() || sentinel_on() || std::getenv("LWHIP_TRACE_ALLOC") != nullptr;
     if (!plainAllocs)
     {
         if (c->tablesFrom && c->tablesFrom->stateBytes > 0)
         {
             arena.size = c->tablesFrom->stateBytes + (64u << 10);
-            // (a batch column's uploads all run on its own stream -- the gathered upload below --, so its clearing fill does too;
-            // otherwise the null stream, which the synchronous table uploads of DevBuf::upload follow)
-            if (hipMalloc((void**)&arena.base, arena.size) == hipSuccess
-                && hipMemsetAsync(arena.base, 0, arena.size, c->batchHint > 1 ? c->stream : nullptr) == hipSuccess)
+            if (hipMalloc((void**)&arena.base, arena.size) == hipSuccess && hipMemsetAsync(arena.base, 0, arena.size, c->stream) == hipSuccess)
                 c->stateArena = arena.base;
             else
             {
@@ -841,15 +840,11 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
         else if (!c->tablesFrom)
             arena.counting = true;
     }
-    struct ArenaScope
-    {
-        explicit ArenaScope(DevArena* a) { devbuf_arena() = a; }
-        ~ArenaScope() { devbuf_arena() = nullptr; }
-    } arenaScope((arena.base || arena.counting) ? &arena : nullptr);
-    // ... and, for a column of a batch, one gathered upload (H2DBatch, lwhip_host.h) on the column's stream
-    H2DBatchScope h2d;
-    if (arena.base && c->batchHint > 1 && dbg_env_int("LWHIP_H2D_BATCH", 1) != 0)
-        h2d.begin(c->device, c->stream);
+    if (arena.base || arena.counting)
+        c->mem.arena = &arena;
+    // ... and, for a column of a batch, one gathered upload (H2DBatch, lwhip_host.h)
+    if (arena.base && c->batchHint > 1 && dbg_env_int("LWHIP_H2D_BATCH", 1) != 0 && h2d.open(c->device, c->stream))
+        c->mem.batch = &h2d;
     st = build_tables(c);
     if (st != LWHIP_OK)
     {
@@ -859,25 +854,9 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
     if (c->tablesFrom)
         c->tablesFrom->borrowers++;
     const auto t1 = now();
-    {
-        // (the state allocations' clearing fills queue up on the null stream; one wait for all of them)
-        struct Defer
-        {
-            Defer() { ++devbuf_defer_fill_sync(); }
-            ~Defer() { --devbuf_defer_fill_sync(); }
-        } defer;
-        struct Skip
-        {
-            const bool on;
-            explicit Skip(bool o) : on(o) { devbuf_skip_safety_clear() += on ? 1 : 0; }
-            ~Skip() { devbuf_skip_safety_clear() -= on ? 1 : 0; }
-        } skip(c->tablesFrom != nullptr);
-        st = alloc_state(c);
-        // (a batch column whose allocations all came out of its arena has queued nothing on the null stream -- and waiting for the
-        // null stream means waiting for every other creating thread's stream)
-        if (!(h2d_batch() && !arena.overflowed) && hipStreamSynchronize(nullptr) != hipSuccess && st == LWHIP_OK)
-            st = fail(LWHIP_ERR_DEVICE, "lwhip_create: clearing the state allocations failed");
-    }
+    c->mem.skipSafetyClear = c->tablesFrom != nullptr;
+    st = alloc_state(c);
+    c->mem.skipSafetyClear = false;
     if (st != LWHIP_OK)
         return bail(st);
     st = build_sweep_args(c);
@@ -892,7 +871,8 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
         return bail(st);
     if (arena.counting)
         c->stateBytes = arena.counted;
-    devbuf_arena() = nullptr;
+    c->mem.arena = nullptr;
+    c->mem.batch = nullptr;
     if (h2d.finish() != hipSuccess)
         return bail(fail(LWHIP_ERR_DEVICE, "lwhip_create: the gathered upload of a batch column failed"));
     if (timing)
@@ -928,13 +908,14 @@ int lwhip_destroy(lwhip_context* c)
         c->tablesFrom->borrowers--;
         c->tablesFrom = nullptr;
     }
-    if (c->lsDbgHost && !c->laneSweep)
+    const double* dbg = c->lsDbg.as<const double>();
+    if (dbg && !c->laneSweep)
     {
         // -DRM_TIMING build of the march: per tile kind the count and the mean / max clocks of a direction's march and of the post-pass
         std::map<int, std::array<double, 6>> kinds; // n, sum march, max march, sum post, max post, -
         for (int t = 0; t < c->nTiles; ++t)
         {
-            const double* o = c->lsDbgHost + (size_t)t * 8;
+            const double* o = dbg + (size_t)t * 8;
             auto& k = kinds[(int)o[0]];
             k[0] += 1.0;
             k[1] += 0.5 * (o[1] + o[2]);
@@ -945,23 +926,21 @@ int lwhip_destroy(lwhip_context* c)
         for (const auto& kv : kinds)
             std::fprintf(stderr, "march clocks, tiles of kind (%d lines, %d mixed): %d tiles, march mean %.0f max %.0f, post-pass mean %.0f max %.0f\n",
                          kv.first / 10, kv.first % 10, (int)kv.second[0], kv.second[1] / kv.second[0], kv.second[2], kv.second[3] / kv.second[0], kv.second[4]);
-        (void)hipHostFree(c->lsDbgHost);
-        c->lsDbgHost = nullptr;
     }
-    if (c->lsDbgHost)
+    else if (dbg)
     {
         double sum[8] = { 0 }, mx = 0.0;
         for (int t = 0; t < c->nTiles; ++t)
         {
             for (int q = 0; q < 8; ++q)
-                sum[q] += c->lsDbgHost[(size_t)t * 8 + q];
-            mx = std::max(mx, c->lsDbgHost[(size_t)t * 8 + 7]);
+                sum[q] += dbg[(size_t)t * 8 + q];
+            mx = std::max(mx, dbg[(size_t)t * 8 + 7]);
         }
         {
             std::map<int, std::array<double, 3>> kinds;
             for (int t = 0; t < c->nTiles; ++t)
             {
-                const double tot = c->lsDbgHost[(size_t)t * 8 + 7];
+                const double tot = dbg[(size_t)t * 8 + 7];
                 auto& k = kinds[(int)std::lround((tot - std::floor(tot)) * 100.0)];
                 k[0] += 1.0;
                 k[1] += std::floor(tot);
@@ -976,7 +955,7 @@ int lwhip_destroy(lwhip_context* c)
             int nw = 0;
             for (int b = 0; b < 4 * c->nTiles; ++b)
             {
-                const double* o = c->lsDbgHost + (size_t)c->nTiles * 8 + (size_t)b * 4;
+                const double* o = dbg + (size_t)c->nTiles * 8 + (size_t)b * 4;
                 if (o[1] > 0.0)
                 {
                     ++nw;
@@ -993,7 +972,6 @@ int lwhip_destroy(lwhip_context* c)
         std::fprintf(stderr, "lane sweep phase clocks per tile (mean): setup %.0f gather %.0f stencils %.0f coefficients %.0f scan %.0f rates %.0f finish %.0f total %.0f (max %.0f) over %d tiles\n",
                      sum[0] / c->nTiles, sum[1] / c->nTiles, sum[2] / c->nTiles, sum[3] / c->nTiles, sum[4] / c->nTiles, sum[5] / c->nTiles,
                      sum[6] / c->nTiles, sum[7] / c->nTiles, mx, c->nTiles);
-        (void)hipHostFree(c->lsDbgHost);
     }
     delete c;
     return LWHIP_OK;
@@ -1219,12 +1197,11 @@ int lwhip_fs_finalise(lwhip_context* c, lwhip_iter_result* res)
     if (res)
     {
         const double* tail = c->red.p + (size_t)c->Ntrans * 4 * c->Ns;
-        if (!c->gatherPinned)
-            HIP_TRY(hipHostMalloc((void**)&c->gatherPinned, c->gatherHost.size() * sizeof(double), hipHostMallocDefault));
-        HIP_TRY(hipMemcpyAsync(c->gatherPinned, tail, c->gatherHost.size() * sizeof(double),
+        HIP_TRY(c->gatherPinned.reserve(c->device, c->gatherHost.size() * sizeof(double), c->stream));
+        HIP_TRY(hipMemcpyAsync(c->gatherPinned.host, tail, c->gatherHost.size() * sizeof(double),
                                hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        std::memcpy(c->gatherHost.data(), c->gatherPinned, c->gatherHost.size() * sizeof(double));
+        std::memcpy(c->gatherHost.data(), c->gatherPinned.host, c->gatherHost.size() * sizeof(double));
         // max over shards, first (lowest) wavelength index on ties: max_idx, Constants.hpp:114-125
         double best = -1.0;
         int bestIdx = 0;
@@ -1361,7 +1338,7 @@ int stat_equil_impl(lwhip_context* c, int atom, bool wait, double* dPops, int32_
         return LWHIP_OK;
     if (c->statEqKey != atom || c->statEqAtoms.n < atoms.size())
     {
-        HIP_TRY(c->statEqAtoms.upload(atoms));
+        HIP_TRY(c->statEqAtoms.upload(c->mem, atoms));
         c->statEqKey = atom;
     }
     if (wait)
@@ -1456,8 +1433,8 @@ int lwhip_ng_configure(lwhip_context* c, int Norder, int Nperiod, int Ndelay)
     c->ngAtomsHost = atoms;
     if (atoms.empty())
         return LWHIP_OK;
-    HIP_TRY(c->ngAtoms.upload(atoms));
-    HIP_TRY(c->ngHistory.alloc((size_t)hist));
+    HIP_TRY(c->ngAtoms.upload(c->mem, atoms));
+    HIP_TRY(c->ngHistory.alloc(c->mem, (size_t)hist));
     HIP_TRY(hipMemsetAsync(c->ngHistory.p, 0, (size_t)hist * sizeof(double), c->stream));
     for (const NgAtom& at : atoms)
         HIP_TRY(hipMemcpyAsync(c->ngHistory.p + at.histOff, c->n.p + at.nOff, (size_t)at.len * sizeof(double),
@@ -1553,7 +1530,7 @@ int lwhip_time_dep_update(lwhip_context* c, int atom, const double* nOld, double
     const lwhip_atom& a = c->atoms[atom];
     const size_t cnt = (size_t)a.Nlevel * c->Ns;
     if (c->popScratch.n < cnt)
-        HIP_TRY(c->popScratch.alloc(cnt));
+        HIP_TRY(c->popScratch.alloc(c->mem, cnt));
     HIP_TRY(hipMemcpyAsync(c->popScratch.p, nOld, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->status.p, 0, sizeof(int32_t), c->stream));
     HIP_TRY(launch_time_dep(a.Nlevel, c->Ns, c->kLo, c->kHi < 0 ? c->Ns : c->kHi, c->n.p + (size_t)c->levelOff[atom] * c->Ns, c->popScratch.p,
@@ -1610,9 +1587,9 @@ int lwhip_nr_post_update(lwhip_context* c, const lwhip_nr_args* args)
     const bool fdC = args->dC != nullptr;
     const size_t need = (size_t)eq + 2 * Ns + (timeDep ? (size_t)eq * Ns : 0) + (fdC ? (size_t)dcRows * Ns : 0);
     if (c->popScratch.n < need)
-        HIP_TRY(c->popScratch.alloc(need));
+        HIP_TRY(c->popScratch.alloc(c->mem, need));
     if (c->nrAtoms.n < atoms.size())
-        HIP_TRY(c->nrAtoms.alloc(atoms.size()));
+        HIP_TRY(c->nrAtoms.alloc(c->mem, atoms.size()));
     HIP_TRY(hipMemcpyAsync(c->nrAtoms.p, atoms.data(), atoms.size() * sizeof(NrAtom), hipMemcpyHostToDevice, c->stream));
     double* dStages = c->popScratch.p;
     double* dNe = dStages + eq;
@@ -1645,7 +1622,7 @@ int lwhip_nr_post_update(lwhip_context* c, const lwhip_nr_args* args)
         std::vector<int32_t> tt((size_t)std::max(c->Ntrans, 1), 0);
         for (int tr = 0; tr < c->Ntrans; ++tr)
             tt[tr] = c->trans[tr].t.type;
-        HIP_TRY(c->transType.upload(tt));
+        HIP_TRY(c->transType.upload(c->mem, tt));
     }
     HIP_TRY(hipMemsetAsync(c->status.p, 0, sizeof(int32_t), c->stream));
     NrArgs a{};
@@ -1700,8 +1677,8 @@ int voigt_line_list(lwhip_context* c, std::vector<VoigtLineArgs>& out)
     const size_t nLine = (size_t)std::max(c->Nline, 1);
     if (!c->is2d && c->wphiScratch.n < nLine * slices * c->Ns)
     {
-        HIP_TRY(c->wphiScratch.alloc(nLine * slices * c->Ns));
-        HIP_TRY(c->wphiTicket.alloc(nLine * tiles));
+        HIP_TRY(c->wphiScratch.alloc(c->mem, nLine * slices * c->Ns));
+        HIP_TRY(c->wphiTicket.alloc(c->mem, nLine * tiles));
         HIP_TRY(hipMemsetAsync(c->wphiTicket.p, 0, c->wphiTicket.n * sizeof(int), c->stream));
     }
     size_t q = 0;
@@ -1750,7 +1727,7 @@ static int compute_profiles_impl(lwhip_context* c)
     {
         // (the copy is queued behind the previous launch pair that read the buffer: same stream)
         if (c->voigtList.n < list.size())
-            HIP_TRY(c->voigtList.alloc(list.size()));
+            HIP_TRY(c->voigtList.alloc(c->mem, list.size()));
         HIP_TRY(hipMemcpyAsync(c->voigtList.p, list.data(), list.size() * sizeof(VoigtLineArgs), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(launch_voigt_lines(c->voigtList.p, list.data(), (int)list.size(), c->stream));
     }
@@ -1787,9 +1764,9 @@ int lwhip_set_zplane_outputs(lwhip_context* c, double* zPlaneDown, double* zPlan
     c->zDownHost = zPlaneDown;
     c->zUpHost = zPlaneUp;
     if (zPlaneDown && c->zDown.n < n)
-        HIP_TRY(c->zDown.alloc(n));
+        HIP_TRY(c->zDown.alloc(c->mem, n));
     if (zPlaneUp && c->zUp.n < n)
-        HIP_TRY(c->zUp.alloc(n));
+        HIP_TRY(c->zUp.alloc(c->mem, n));
     if (!zPlaneDown)
         c->zDown.release();
     if (!zPlaneUp)
@@ -1845,7 +1822,7 @@ int lwhip_j_snapshot(lwhip_context* c)
         return fail(LWHIP_ERR_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
     if (c->Jsnap.n < c->J.n)
-        HIP_TRY(c->Jsnap.alloc(c->J.n, false));
+        HIP_TRY(c->Jsnap.alloc(c->mem, c->J.n, false));
     HIP_TRY(hipMemcpyAsync(c->Jsnap.p, c->J.p, c->J.n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return LWHIP_OK;
 }

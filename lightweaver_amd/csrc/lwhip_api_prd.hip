@@ -23,7 +23,7 @@ int lwhip_prd_pack(lwhip_context* c, void** devPtr, size_t* count)
     const size_t Ns = c->Ns;
     const size_t n = (size_t)std::max<int64_t>(c->prdRowsTot, 1) * Ns;
     if (c->prdJ.n < n)
-        HIP_TRY(c->prdJ.alloc(n));
+        HIP_TRY(c->prdJ.alloc(c->mem, n));
     if (c->worldSize > 1)
         HIP_TRY(hipMemsetAsync(c->prdJ.p, 0, n * sizeof(double), c->stream)); // rows of other shards: the all-reduce sums
     for (size_t q = 0; q < c->prdLines.size(); ++q)
@@ -78,15 +78,15 @@ int lwhip_prd_partial(lwhip_context* c)
                                            + std::to_string(c->trans[tr].atom));
     if (c->prdChange.n < (size_t)Nprd * Ns * PRD_MAX_SLICES)
     {
-        HIP_TRY(c->prdChange.alloc((size_t)Nprd * Ns * PRD_MAX_SLICES));
-        HIP_TRY(c->prdChangeIdx.alloc((size_t)Nprd * Ns * PRD_MAX_SLICES));
+        HIP_TRY(c->prdChange.alloc(c->mem, (size_t)Nprd * Ns * PRD_MAX_SLICES));
+        HIP_TRY(c->prdChangeIdx.alloc(c->mem, (size_t)Nprd * Ns * PRD_MAX_SLICES));
     }
     // transposed J of every line side by side (the lines' scattering integrals run in one launch)
     std::vector<size_t> jtOff(Nprd + 1, 0);
     for (int q = 0; q < Nprd; ++q)
         jtOff[q + 1] = jtOff[q] + (size_t)(c->trans[c->prdLines[q]].t.Nred - c->trans[c->prdLines[q]].t.Nblue) * Ns;
     if (c->prdJt.n < jtOff[Nprd])
-        HIP_TRY(c->prdJt.alloc(jtOff[Nprd]));
+        HIP_TRY(c->prdJt.alloc(c->mem, jtOff[Nprd]));
     std::vector<PrdLineArgs> lineArgs(Nprd);
     // PRD section of the reduce tail: [world][Nprd] x (max |d rho / rho|, flattened index)
     double* prdTail = c->red.p + (size_t)c->Ntrans * 4 * Ns + 2 * (size_t)c->worldSize;
@@ -160,7 +160,7 @@ int lwhip_prd_partial(lwhip_context* c)
                 c->gII[tr] = std::make_unique<DevBuf<double>>();
             if (c->gII[tr]->n < need)
             {
-                if (c->gII[tr]->alloc(need) != hipSuccess)
+                if (c->gII[tr]->alloc(c->mem, need) != hipSuccess)
                 {
                     (void)hipGetLastError(); // out of memory for the cache: recompute every time
                     c->gII[tr].reset();
@@ -194,7 +194,7 @@ int lwhip_prd_partial(lwhip_context* c)
         HIP_TRY(hipStreamSynchronize(c->stream)); // the previous copy may still be read
         c->prdArgsHost = lineArgs;
         if (c->prdArgsDev.n < (size_t)Nprd)
-            HIP_TRY(c->prdArgsDev.alloc(Nprd));
+            HIP_TRY(c->prdArgsDev.alloc(c->mem, Nprd));
         HIP_TRY(hipMemcpyAsync(c->prdArgsDev.p, c->prdArgsHost.data(), (size_t)Nprd * sizeof(PrdLineArgs), hipMemcpyHostToDevice,
                                c->stream));
     }
@@ -296,16 +296,15 @@ int lwhip_prd_finalise(lwhip_context* c, double* dRho, int32_t* dRhoMaxIdx, doub
     if (piped)
     {
         // (queued: the slot of this sub-iteration; lwhip_redistribute_prd waits once for the whole group and reads them)
-        HIP_TRY(hipMemcpyAsync(c->prdPinnedPipe + (size_t)((c->prdPipeIter - 1) % PRD_PIPE_DEPTH) * nTail,
+        HIP_TRY(hipMemcpyAsync(c->prdPinnedPipe.as<double>() + (size_t)((c->prdPipeIter - 1) % PRD_PIPE_DEPTH) * nTail,
                                c->red.p + (size_t)c->Ntrans * 4 * Ns, nTail * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         return LWHIP_OK;
     }
-    if (!c->prdPinned)
-        HIP_TRY(hipHostMalloc((void**)&c->prdPinned, nTail * sizeof(double), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(c->prdPinned, c->red.p + (size_t)c->Ntrans * 4 * Ns, nTail * sizeof(double),
+    HIP_TRY(c->prdPinned.reserve(c->device, nTail * sizeof(double), c->stream));
+    HIP_TRY(hipMemcpyAsync(c->prdPinned.host, c->red.p + (size_t)c->Ntrans * 4 * Ns, nTail * sizeof(double),
                            hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    prd_read_results(c, c->prdPinned, dRho, dRhoMaxIdx, dJMax, dJMaxIdx);
+    prd_read_results(c, c->prdPinned.as<double>(), dRho, dRhoMaxIdx, dJMax, dJMaxIdx);
     return LWHIP_OK;
 }
 
@@ -400,19 +399,9 @@ int lwhip_redistribute_prd(lwhip_context* c, int maxIter, double tol, lwhip_prd_
     if (piped)
     {
         const size_t nTail = 2 * (size_t)c->worldSize * (1 + Nprd);
-        if (c->prdPinnedPipeN < (size_t)PRD_PIPE_DEPTH * nTail)
-        {
-            if (c->prdPinnedPipe)
-            {
-                HIP_TRY(hipStreamSynchronize(c->stream)); // (no queued copy may still aim at the block that goes)
-                HIP_TRY(hipHostFree(c->prdPinnedPipe));
-            }
-            c->prdPinnedPipe = nullptr;
-            c->prdPinnedPipeN = (size_t)PRD_PIPE_DEPTH * nTail;
-            HIP_TRY(hipHostMalloc((void**)&c->prdPinnedPipe, c->prdPinnedPipeN * sizeof(double), hipHostMallocDefault));
-        }
+        HIP_TRY(c->prdPinnedPipe.reserve(c->device, (size_t)PRD_PIPE_DEPTH * nTail * sizeof(double), c->stream));
         if (c->prdCtl.n < 4)
-            HIP_TRY(c->prdCtl.alloc_zero(4));
+            HIP_TRY(c->prdCtl.alloc_zero(c->mem, 4));
         HIP_TRY(hipMemsetAsync(c->prdCtl.p, 0, 4 * sizeof(int32_t), c->stream));
         int32_t* ctlHost = c->prdCtlHost; // (a window of the context's host block)
         int st = LWHIP_OK;
@@ -441,7 +430,7 @@ int lwhip_redistribute_prd(lwhip_context* c, int maxIter, double tol, lwhip_prd_
                 const int it = iter + j + 1;
                 double dJ = 0.0;
                 int32_t dJIdx = 0;
-                prd_read_results(c, c->prdPinnedPipe + (size_t)((it - 1) % PRD_PIPE_DEPTH) * nTail, dRho.data(), dRhoIdx.data(), &dJ, &dJIdx);
+                prd_read_results(c, c->prdPinnedPipe.as<double>() + (size_t)((it - 1) % PRD_PIPE_DEPTH) * nTail, dRho.data(), dRhoIdx.data(), &dJ, &dJIdx);
                 record(it, dJ, dJIdx);
                 if (stopAt == it)
                 {

@@ -11,7 +11,7 @@ struct lwhip_batch
     DevBuf<ReduceArgs> rList;
     DevBuf<ApplyArgs> aList;
     DevBuf<double> tail;       // [n][2] (dJMax, idx) of every column
-    double* tailPinned = nullptr;
+    PinnedBlock tailPinned;
     std::vector<ApplyArgs> aHost;
     double aCrsw = 0.0;        // what the device copy of the apply blocks was built with
     bool aValid = false;
@@ -46,7 +46,7 @@ static int batch_compute_profiles(lwhip_batch* b, bool all)
         if (b->voigtList.n < list.size())
         {
             HIP_TRY(hipStreamSynchronize(c0->stream)); // nothing may still read the buffer about to be replaced
-            HIP_TRY(b->voigtList.alloc(list.size()));
+            HIP_TRY(b->voigtList.alloc(c0->mem, list.size()));
         }
         HIP_TRY(hipMemcpyAsync(b->voigtList.p, list.data(), list.size() * sizeof(VoigtLineArgs), hipMemcpyHostToDevice, c0->stream));
         // the launch geometry allows 65 535 entries per grid dimension
@@ -72,7 +72,7 @@ static int batch_compute_profiles(lwhip_batch* b, bool all)
         if (b->retileList.n < rl.size())
         {
             HIP_TRY(hipStreamSynchronize(c0->stream));
-            HIP_TRY(b->retileList.alloc(rl.size()));
+            HIP_TRY(b->retileList.alloc(c0->mem, rl.size()));
         }
         HIP_TRY(hipMemcpyAsync(b->retileList.p, rl.data(), rl.size() * sizeof(RetileArgs), hipMemcpyHostToDevice, c0->stream));
         for (size_t off = 0; off < rl.size(); off += 32768)
@@ -128,7 +128,7 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
     b->ownStreams = before;
     std::vector<const TileArgs*> ap(n);
     std::vector<ReduceArgs> rl(n);
-    HIP_TRY(b->tail.alloc((size_t)2 * n));
+    HIP_TRY(b->tail.alloc(c0->mem, (size_t)2 * n));
     for (int i = 0; i < n; ++i)
     {
         ap[i] = ctxs[i]->dtargs.p;
@@ -140,9 +140,9 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
             HIP_TRY(hipMemsetAsync(ctxs[i]->red8.p, 0, ctxs[i]->red8.n * sizeof(double), c0->stream));
         ctxs[i]->red8Clean = true;
     }
-    HIP_TRY(b->apList.upload(ap));
-    HIP_TRY(b->rList.upload(rl));
-    HIP_TRY(b->aList.alloc((size_t)n));
+    HIP_TRY(b->apList.upload(c0->mem, ap));
+    HIP_TRY(b->rList.upload(c0->mem, rl));
+    HIP_TRY(b->aList.alloc(c0->mem, (size_t)n));
     b->aHost.resize(n);
     {
         std::vector<StatEqArgs> sl(n);
@@ -166,7 +166,7 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
             }
             if (!atoms.empty())
             {
-                HIP_TRY(c->statEqAtoms.upload(atoms));
+                HIP_TRY(c->statEqAtoms.upload(c->mem, atoms));
                 c->statEqKey = -1;
             }
             StatEqArgs sa{};
@@ -189,9 +189,9 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
             else if (sa.Natoms != b->se0.Natoms || maxNl != b->seMaxNl)
                 return fail(LWHIP_ERR_INVALID, "batch_create: the columns must share their active atoms");
         }
-        HIP_TRY(b->seList.upload(sl));
+        HIP_TRY(b->seList.upload(c0->mem, sl));
     }
-    HIP_TRY(hipHostMalloc((void**)&b->tailPinned, (size_t)2 * n * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(b->tailPinned.reserve(c0->device, (size_t)2 * n * sizeof(double), c0->stream));
     *out = b.release();
     return LWHIP_OK;
 }
@@ -205,11 +205,10 @@ void lwhip_batch_destroy(lwhip_batch* b)
     {
         (void)hipSetDevice(b->ctxs[0]->device);
         (void)hipStreamSynchronize(b->ctxs[0]->stream);
+        b->tailPinned.release();
         for (size_t i = 0; i < b->ctxs.size() && i < b->ownStreams.size(); ++i)
             b->ctxs[i]->stream = b->ownStreams[i];
     }
-    if (b->tailPinned)
-        (void)hipHostFree(b->tailPinned);
     delete b;
 }
 
@@ -270,13 +269,13 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
         HIP_TRY(launch_apply(b->aHost[0], c0->stream, b->aList.p, n));
     if (results)
     {
-        HIP_TRY(hipMemcpyAsync(b->tailPinned, b->tail.p, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+        HIP_TRY(hipMemcpyAsync(b->tailPinned.host, b->tail.p, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
         HIP_TRY(hipStreamSynchronize(c0->stream));
         for (int i = 0; i < n; ++i)
         {
             results[i].updatedJ = 1;
-            results[i].dJMax = b->tailPinned[2 * i];
-            results[i].dJMaxIdx = (int32_t)b->tailPinned[2 * i + 1];
+            results[i].dJMax = b->tailPinned.as<double>()[2 * i];
+            results[i].dJMaxIdx = (int32_t)b->tailPinned.as<double>()[2 * i + 1];
         }
     }
     return LWHIP_OK;

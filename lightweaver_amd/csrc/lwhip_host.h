@@ -45,24 +45,28 @@ int fail(int code, const std::string& msg);
             return fail(LWHIP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(err__));       \
     } while (0)
 
-// > 0: the clearing fills of DevBuf::alloc are queued, not waited for: whoever raised it synchronises the null stream before
-// anything touches the buffers (lwhip_create: 0.7 s less per 512 columns than a wait per allocation)
 inline bool debug_knobs_on(); // (LWHIP_DEBUG=1: the diagnosis knobs below are read only then)
-inline int& devbuf_defer_fill_sync()
-{
-    static thread_local int depth = 0;
-    return depth;
-}
 
-// > 0: alloc(count) leaves out its safety-net clearing (alloc_zero still clears): the state buffers of a context made with
-// lwhip_create_like -- a column of a 1.5D batch: ~40 fills of a few KB each per column, a driver call apiece.  Every byte a
-// kernel reads of such a buffer is written first by an upload or a kernel (tests/test_padding.py runs the column batches under
-// the finite sentinel fills); the owner of the tables, and every ordinary context, keeps the net.
-inline int& devbuf_skip_safety_clear()
+// Page-locked host memory out of the library's one pool (lwhip_api.hip).  mapped: host-mapped and coherent, the device reaches it
+// through `dev` (the host block, the upload stage, LWHIP_LS_TIMING); otherwise a source or target of copies only.  The block goes
+// back to the pool only after `stream` -- the stream whose queued copies or kernels read or write it -- has drained: release()
+// waits for it, whatever path the owner leaves by.
+struct PinnedBlock
 {
-    static thread_local int depth = 0;
-    return depth;
-}
+    unsigned char* host = nullptr;
+    unsigned char* dev = nullptr;
+    size_t bytes = 0;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    // at least `need` bytes, used on `s` from now on (a smaller block goes back first)
+    hipError_t reserve(int device, size_t need, hipStream_t s, bool mapped = false);
+    void release();
+    template <typename U> U* as() const { return (U*)host; }
+    PinnedBlock() = default;
+    PinnedBlock(const PinnedBlock&) = delete;
+    PinnedBlock& operator=(const PinnedBlock&) = delete;
+    ~PinnedBlock() { release(); }
+};
 
 // The state allocations of a context made with lwhip_create_like come out of ONE device allocation (round 6): the owner of the
 // tables counts the bytes its own alloc_state asks for (count mode), a borrower gets an arena of that size, cleared with one
@@ -74,13 +78,19 @@ struct DevArena
     size_t size = 0, used = 0;
     size_t counted = 0;   // count mode: bytes asked for
     bool counting = false;
-    bool overflowed = false; // a piece did not fit and took the ordinary path (with its clearing fill on the null stream)
+    bool take(size_t bytes, void** p)
+    {
+        bytes = (bytes + 255) & ~(size_t)255;
+        if (counting)
+            counted += bytes;
+        if (counting || used + bytes > size)
+            return false;
+        *p = base + used;
+        used += bytes;
+        return true;
+    }
+    bool holds(const void* p) const { return !counting && (const unsigned char*)p >= base && (const unsigned char*)p < base + size; }
 };
-inline DevArena*& devbuf_arena()
-{
-    static thread_local DevArena* a = nullptr;
-    return a;
-}
 
 // Host-to-device copies of a batch column's creation, gathered (round 6): while a borrower of a 1.5D batch is created, every
 // upload -- the H2D macro, the argument blocks, DevBuf::upload -- is copied into ONE page-locked stage and described by a record;
@@ -89,31 +99,57 @@ inline DevArena*& devbuf_arena()
 // lock) and one synchronous hipMemcpy that waited 6 ms for the other creating threads' streams; now one copy and one launch.
 struct H2DBatch
 {
-    hipStream_t stream = nullptr;
-    unsigned char* host = nullptr;  // page-locked stage
-    unsigned char* inbox = nullptr; // its landing place on the device
-    size_t cap = 0, used = 0;
+    PinnedBlock stage;              // out of the pinned pool
+    unsigned char* inbox = nullptr; // its landing place on the device (a per-device pool of them, lwhip_api.hip)
+    int device = 0;
+    size_t used = 0;
     std::vector<H2DRec> recs;
     bool inFlight = false; // a flush was queued and the stage not yet known to be free again
-    long copies = 0;
+    bool open(int device, hipStream_t s); // false: no stage to be had (the ordinary copies)
     bool add(void* dst, const void* src, size_t bytes);
     hipError_t flush();
+    hipError_t finish(); // what was gathered goes out, and the stream drains
+    void close();        // the stage (after the stream has drained) and the inbox back to their pools
+    ~H2DBatch() { close(); }
 };
-inline H2DBatch*& h2d_batch()
+
+// Everything a context's allocations, fills and host-to-device copies go through (lwhip_context::mem): all of it is queued on
+// `stream`, the context's stream; the library queues nothing on the null stream.  The other fields are set only while
+// lwhip_create runs.
+struct DevMem
 {
-    static thread_local H2DBatch* b = nullptr;
-    return b;
-}
-// the copy every upload path calls: into the thread's batch when one is open on this stream, else the ordinary copy
-inline hipError_t h2d_copy(void* dst, const void* src, size_t bytes, hipStream_t stream)
-{
-    if (bytes == 0)
-        return hipSuccess;
-    H2DBatch* b = h2d_batch();
-    if (b && b->stream == stream && b->add(dst, src, bytes))
-        return hipSuccess;
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
-}
+    hipStream_t stream = nullptr;
+    DevArena* arena = nullptr;    // the borrower's arena, or the owner's count
+    // alloc(count) leaves out its safety-net clearing (alloc_zero still clears): the state buffers of a context made with
+    // lwhip_create_like -- a column of a 1.5D batch: ~40 fills of a few KB each per column, a driver call apiece.  Every byte a
+    // kernel reads of such a buffer is written first by an upload or a kernel (tests/test_padding.py runs the column batches
+    // under the finite sentinel fills); the owner of the tables, and every ordinary context, keeps the net.
+    bool skipSafetyClear = false;
+    H2DBatch* batch = nullptr;    // the open gathered upload
+    bool unstaged = false;        // a copy since the last settle() reads its source where it lies
+    // the one host-to-device copy: into the open gathered upload, else queued on the stream
+    hipError_t h2d(void* dst, const void* src, size_t bytes)
+    {
+        if (bytes == 0 || (batch && batch->add(dst, src, bytes)))
+            return hipSuccess;
+        unstaged = true;
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
+    }
+    // the sources of the copies queued so far may go once this has returned
+    hipError_t settle()
+    {
+        if (batch && !unstaged)
+            return hipSuccess;
+        unstaged = false;
+        return hipStreamSynchronize(stream);
+    }
+};
+
+// What a fresh allocation holds (lwhip_state.hip): init 0 nothing, 1 the safety net, 2 zeros -- or a diagnosis fill (below)
+hipError_t fresh_fill(DevMem& m, void* p, size_t count, size_t elem, bool fp64, int init, int seq);
+void released_fill(void* p, size_t bytes);
+bool poison_on();
+bool sentinel_on();
 
 template <typename T> struct DevBuf
 {
@@ -123,171 +159,42 @@ template <typename T> struct DevBuf
     uint64_t sig = 0; // content fingerprint of what upload() put there (see upload_or_borrow)
     // What a fresh allocation holds.  Round 4 handed out CLEARED memory because some kernel read bytes no upload had written and
     // hipMalloc returns whatever the pages' previous owner left there.  Round 5 located such reads with a FINITE sentinel
-    // (LWHIP_PAD_SENTINEL, below; NaN is swallowed by the fmin / fmax of the Steffen derivative, a finite 6.7e299 is not) and
-    // fixed them; what is left of the clearing is listed in DESIGN.md section 4.
-    //   alloc(count)         state buffer: every byte a kernel reads is written first by an upload or a kernel (asserted by the
-    //                        sentinel test); cleared all the same as a safety net unless LWHIP_NO_CLEAR is set
-    //   alloc(count, false)  the caller overwrites all of it at once (upload)
-    //   alloc_zero(count)    a buffer that is ACCUMULATED into, or whose zero is a value: always cleared
-    // LWHIP_PAD_SENTINEL=all | N | A-B (diagnosis): the fp64 state allocations numbered so (per context, LWHIP_TRACE_ALLOC prints
-    // the numbers) are filled with the sentinel instead of zeros -- a result that depends on never-written memory is then off by
-    // hundreds of orders of magnitude, deterministically (tests/test_padding.py runs the parity problems this way).
-    hipError_t alloc(size_t count, bool clear = true) { return alloc_impl(count, clear ? 1 : 0); }
-    hipError_t alloc_zero(size_t count) { return alloc_impl(count, 2); }
-    hipError_t alloc_impl(size_t count, int init)
+    // (LWHIP_PAD_SENTINEL, lwhip_state.hip; NaN is swallowed by the fmin / fmax of the Steffen derivative, a finite 6.7e299 is
+    // not) and fixed them; what is left of the clearing is listed in DESIGN.md section 4.
+    //   alloc(m, count)         state buffer: every byte a kernel reads is written first by an upload or a kernel (asserted by
+    //                           the sentinel test); cleared all the same as a safety net unless LWHIP_NO_CLEAR is set
+    //   alloc(m, count, false)  the caller overwrites all of it at once (upload)
+    //   alloc_zero(m, count)    a buffer that is ACCUMULATED into, or whose zero is a value: always cleared
+    // The fills are queued on m.stream, ahead of every copy and kernel that touches the buffer.
+    hipError_t alloc(DevMem& m, size_t count, bool clear = true) { return alloc_impl(m, count, clear ? 1 : 0); }
+    hipError_t alloc_zero(DevMem& m, size_t count) { return alloc_impl(m, count, 2); }
+    hipError_t alloc_impl(DevMem& m, size_t count, int init)
     {
         release();
         n = count;
         if (count == 0)
             return hipSuccess;
-        if (DevArena* ar = devbuf_arena())
+        if (m.arena && m.arena->take(count * sizeof(T), (void**)&p))
         {
-            const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-            if (ar->counting)
-                ar->counted += bytes;
-            else if (ar->used + bytes <= ar->size)
-            {
-                // (the arena was cleared as a whole: zeros serve alloc_zero and the safety net alike)
-                p = (T*)(ar->base + ar->used);
-                ar->used += bytes;
-                owned = false;
-                return hipSuccess;
-            }
-            else
-                ar->overflowed = true;
+            owned = false; // (the arena was cleared as a whole: zeros serve alloc_zero and the safety net alike)
+            return hipSuccess;
         }
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
         const int seq = alloc_seq()++;
-        static const bool noClear = debug_knobs_on() && std::getenv("LWHIP_NO_CLEAR") != nullptr; // (no safety net: what hipMalloc returns)
-        const bool sentinel = init == 1 && std::is_same<T, double>::value && sentinel_for(seq);
-        const char* what = "";
-        if (e == hipSuccess && poison_on() && init != 2)
-        {
-            // diagnosis (LWHIP_POISON=1): fresh allocations hold NaN / -1 (not alloc_zero's: their zero is a value -- counters,
-            // accumulators --, which round 6's peer-exchange arrival counter was the first to rely on without a clear of its own)
-            e = hipMemset(p, 0xFF, count * sizeof(T));
-            what = " poisoned";
-        }
-        else if (e == hipSuccess && sentinel)
-        {
-            // LWHIP_PAD_SENTINEL_VALUE=<x>: another fill value (a huge one is "optically thick" and may be as harmless as zero
-            // where a plausible one is not: tests/test_padding.py tries several)
-            static const char* sv = std::getenv("LWHIP_PAD_SENTINEL_VALUE");
-            if (sv && *sv)
-            {
-                std::vector<double> h(count * sizeof(T) / sizeof(double) + 1, std::atof(sv));
-                if (sv[0] == 'r')
-                {
-                    // "rand" / "randsign": DIFFERENT plausible values everywhere (log-uniform in 1e-8 .. 1e8) -- what stale data
-                    // of a destroyed context looks like.  A uniform fill cannot show a dependence that goes through a
-                    // difference or a ratio of two padding values (a slope, S = eta / chi): those are 0 and 1 for any constant.
-                    // (one table of 2^20 values, made once, laid end to end from an offset that follows the allocation number)
-                    const bool sign = std::strncmp(sv, "randsign", 8) == 0;
-                    static std::vector<double> table;
-                    if (table.empty())
-                    {
-                        table.resize(1u << 20);
-                        uint64_t x = 0x9E3779B97F4A7C15ull;
-                        for (auto& v : table)
-                        {
-                            x ^= x << 13;
-                            x ^= x >> 7;
-                            x ^= x << 17;
-                            const double u = (double)(x >> 11) * (1.0 / 9007199254740992.0);
-                            v = std::pow(10.0, 16.0 * u - 8.0) * ((sign && (x & 1)) ? -1.0 : 1.0);
-                        }
-                    }
-                    size_t off = ((size_t)(seq + 1) * 7919u) & (table.size() - 1);
-                    for (size_t i = 0; i < h.size();)
-                    {
-                        const size_t nCopy = std::min(h.size() - i, table.size() - off);
-                        std::memcpy(h.data() + i, table.data() + off, nCopy * sizeof(double));
-                        i += nCopy;
-                        off = 0;
-                    }
-                }
-                e = hipMemcpy(p, h.data(), count * sizeof(T), hipMemcpyHostToDevice);
-            }
-            else
-                e = hipMemsetD32((hipDeviceptr_t)p, (int)0x7E377E37, count * sizeof(T) / 4); // 0x7E377E377E377E37 = 6.7e299
-            what = " sentinel";
-        }
-        else if (e == hipSuccess && init == 1 && !std::is_same<T, double>::value && sentinel_on() && std::getenv("LWHIP_PAD_SENTINEL_INT"))
-        {
-            // (the other state allocations -- index and argument tables -- hold this 32-bit word: stale but valid-looking
-            // indices are what neither zeros nor the 0xFF of LWHIP_POISON imitate)
-            e = hipMemset(p, 0, count * sizeof(T));
-            if (e == hipSuccess && count * sizeof(T) >= 4)
-                e = hipMemsetD32((hipDeviceptr_t)p, std::atoi(std::getenv("LWHIP_PAD_SENTINEL_INT")), count * sizeof(T) / 4);
-            what = " int-sentinel";
-        }
-        else if (e == hipSuccess && (init == 2 || (init == 1 && !noClear && devbuf_skip_safety_clear() == 0)))
-        {
-            e = hipMemset(p, 0, count * sizeof(T));
-            what = " cleared";
-        }
-        static const bool syncAlloc = debug_knobs_on() && std::getenv("LWHIP_SYNC_ALLOC") != nullptr; // (diagnosis: round 4's clearing minus the clearing)
-        // (the caller's stream may be a non-blocking one: no implicit order with the fill -- wait for it, or, inside lwhip_create,
-        // let the ~60 fills of a context queue up and wait once before the first upload: defer_fill_sync)
-        if (e == hipSuccess && ((*what && devbuf_defer_fill_sync() == 0) || syncAlloc))
-            e = hipStreamSynchronize(nullptr);
-        static const bool trace = std::getenv("LWHIP_TRACE_ALLOC") != nullptr; // diagnosis: which buffer a number / an address is
-        if (trace)
-            std::fprintf(stderr, "lwhip alloc #%d %p .. %p (%zu x %zu B)%s\n", seq, (void*)p, (void*)((char*)p + count * sizeof(T)), count, sizeof(T),
-                         what);
-        return e;
+        return e != hipSuccess ? e : fresh_fill(m, p, count, sizeof(T), std::is_same<T, double>::value, init, seq);
     }
     static std::atomic<int>& alloc_seq() // (diagnosis only: the numbers of LWHIP_TRACE_ALLOC / LWHIP_PAD_SENTINEL)
     {
         static std::atomic<int> seq{ 0 };
         return seq;
     }
-    static bool poison_on()
+    // the clearing of a buffer whose zeros only keep its padding finite (not a value): left out under the sentinel, and for a
+    // piece of the borrower's arena (cleared as a whole a moment ago)
+    hipError_t clear_padding(DevMem& m)
     {
-        static const bool poison = debug_knobs_on() && std::getenv("LWHIP_POISON") != nullptr;
-        return poison;
-    }
-    // LWHIP_PAD_SENTINEL: "all", one number, or a range A-B (inclusive) of the fp64 allocation numbers of a context
-    static bool sentinel_on()
-    {
-        static const bool on = debug_knobs_on() && std::getenv("LWHIP_PAD_SENTINEL") != nullptr && *std::getenv("LWHIP_PAD_SENTINEL");
-        return on;
-    }
-    static bool sentinel_for(int seq)
-    {
-        if (!sentinel_on())
-            return false;
-        static int lo = 0, hi = -1;
-        static bool parsed = false;
-        if (!parsed)
-        {
-            const char* v = std::getenv("LWHIP_PAD_SENTINEL");
-            if (v[0] == 'a')
-            {
-                lo = 0;
-                hi = 1 << 30;
-            }
-            else
-            {
-                lo = hi = std::atoi(v);
-                const char* dash = std::strchr(v, '-');
-                if (dash)
-                    hi = std::atoi(dash + 1);
-            }
-            parsed = true;
-        }
-        return seq >= lo && seq <= hi;
-    }
-    // the clearing of a buffer whose zeros only keep its padding finite (not a value): left out under the sentinel
-    hipError_t clear_padding()
-    {
-        if (!p || sentinel_on())
+        if (!p || sentinel_on() || (m.arena && m.arena->holds(p)))
             return hipSuccess;
-        if (const DevArena* ar = devbuf_arena())
-            if (!ar->counting && (unsigned char*)p >= ar->base && (unsigned char*)p < ar->base + ar->size)
-                return hipSuccess; // (a piece of the borrower's arena, cleared as a whole a moment ago)
-        hipError_t e = hipMemset(p, 0, n * sizeof(T));
-        return (e == hipSuccess && devbuf_defer_fill_sync() == 0) ? hipStreamSynchronize(nullptr) : e;
+        return hipMemsetAsync(p, 0, n * sizeof(T), m.stream);
     }
     // a window of somebody else's allocation (the depth arena of the lane sweep)
     void view(T* ptr, size_t count)
@@ -320,7 +227,7 @@ template <typename T> struct DevBuf
             word(w);
         return h | 1ull;
     }
-    hipError_t upload_or_borrow(const std::vector<T>& v, const DevBuf<T>* from)
+    hipError_t upload_or_borrow(DevMem& m, const std::vector<T>& v, const DevBuf<T>* from)
     {
         if (from && from->p && from->n == v.size() && !v.empty() && from->sig == fingerprint(v))
         {
@@ -330,31 +237,27 @@ template <typename T> struct DevBuf
         }
         // (a structure table: the owner's copy is what borrowers use, so it is neither counted into the size of a borrower's
         // arena nor -- where a borrower has to keep a copy of its own after all -- taken out of one)
-        DevArena* const ar = devbuf_arena();
-        devbuf_arena() = nullptr;
-        const hipError_t e = upload(v);
-        devbuf_arena() = ar;
+        DevArena* const ar = m.arena;
+        m.arena = nullptr;
+        const hipError_t e = upload(m, v);
+        m.arena = ar;
         return e;
     }
-    hipError_t upload(const std::vector<T>& v)
+    hipError_t upload(DevMem& m, const std::vector<T>& v)
     {
-        hipError_t e = alloc(v.size(), poison_on());
+        hipError_t e = alloc(m, v.size(), poison_on());
         if (e != hipSuccess || v.empty())
             return e;
         sig = fingerprint(v);
-        if (H2DBatch* b = h2d_batch())
-            if (b->add(p, v.data(), v.size() * sizeof(T)))
-                return hipSuccess;
-        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+        e = m.h2d(p, v.data(), v.size() * sizeof(T));
+        return e != hipSuccess ? e : m.settle(); // (v is the caller's: it may go when this returns)
     }
     void release()
     {
         if (p && owned)
         {
-            // (LWHIP_POISON=1: and a buffer is poisoned again when it is given back, with another pattern -- a stale device
-            // pointer into it, or memory the allocator hands out behind this wrapper's back, then reads -nan / 0xFEFEFEFE)
             if (poison_on())
-                (void)hipMemset(p, 0xFE, n * sizeof(T));
+                released_fill(p, n * sizeof(T));
             (void)hipFree(p);
         }
         p = nullptr;
@@ -389,7 +292,7 @@ hipError_t stream_acquire(int device, hipStream_t* out);
 void stream_release(int device, hipStream_t s);
 hipError_t stream_acquire_shared(int device, hipStream_t* out); // the columns of a batch made by one thread share a stream
 void stream_release_shared(int device, hipStream_t s);
-void* pinned_acquire(int device, size_t bytes, void** devPtr);  // page-locked, device-mapped host memory out of pooled slabs
+void* pinned_acquire(int device, size_t bytes, void** devPtr, bool mapped); // the pinned pool (PinnedBlock: its owner type)
 void pinned_release(int device, void* p, size_t bytes);
 void peer_release(lwhip_context* c);
 int peer_publish(lwhip_context* c);
@@ -441,7 +344,7 @@ struct lwhip_context
     DevBuf<int64_t> hJOff;
     DevBuf<lwhip_j_coeff> hJCoef;
     DevBuf<double> JRest;
-    double* lsDbgHost = nullptr; // LWHIP_LS_TIMING: phase clocks of the last sweep, [nTiles][8]
+    PinnedBlock lsDbg;           // LWHIP_LS_TIMING: phase clocks of the last sweep, [nTiles][8] (mapped)
     DevBuf<double> depArena; // lane sweep: n | wphi | ratio | geoT in one allocation (one buffer resource in the kernel)
     int tileWaves = 4, maxSlotsTile = 0, maxCTTile = 1, maxCTPost = 1, tileCap = 0, ktStride = 4;
     int64_t rowsTileTot = 0, momTot = 0, phiTTot = 0;
@@ -471,7 +374,9 @@ struct lwhip_context
     int64_t rowsTot = 0;
     int nContLa = 0;
     int64_t gammaTot = 0, phiTot = 0, rhoTot = 0, parTot = 0;
-    hipStream_t ownStream = nullptr, stream = nullptr;
+    DevMem mem;                   // allocations, fills and uploads: all on the context's stream
+    hipStream_t& stream = mem.stream;
+    hipStream_t ownStream = nullptr;
     bool ownStreamShared = false;
 
     DevBuf<double> height, temperature, muz, wmu, wavelength, lowerBcData, upperBcData;
@@ -537,7 +442,7 @@ struct lwhip_context
     DevBuf<int32_t> transType;
     DevBuf<int32_t> contLa;
     DevBuf<int32_t> prdChangeIdx;
-    double* prdPinned = nullptr;
+    PinnedBlock prdPinned;
     // pipelined sub-iterations of lwhip_redistribute_prd (one device, 1D, lane sweep): the launches of up to PRD_PIPE_DEPTH
     // sub-iterations are queued without a host round trip in between; the device keeps the loop's stopping rule (prdCtl, see
     // ApplyArgs) and every sub-iteration's results land in its own slot of prdPinnedPipe
@@ -548,8 +453,7 @@ struct lwhip_context
     // LWHIP_PAIR_RAYS=0 / LWHIP_PRD_PIPELINE=0 (experiment knobs, read ONCE per context in lwhip_create and only under
     // LWHIP_DEBUG like the other layout knobs: the first changes the order of the arithmetic)
     bool pairRays = true, prdPipeline = true, prdGeneral = false;
-    double* prdPinnedPipe = nullptr;
-    size_t prdPinnedPipeN = 0;
+    PinnedBlock prdPinnedPipe;
     int prdPipeIter = 0;     // > 0: the sub-iteration the calls of lwhip_prd_partial / _finalise belong to
     double prdPipeTol = 0.0;
     DevBuf<DevTrans> dtrans;
@@ -579,11 +483,10 @@ struct lwhip_context
     bool partialPending = false;
     bool prefillPending = false; // lwhip_gamma_prefill_from_C deferred into the next apply_kernel
     double prefillCrsw = 1.0;
-    double* gatherPinned = nullptr;
+    PinnedBlock gatherPinned;
     // pinned staging for the many small per-atom / per-transition host arrays: they are packed here and
-    // cross PCIe as a few large copies (a pageable hipMemcpy per 656-byte row costs ~12 us each)
-    double* stage = nullptr;
-    size_t stageDoubles = 0;
+    // cross PCIe as a few large copies (a pageable hipMemcpy per 656-byte row costs ~12 us each); layout: stage_layout
+    PinnedBlock stage;
 
     // ONE pinned, host-mapped block per context holds every word the DEVICE stores into host memory (tailMapped, statusHost,
     // changeHost, zeroCheck point into it) and every target of a small device-to-host copy the API used to aim at a stack
@@ -607,8 +510,7 @@ struct lwhip_context
     double* JhostDev = nullptr;    // device address of this shard's first row in it
     DevBuf<double> Jsnap;          // lwhip_j_snapshot
     DevBuf<unsigned long long> fpSums; // lwhip_fingerprint_J: the blocks' sums
-    unsigned long long* fpPinned = nullptr;
-    size_t fpPinnedN = 0;
+    PinnedBlock fpPinned;
     bool fpJValid = false;         // fpJValue is the fingerprint of the device's current J as seen at address fpJPtr
     uint64_t fpJValue = 0;
     const void* fpJPtr = nullptr;
@@ -622,10 +524,11 @@ struct lwhip_context
     ~lwhip_context()
     {
         // (a context that failed half-way through lwhip_create comes here without lwhip_destroy: nothing of it may be
-        // released while its stream -- or a clearing fill on the null stream -- still runs)
+        // released while its stream still runs)
         if (stream)
             (void)hipStreamSynchronize(stream);
-        (void)hipStreamSynchronize(nullptr);
+        for (PinnedBlock* b : { &stage, &gatherPinned, &prdPinned, &prdPinnedPipe, &fpPinned, &lsDbg })
+            b->release(); // (before the stream they were used on goes back to its pool)
         for (auto& pr : pending)
         {
             (void)hipEventDestroy(pr.first);
@@ -635,27 +538,17 @@ struct lwhip_context
             stream_release_shared(device, ownStream);
         else if (ownStream)
             stream_release(device, ownStream); // (never hipStreamDestroy: see stream_acquire, lwhip_api.hip)
-        if (gatherPinned)
-            (void)hipHostFree(gatherPinned);
-        if (stage)
-            pinned_release(device, stage, stageDoubles * sizeof(double));
-        if (prdPinned)
-            (void)hipHostFree(prdPinned);
-        if (prdPinnedPipe)
-            (void)hipHostFree(prdPinnedPipe);
         peer_release(this);
         if (stateArena) // (the DevBufs that point into it do not own their pieces)
             (void)hipFree(stateArena);
         if (JhostReg)
             (void)hipHostUnregister(JhostReg);
-        if (fpPinned)
-            (void)hipHostFree(fpPinned);
         host_block_release(this);
     }
 };
 
 #define H2D(dst, src, count)                                                                           \
-    HIP_TRY(lwhip::h2d_copy((dst), (src), (size_t)(count) * sizeof(double), c->stream))
+    HIP_TRY(c->mem.h2d((dst), (src), (size_t)(count) * sizeof(double)))
 #define D2H(dst, src, count)                                                                           \
     HIP_TRY(hipMemcpyAsync((dst), (src), (size_t)(count) * sizeof(double), hipMemcpyDeviceToHost, c->stream))
 

@@ -4,6 +4,135 @@
 
 namespace lwhip
 {
+// ---- what a fresh allocation holds (DevBuf::alloc, lwhip_host.h) -----------------------------------------------------------
+// The diagnosis fills (LWHIP_DEBUG):
+//   LWHIP_POISON=1                  fresh allocations hold NaN / -1 (not alloc_zero's: their zero is a value -- counters,
+//                                   accumulators --, which round 6's peer-exchange arrival counter was the first to rely on
+//                                   without a clear of its own); a buffer given back is poisoned again, with 0xFE
+//   LWHIP_PAD_SENTINEL=all | N | A-B  the fp64 state allocations numbered so (per context, LWHIP_TRACE_ALLOC prints the numbers)
+//                                   hold the sentinel 6.7e299 instead of zeros -- a result that depends on never-written memory
+//                                   is then off by hundreds of orders of magnitude, deterministically (tests/test_padding.py)
+//   LWHIP_PAD_SENTINEL_VALUE=<x>    another fill value (a huge one is "optically thick" and may be as harmless as zero where a
+//                                   plausible one is not); "rand" / "randsign": different plausible values everywhere
+//   LWHIP_PAD_SENTINEL_INT=<i>      the other state allocations (index and argument tables) hold this 32-bit word: stale but
+//                                   valid-looking indices are what neither zeros nor the 0xFF of LWHIP_POISON imitate
+//   LWHIP_NO_CLEAR=1                no safety net: what hipMalloc returns
+// LWHIP_TRACE_ALLOC (always read): every allocation's number, address range and fill on stderr.
+bool poison_on()
+{
+    static const bool poison = debug_knobs_on() && std::getenv("LWHIP_POISON") != nullptr;
+    return poison;
+}
+bool sentinel_on()
+{
+    static const bool on = debug_knobs_on() && std::getenv("LWHIP_PAD_SENTINEL") != nullptr && *std::getenv("LWHIP_PAD_SENTINEL");
+    return on;
+}
+static bool sentinel_for(int seq)
+{
+    if (!sentinel_on())
+        return false;
+    static int lo = 0, hi = -1;
+    static bool parsed = false;
+    if (!parsed)
+    {
+        const char* v = std::getenv("LWHIP_PAD_SENTINEL");
+        if (v[0] == 'a')
+        {
+            lo = 0;
+            hi = 1 << 30;
+        }
+        else
+        {
+            lo = hi = std::atoi(v);
+            const char* dash = std::strchr(v, '-');
+            if (dash)
+                hi = std::atoi(dash + 1);
+        }
+        parsed = true;
+    }
+    return seq >= lo && seq <= hi;
+}
+// "rand" / "randsign": what stale data of a destroyed context looks like (log-uniform in 1e-8 .. 1e8).  A uniform fill cannot
+// show a dependence that goes through a difference or a ratio of two padding values (a slope, S = eta / chi): those are 0 and 1
+// for any constant.  (one table of 2^20 values, made once, laid end to end from an offset that follows the allocation number)
+static void sentinel_random(std::vector<double>& h, bool sign, int seq)
+{
+    static std::vector<double> table;
+    if (table.empty())
+    {
+        table.resize(1u << 20);
+        uint64_t x = 0x9E3779B97F4A7C15ull;
+        for (auto& v : table)
+        {
+            x ^= x << 13;
+            x ^= x >> 7;
+            x ^= x << 17;
+            const double u = (double)(x >> 11) * (1.0 / 9007199254740992.0);
+            v = std::pow(10.0, 16.0 * u - 8.0) * ((sign && (x & 1)) ? -1.0 : 1.0);
+        }
+    }
+    size_t off = ((size_t)(seq + 1) * 7919u) & (table.size() - 1);
+    for (size_t i = 0; i < h.size();)
+    {
+        const size_t nCopy = std::min(h.size() - i, table.size() - off);
+        std::memcpy(h.data() + i, table.data() + off, nCopy * sizeof(double));
+        i += nCopy;
+        off = 0;
+    }
+}
+hipError_t fresh_fill(DevMem& m, void* p, size_t count, size_t elem, bool fp64, int init, int seq)
+{
+    const size_t bytes = count * elem;
+    static const bool noClear = debug_knobs_on() && std::getenv("LWHIP_NO_CLEAR") != nullptr;
+    hipError_t e = hipSuccess;
+    const char* what = "";
+    if (poison_on() && init != 2)
+    {
+        e = hipMemsetAsync(p, 0xFF, bytes, m.stream);
+        what = " poisoned";
+    }
+    else if (init == 1 && fp64 && sentinel_for(seq))
+    {
+        static const char* sv = std::getenv("LWHIP_PAD_SENTINEL_VALUE");
+        if (sv && *sv)
+        {
+            std::vector<double> h(bytes / sizeof(double) + 1, std::atof(sv));
+            if (sv[0] == 'r')
+                sentinel_random(h, std::strncmp(sv, "randsign", 8) == 0, seq);
+            e = m.h2d(p, h.data(), bytes);
+            if (e == hipSuccess)
+                e = m.settle(); // (h is this call's)
+        }
+        else
+            e = hipMemsetD32Async((hipDeviceptr_t)p, (int)0x7E377E37, bytes / 4, m.stream); // 0x7E377E377E377E37 = 6.7e299
+        what = " sentinel";
+    }
+    else if (init == 1 && !fp64 && sentinel_on() && std::getenv("LWHIP_PAD_SENTINEL_INT"))
+    {
+        e = hipMemsetAsync(p, 0, bytes, m.stream);
+        if (e == hipSuccess && bytes >= 4)
+            e = hipMemsetD32Async((hipDeviceptr_t)p, std::atoi(std::getenv("LWHIP_PAD_SENTINEL_INT")), bytes / 4, m.stream);
+        what = " int-sentinel";
+    }
+    else if (init == 2 || (init == 1 && !noClear && !m.skipSafetyClear))
+    {
+        e = hipMemsetAsync(p, 0, bytes, m.stream);
+        what = " cleared";
+    }
+    static const bool trace = std::getenv("LWHIP_TRACE_ALLOC") != nullptr; // diagnosis: which buffer a number / an address is
+    if (trace)
+        std::fprintf(stderr, "lwhip alloc #%d %p .. %p (%zu x %zu B)%s\n", seq, p, (void*)((char*)p + bytes), count, elem, what);
+    return e;
+}
+// LWHIP_POISON: a buffer given back -- no context's any more -- is filled on the thread's own stream (hipFree, right after,
+// waits for the device): a stale device pointer into it, or memory the allocator hands out behind DevBuf's back, then reads
+// -nan / 0xFEFEFEFE
+void released_fill(void* p, size_t bytes)
+{
+    (void)hipMemsetAsync(p, 0xFE, bytes, hipStreamPerThread);
+}
+
 int alloc_state(lwhip_context* c)
 {
     const size_t Ns = c->Ns, Nla = c->Nla, Nr = c->Nrays;
@@ -23,94 +152,93 @@ int alloc_state(lwhip_context* c)
                 c->prdRowsTot += h.t.Nred - h.t.Nblue;
             }
         }
-    HIP_TRY(c->height.alloc(Ns));
-    HIP_TRY(c->temperature.alloc(Ns));
-    HIP_TRY(c->muz.alloc(2 * Nr)); // [muz | 1 / muz]
-    HIP_TRY(c->wmu.alloc(Nr));
-    HIP_TRY(c->wavelength.alloc(Nla));
+    HIP_TRY(c->height.alloc(c->mem, Ns));
+    HIP_TRY(c->temperature.alloc(c->mem, Ns));
+    HIP_TRY(c->muz.alloc(c->mem, 2 * Nr)); // [muz | 1 / muz]
+    HIP_TRY(c->wmu.alloc(c->mem, Nr));
+    HIP_TRY(c->wavelength.alloc(c->mem, Nla));
     // (+ 8: the lane sweep reads a lane's block of depths with one wide load -- up to three doubles past the last row)
-    HIP_TRY(c->bgChi.alloc(Nla * Ns + 8));
-    HIP_TRY(c->bgEta.alloc(Nla * Ns + 8));
-    HIP_TRY(c->bgSca.alloc(Nla * Ns + 8));
-    HIP_TRY(c->J.alloc(Nla * Ns + 8));
-    HIP_TRY(c->I.alloc(Nla * Nr * (size_t)c->Nx));
+    HIP_TRY(c->bgChi.alloc(c->mem, Nla * Ns + 8));
+    HIP_TRY(c->bgEta.alloc(c->mem, Nla * Ns + 8));
+    HIP_TRY(c->bgSca.alloc(c->mem, Nla * Ns + 8));
+    HIP_TRY(c->J.alloc(c->mem, Nla * Ns + 8));
+    HIP_TRY(c->I.alloc(c->mem, Nla * Nr * (size_t)c->Nx));
     if (c->prob.storeDepthData)
     {
-        HIP_TRY(c->depthChi.alloc(Nla * Nr * 2 * Ns));
-        HIP_TRY(c->depthEta.alloc(Nla * Nr * 2 * Ns));
-        HIP_TRY(c->depthI.alloc(Nla * Nr * 2 * Ns));
+        HIP_TRY(c->depthChi.alloc(c->mem, Nla * Nr * 2 * Ns));
+        HIP_TRY(c->depthEta.alloc(c->mem, Nla * Nr * 2 * Ns));
+        HIP_TRY(c->depthI.alloc(c->mem, Nla * Nr * 2 * Ns));
     }
-    HIP_TRY(c->vlosMu.alloc(Nr * Ns));
-    HIP_TRY(c->vBroad.alloc((size_t)std::max(c->Natom, 1) * Ns));
-    HIP_TRY(c->aDamp.alloc_zero((size_t)std::max(c->Nline, 1) * Ns)); // (zero = the value of a line without damping data)
-    HIP_TRY(c->Qelast.alloc_zero((size_t)std::max(c->Nline, 1) * Ns));
+    HIP_TRY(c->vlosMu.alloc(c->mem, Nr * Ns));
+    HIP_TRY(c->vBroad.alloc(c->mem, (size_t)std::max(c->Natom, 1) * Ns));
+    HIP_TRY(c->aDamp.alloc_zero(c->mem, (size_t)std::max(c->Nline, 1) * Ns)); // (zero = the value of a line without damping data)
+    HIP_TRY(c->Qelast.alloc_zero(c->mem, (size_t)std::max(c->Nline, 1) * Ns));
     if (!c->is2d && c->batchHint > 1 && c->prob.vlosMu)
     {
         // a column of a 1.5D batch: the scratch of its device-side profiles (voigt_line_list, lwhip_api.hip -- same sizes) now,
         // out of the column's arena, instead of two allocations and a fill per column at the batch's first profile launch
         const size_t nLine = (size_t)std::max(c->Nline, 1);
-        HIP_TRY(c->wphiScratch.alloc(nLine * 16 * Ns));
-        HIP_TRY(c->wphiTicket.alloc_zero(nLine * ((Ns + 7) / 8 + 1)));
+        HIP_TRY(c->wphiScratch.alloc(c->mem, nLine * 16 * Ns));
+        HIP_TRY(c->wphiTicket.alloc_zero(c->mem, nLine * ((Ns + 7) / 8 + 1)));
     }
     if (c->laneSweep)
     {
         // the depth-only pools the lane sweep reads, back to back (+ padding: a ray's last block reads past its row)
         const size_t nN = (size_t)c->NlevTot * Ns, nW = (size_t)std::max(c->Nline, 1) * Ns, nR = (size_t)std::max(c->Ncont, 1) * Ns;
         const size_t nG = (size_t)4 * (c->laneLR * c->laneD + 2);
-        HIP_TRY(c->depArena.alloc(nN + nW + nR + nG + 16));
-        HIP_TRY(c->depArena.clear_padding());
+        HIP_TRY(c->depArena.alloc(c->mem, nN + nW + nR + nG + 16));
+        HIP_TRY(c->depArena.clear_padding(c->mem));
         c->n.view(c->depArena.p, nN);
         c->wphi.view(c->depArena.p + nN, nW);
         c->ratio.view(c->depArena.p + nN + nW, nR);
         c->geoT.view(c->depArena.p + nN + nW + nR, nG);
-        HIP_TRY(c->bcPlanck.alloc(4 * Nla));
-        HIP_TRY(c->bcPlanck.clear_padding());
+        HIP_TRY(c->bcPlanck.alloc(c->mem, 4 * Nla));
+        HIP_TRY(c->bcPlanck.clear_padding(c->mem));
     }
     else
     {
-        HIP_TRY(c->n.alloc((size_t)c->NlevTot * Ns));
-        HIP_TRY(c->ratio.alloc((size_t)std::max(c->Ncont, 1) * Ns));
-        HIP_TRY(c->wphi.alloc((size_t)std::max(c->Nline, 1) * Ns));
+        HIP_TRY(c->n.alloc(c->mem, (size_t)c->NlevTot * Ns));
+        HIP_TRY(c->ratio.alloc(c->mem, (size_t)std::max(c->Ncont, 1) * Ns));
+        HIP_TRY(c->wphi.alloc(c->mem, (size_t)std::max(c->Nline, 1) * Ns));
     }
-    HIP_TRY(c->nTotal.alloc((size_t)c->Natom * Ns));
+    HIP_TRY(c->nTotal.alloc(c->mem, (size_t)c->Natom * Ns));
     // (+ one ray's block: the lane sweep requests a ray's profile one ray ahead, after the last ray of the pool's last
     // wavelength that request reaches up to 2 Ns doubles past the end -- it is never used, but it must be mapped memory)
-    HIP_TRY(c->phi.alloc((size_t)std::max<int64_t>(c->phiTot, 1) + 2 * (size_t)c->Ns + 8));
-    HIP_TRY(c->rho.alloc((size_t)std::max<int64_t>(c->rhoTot, 1) + 8)); // (+ padding: reads past a row's end by a block of depths)
-    HIP_TRY(c->Gamma.alloc((size_t)std::max<int64_t>(c->gammaTot, 1)));
-    HIP_TRY(c->Cmat.alloc_zero((size_t)std::max<int64_t>(c->gammaTot, 1))); // (zero = no collisional pre-fill given)
-    HIP_TRY(c->Rij.alloc((size_t)std::max(c->Ntrans, 1) * Ns));
-    HIP_TRY(c->Rji.alloc((size_t)std::max(c->Ntrans, 1) * Ns));
+    HIP_TRY(c->phi.alloc(c->mem, (size_t)std::max<int64_t>(c->phiTot, 1) + 2 * (size_t)c->Ns + 8));
+    HIP_TRY(c->rho.alloc(c->mem, (size_t)std::max<int64_t>(c->rhoTot, 1) + 8)); // (+ padding: reads past a row's end by a block of depths)
+    HIP_TRY(c->Gamma.alloc(c->mem, (size_t)std::max<int64_t>(c->gammaTot, 1)));
+    HIP_TRY(c->Cmat.alloc_zero(c->mem, (size_t)std::max<int64_t>(c->gammaTot, 1))); // (zero = no collisional pre-fill given)
+    HIP_TRY(c->Rij.alloc(c->mem, (size_t)std::max(c->Ntrans, 1) * Ns));
+    HIP_TRY(c->Rji.alloc(c->mem, (size_t)std::max(c->Ntrans, 1) * Ns));
     // reduce buffer: [Ntrans,4,Ns] partial sums followed by one (dJMax, idx) slot per shard
-    HIP_TRY(c->red.alloc_zero((size_t)c->Ntrans * 4 * Ns + 2 * (size_t)c->worldSize * (1 + c->prdLines.size())));
-    HIP_TRY(c->red8.alloc(c->is2d ? 8 : (size_t)std::max(c->Ntrans, 1) * LWHIP_REDUCE_SPLIT * 4 * Ns));
+    HIP_TRY(c->red.alloc_zero(c->mem, (size_t)c->Ntrans * 4 * Ns + 2 * (size_t)c->worldSize * (1 + c->prdLines.size())));
+    HIP_TRY(c->red8.alloc(c->mem, c->is2d ? 8 : (size_t)std::max(c->Ntrans, 1) * LWHIP_REDUCE_SPLIT * 4 * Ns));
     c->gatherHost.assign(2 * (size_t)c->worldSize, 0.0);
-    HIP_TRY(c->dJ.alloc(Nla));
-    HIP_TRY(c->status.alloc(1));
+    HIP_TRY(c->dJ.alloc(c->mem, Nla));
+    HIP_TRY(c->status.alloc(c->mem, 1));
     if (c->tiled)
     {
-        HIP_TRY(c->geo.alloc(4 * Ns));
+        HIP_TRY(c->geo.alloc(c->mem, 4 * Ns));
         c->ktStride = (4 + c->NlevTot + c->Nline + 1) / 2 * 2;
-        HIP_TRY(c->kt.alloc((size_t)c->ktStride * (Ns + 2))); // one padding entry at each end
-        HIP_TRY(c->rowsTile.alloc((size_t)std::max<int64_t>(c->rowsTileTot, 1)));
+        HIP_TRY(c->kt.alloc(c->mem, (size_t)c->ktStride * (Ns + 2))); // one padding entry at each end
+        HIP_TRY(c->rowsTile.alloc(c->mem, (size_t)std::max<int64_t>(c->rowsTileTot, 1)));
         if (c->laneSweep)
         {
             // the padding points of the row blocks (k >= Ns) are read: keep them finite
-            HIP_TRY(c->rowsTile.clear_padding());
+            HIP_TRY(c->rowsTile.clear_padding(c->mem));
         }
-        HIP_TRY(c->momTile.alloc((size_t)std::max<int64_t>(c->momTot, 1)));
-        HIP_TRY(c->phiT.alloc((size_t)std::max<int64_t>(c->phiTTot, 1)));
-        HIP_TRY(c->momTile.clear_padding());
+        HIP_TRY(c->momTile.alloc(c->mem, (size_t)std::max<int64_t>(c->momTot, 1)));
+        HIP_TRY(c->phiT.alloc(c->mem, (size_t)std::max<int64_t>(c->phiTTot, 1)));
+        HIP_TRY(c->momTile.clear_padding(c->mem));
     }
     if (c->is2d)
     {
         const lwhip_grid2d& g = *c->prob.grid2d;
         const size_t nSt = (size_t)g.Nrays * 2 * Ns;
-        auto upv = [](auto& buf, const auto* host, size_t count) -> hipError_t {
-            hipError_t e = buf.alloc(std::max<size_t>(count, 1));
-            if (e != hipSuccess || !count)
-                return e;
-            return hipMemcpy(buf.p, host, count * sizeof(*host), hipMemcpyHostToDevice);
+        // (the caller's arrays: they outlive lwhip_create, which waits for its stream)
+        auto upv = [c](auto& buf, const auto* host, size_t count) -> hipError_t {
+            hipError_t e = buf.alloc(c->mem, std::max<size_t>(count, 1));
+            return e != hipSuccess ? e : c->mem.h2d(buf.p, host, count * sizeof(*host));
         };
         HIP_TRY(upv(c->g2mux, g.mux, (size_t)g.Nrays));
         HIP_TRY(upv(c->g2uw, g.uw, nSt));
@@ -120,10 +248,10 @@ int alloc_state(lwhip_context* c)
             std::vector<int32_t> wu, wd;
             if (fs2d_records_packed(g.uw, nSt, g.Nx, g.Nz, su, wu) && fs2d_records_packed(g.dw, nSt, g.Nx, g.Nz, sd, wd))
             {
-                HIP_TRY(c->g2uwS.upload(su));
-                HIP_TRY(c->g2uwA.upload(wu));
-                HIP_TRY(c->g2dwS.upload(sd));
-                HIP_TRY(c->g2dwA.upload(wd));
+                HIP_TRY(c->g2uwS.upload(c->mem, su));
+                HIP_TRY(c->g2uwA.upload(c->mem, wu));
+                HIP_TRY(c->g2dwS.upload(c->mem, sd));
+                HIP_TRY(c->g2dwA.upload(c->mem, wd));
             }
         }
         HIP_TRY(upv(c->g2long, g.longCharIdx, nSt));
@@ -146,7 +274,7 @@ int alloc_state(lwhip_context* c)
             for (int lc = 0; lc < g.NlongChar; ++lc)
                 if (owner[2 * (size_t)lc] < 0)
                     return fail(LWHIP_ERR_INVALID, "grid2d: a long characteristic belongs to no point");
-            HIP_TRY(c->g2lcOwner.upload(owner));
+            HIP_TRY(c->g2lcOwner.upload(c->mem, owner));
         }
         // wavelengths per batch: per-ray chi, S, I, Psi* of a batch within ~8 GB of the 288.  Every kernel of a batch is
         // latency-bound per workgroup (82 sequential planes in fs2d), so the batch should fill the chip, and fewer,
@@ -168,15 +296,15 @@ int alloc_state(lwhip_context* c)
             c->groups2d = (int)std::max<size_t>(1, std::min<size_t>({ (size_t)16, (size_t)c->batch2d, (size_t)numCU * 4 * R2D_WAVES_HOST / wavesPerGroup }));
         }
         c->groups2d = std::max(1, c->groups2d);
-        HIP_TRY(c->red2d.alloc((size_t)c->groups2d * std::max(c->Ntrans, 1) * 4 * Ns));
+        HIP_TRY(c->red2d.alloc(c->mem, (size_t)c->groups2d * std::max(c->Ntrans, 1) * 4 * Ns));
         const size_t nb = (size_t)c->batch2d * 2 * Nr * Ns;
-        HIP_TRY(c->b2cs.alloc(2 * nb)); // (chi, S) pairs
-        HIP_TRY(c->b2I.alloc(nb));
-        HIP_TRY(c->b2Psi.alloc(nb));
-        HIP_TRY(c->b2coef.alloc(3 * nb));
-        HIP_TRY(c->b2idx.alloc(nb));
+        HIP_TRY(c->b2cs.alloc(c->mem, 2 * nb)); // (chi, S) pairs
+        HIP_TRY(c->b2I.alloc(c->mem, nb));
+        HIP_TRY(c->b2Psi.alloc(c->mem, nb));
+        HIP_TRY(c->b2coef.alloc(c->mem, 3 * nb));
+        HIP_TRY(c->b2idx.alloc(c->mem, nb));
         if (g.NlongChar > 0)
-            HIP_TRY(c->b2lc.alloc((size_t)c->batch2d * g.NlongChar * 3));
+            HIP_TRY(c->b2lc.alloc(c->mem, (size_t)c->batch2d * g.NlongChar * 3));
         for (size_t la = 0; la < Nla; ++la)
             if (c->hdrHost[la].rowBase >= 0)
                 c->maxRowsLa = std::max(c->maxRowsLa, c->hdrHost[la].nRows + c->hdrHost[la].nMixed + c->hdrHost[la].nPure);
@@ -193,17 +321,17 @@ int alloc_state(lwhip_context* c)
             for (size_t la = 0; la < Nla; ++la)
                 maxRows = std::max(maxRows, pre[std::min(Nla, la + (size_t)c->batch2d)] - pre[la]);
         }
-        HIP_TRY(c->rowsBuf.alloc((size_t)maxRows * Ns));
+        HIP_TRY(c->rowsBuf.alloc(c->mem, (size_t)maxRows * Ns));
     }
     if (c->prob.zLowerBc.type == LWHIP_BC_CALLABLE)
     {
-        HIP_TRY(c->lowerBcData.alloc(Nla * c->prob.zLowerBc.Nmu * (size_t)c->Nx));
-        HIP_TRY(c->lowerIdx.alloc(Nr * 2));
+        HIP_TRY(c->lowerBcData.alloc(c->mem, Nla * c->prob.zLowerBc.Nmu * (size_t)c->Nx));
+        HIP_TRY(c->lowerIdx.alloc(c->mem, Nr * 2));
     }
     if (c->prob.zUpperBc.type == LWHIP_BC_CALLABLE)
     {
-        HIP_TRY(c->upperBcData.alloc(Nla * c->prob.zUpperBc.Nmu * (size_t)c->Nx));
-        HIP_TRY(c->upperIdx.alloc(Nr * 2));
+        HIP_TRY(c->upperBcData.alloc(c->mem, Nla * c->prob.zUpperBc.Nmu * (size_t)c->Nx));
+        HIP_TRY(c->upperIdx.alloc(c->mem, Nr * 2));
     }
     return LWHIP_OK;
 }
@@ -232,7 +360,7 @@ int build_sweep_args(lwhip_context* c)
     a.nContLa = c->nContLa;
     c->hargs = a;
     std::vector<ContArgs> v(1, a);
-    HIP_TRY(c->dargs.upload(v));
+    HIP_TRY(c->dargs.upload(c->mem, v));
     return LWHIP_OK;
 }
 
@@ -348,13 +476,13 @@ int build_tile_args(lwhip_context* c)
     if (std::getenv("LWHIP_LS_TIMING"))
     {
         // phase clocks of a -DLS_TIMING / -DRM_TIMING build: host-mapped, dumped by lwhip_destroy
-        if (!c->lsDbgHost)
+        if (!c->lsDbg.host)
         {
             // [nTiles][8] per tile, then [workgroup][4]: prologue, tasks, epilogue clocks (lane sweep)
-            HIP_TRY(hipHostMalloc((void**)&c->lsDbgHost, (size_t)c->nTiles * 24 * sizeof(double), hipHostMallocMapped));
-            std::memset(c->lsDbgHost, 0, (size_t)c->nTiles * 24 * sizeof(double));
+            HIP_TRY(c->lsDbg.reserve(c->device, (size_t)c->nTiles * 24 * sizeof(double), c->stream, true));
+            std::memset(c->lsDbg.host, 0, c->lsDbg.bytes);
         }
-        HIP_TRY(hipHostGetDevicePointer((void**)&a.lsDbg, c->lsDbgHost, 0));
+        a.lsDbg = (double*)c->lsDbg.dev;
     }
     // The device copies of the argument blocks keep their addresses for the life of the context (a fused column batch
     // holds them): the first call allocates, later ones (lwhip_set_zplane_outputs) overwrite in place on the stream.
@@ -362,11 +490,11 @@ int build_tile_args(lwhip_context* c)
         host = val;
         if (!dev.p)
         {
-            hipError_t e = dev.alloc(1);
+            hipError_t e = dev.alloc(c->mem, 1);
             if (e != hipSuccess)
                 return e;
         }
-        return h2d_copy(dev.p, &host, sizeof(TileArgs), c->stream);
+        return c->mem.h2d(dev.p, &host, sizeof(TileArgs));
     };
     HIP_TRY(put(c->dtargs, c->htargs, a));
     if (c->nTileChunksPrd > 0)
@@ -516,54 +644,34 @@ extern "C"
 {
 namespace
 {
-// pinned staging blocks for the large uploads of column batches: taken from a pool for the duration of one lwhip_upload (the
-// call waits for its stream before it returns), given back afterwards; at most one per concurrently creating thread exists
-struct BigStage
+// The layout of c->stage (doubles), the same for upload and download: [n pool][Gamma pool][C pool][Rij][Rji][nTotal][vBroad]
+// [aDamp][Qelast].  (round 6: the per-atom / per-line rows of the LWHIP_NSTAR group and C ride in it too -- a column of a 1.5D
+// batch made ~40 pageable 656-byte copies for them at creation, each a driver call)
+struct StageLayout
 {
-    double* p = nullptr;
-    size_t n = 0;
-    static std::mutex& mtx()
-    {
-        static std::mutex m;
-        return m;
-    }
-    static std::vector<std::pair<double*, size_t>>& pool()
-    {
-        static std::vector<std::pair<double*, size_t>>* v = new std::vector<std::pair<double*, size_t>>();
-        return *v;
-    }
-    explicit BigStage(size_t doubles)
-    {
-        if (!doubles || doubles * sizeof(double) > ((size_t)64 << 20))
-            return;
-        {
-            std::lock_guard<std::mutex> g(mtx());
-            auto& v = pool();
-            for (size_t i = 0; i < v.size(); ++i)
-                if (v[i].second >= doubles)
-                {
-                    p = v[i].first;
-                    n = v[i].second;
-                    v.erase(v.begin() + (long)i);
-                    return;
-                }
-        }
-        if (hipHostMalloc((void**)&p, doubles * sizeof(double), hipHostMallocDefault) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            p = nullptr; // (no staging: the plain copies)
-            return;
-        }
-        n = doubles;
-    }
-    ~BigStage()
-    {
-        if (!p)
-            return;
-        std::lock_guard<std::mutex> g(mtx());
-        pool().emplace_back(p, n);
-    }
+    size_t nPool, gPool, rPool;
+    double *n, *G, *C, *Rij, *Rji, *NT, *VB, *AD, *QE;
 };
+int stage_layout(lwhip_context* c, StageLayout& L)
+{
+    const size_t Ns = c->Ns, aPool = (size_t)std::max(c->Natom, 1) * Ns, lPool = (size_t)std::max(c->Nline, 1) * Ns;
+    L.nPool = (size_t)c->NlevTot * Ns;
+    L.gPool = (size_t)c->gammaTot;
+    L.rPool = (size_t)c->Ntrans * Ns;
+    const size_t doubles = L.nPool + 2 * L.gPool + 2 * L.rPool + 2 * aPool + 2 * lPool + 8;
+    if (c->stage.reserve(c->device, doubles * sizeof(double), c->stream, true) != hipSuccess)
+        return fail(LWHIP_ERR_DEVICE, "no page-locked memory for the upload stage");
+    L.n = c->stage.as<double>();
+    L.G = L.n + L.nPool;
+    L.C = L.G + L.gPool;
+    L.Rij = L.C + L.gPool;
+    L.Rji = L.Rij + L.rPool;
+    L.NT = L.Rji + L.rPool;
+    L.VB = L.NT + aPool;
+    L.AD = L.VB + aPool;
+    L.QE = L.AD + lPool;
+    return LWHIP_OK;
+}
 }
 static int upload_impl(lwhip_context* c, uint32_t mask);
 int lwhip_upload(lwhip_context* c, uint32_t mask)
@@ -574,7 +682,7 @@ int lwhip_upload(lwhip_context* c, uint32_t mask)
     // stream has drained before either can go away)
     const int st = upload_impl(c, mask);
     if (st != LWHIP_OK)
-        (void)hipStreamSynchronize(c->stream);
+        (void)c->mem.settle();
     return st;
 }
 static int upload_impl(lwhip_context* c, uint32_t mask)
@@ -583,7 +691,7 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
     const lwhip_problem& p = c->prob;
     const size_t Ns = c->Ns, Nla = c->Nla, Nr = c->Nrays;
     const size_t l0 = c->laStart;
-    std::vector<double> rmuzHost; // (lives until the synchronisation at the end)
+    std::vector<double> rmuzHost; // (lives until the stream has drained, at the end)
     bool phiSymUp = true;         // (LWHIP_PROFILES: the uploaded profiles are the same for both directions of every angle)
     if (mask & LWHIP_GAMMA)
         c->prefillPending = false; // the host pre-fill being uploaded supersedes it
@@ -625,7 +733,7 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
                     geo[4 * k + 2] = 1.0 / (std::fabs(p.height[k - 1] - p.height[k]) + std::fabs(p.height[k] - p.height[k + 1]));
                 geo[4 * k + 3] = 1.0 / p.temperature[k];
             }
-            HIP_TRY(h2d_copy(c->geo.p, geo.data(), geo.size() * sizeof(double), c->stream));
+            H2D(c->geo.p, geo.data(), geo.size());
             std::vector<double> geoT;
             if (c->laneSweep)
             {
@@ -635,7 +743,7 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
                 for (size_t k = 0; k < Ns; ++k)
                     for (int q = 0; q < 4; ++q)
                         geoT[q * st + k + 1] = geo[4 * k + q];
-                HIP_TRY(h2d_copy(c->geoT.p, geoT.data(), geoT.size() * sizeof(double), c->stream));
+                H2D(c->geoT.p, geoT.data(), geoT.size());
             }
             std::vector<double> bcB;
             if (c->laneSweep)
@@ -654,48 +762,49 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
                     for (int q = 0; q < 4; ++q)
                         bcB[4 * la + q] = planck(p.temperature[kk[q]], p.wavelength[l0 + la]);
                 if (c->bcPlanck.n < bcB.size())
-                    HIP_TRY(c->bcPlanck.alloc(bcB.size()));
-                HIP_TRY(h2d_copy(c->bcPlanck.p, bcB.data(), bcB.size() * sizeof(double), c->stream));
+                    HIP_TRY(c->bcPlanck.alloc(c->mem, bcB.size()));
+                H2D(c->bcPlanck.p, bcB.data(), bcB.size());
             }
-            if (!h2d_batch()) // (a gathered upload has copied them already)
-                HIP_TRY(hipStreamSynchronize(c->stream)); // `geo`, `bcB` are locals
+            HIP_TRY(c->mem.settle()); // `geo`, `geoT`, `bcB` are locals
         }
     }
     // Column batches (round 6): the four [Nla, Ns] arrays of a column -- 7.6 MB at 2 908 wavelengths -- go through a pinned
-    // staging block of this call (a pool of them, one per creating thread at a time): the host copy runs in parallel on the
-    // creating threads, while four pageable hipMemcpyAsync per column took ~1.5 ms each INSIDE the runtime's lock -- the
-    // serial part of setting up 512 columns.
-    BigStage big(c->batchHint > 1 && !h2d_batch() ? (size_t)4 * Nla * Ns : 0);
-    auto h2d_big = [&](double* dst, const double* src, size_t count, size_t slot) -> hipError_t {
-        if (h2d_batch())
-            return h2d_copy(dst, src, count * sizeof(double), c->stream);
-        if (!big.p)
-            return hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        double* st = big.p + slot * Nla * Ns;
-        std::memcpy(st, src, count * sizeof(double));
-        return hipMemcpyAsync(dst, st, count * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    };
-    if (mask & LWHIP_BACKGROUND)
+    // staging block of this call (out of the pinned pool, back when the call returns and the stream has drained) unless a
+    // gathered upload takes them: the host copy runs in parallel on the creating threads, while four pageable hipMemcpyAsync per
+    // column took ~1.5 ms each INSIDE the runtime's lock -- the serial part of setting up 512 columns.
+    const struct
     {
-        HIP_TRY(h2d_big(c->bgChi.p, p.bgChi + l0 * Ns, Nla * Ns, 0));
-        HIP_TRY(h2d_big(c->bgEta.p, p.bgEta + l0 * Ns, Nla * Ns, 1));
-        HIP_TRY(h2d_big(c->bgSca.p, p.bgSca + l0 * Ns, Nla * Ns, 2));
-    }
-    if (mask & LWHIP_J)
-        HIP_TRY(h2d_big(c->J.p, p.J + l0 * Ns, Nla * Ns, 3));
+        double* dst;
+        const double* src;
+        bool on;
+    } big[4] = { { c->bgChi.p, p.bgChi + l0 * Ns, (mask & LWHIP_BACKGROUND) != 0 }, { c->bgEta.p, p.bgEta + l0 * Ns, (mask & LWHIP_BACKGROUND) != 0 },
+                 { c->bgSca.p, p.bgSca + l0 * Ns, (mask & LWHIP_BACKGROUND) != 0 }, { c->J.p, p.J + l0 * Ns, (mask & LWHIP_J) != 0 } };
+    PinnedBlock bigStage;
+    if (c->batchHint > 1 && !c->mem.batch && (mask & (LWHIP_BACKGROUND | LWHIP_J)) && 4 * Nla * Ns * sizeof(double) <= ((size_t)64 << 20))
+        (void)bigStage.reserve(c->device, 4 * Nla * Ns * sizeof(double), c->stream); // (none to be had: the plain copies)
+    for (int q = 0; q < 4; ++q)
+        if (big[q].on)
+        {
+            const double* src = big[q].src;
+            if (bigStage.host)
+            {
+                double* st = bigStage.as<double>() + q * Nla * Ns;
+                std::memcpy(st, src, Nla * Ns * sizeof(double));
+                src = st;
+            }
+            H2D(big[q].dst, src, Nla * Ns);
+        }
     if (mask & LWHIP_BC)
     {
         if (p.zLowerBc.type == LWHIP_BC_CALLABLE)
         {
             H2D(c->lowerBcData.p, p.zLowerBc.bcData + l0 * p.zLowerBc.Nmu * c->Nx, Nla * p.zLowerBc.Nmu * (size_t)c->Nx);
-            HIP_TRY(hipMemcpyAsync(c->lowerIdx.p, p.zLowerBc.idxs, Nr * 2 * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c->mem.h2d(c->lowerIdx.p, p.zLowerBc.idxs, Nr * 2 * sizeof(int32_t)));
         }
         if (p.zUpperBc.type == LWHIP_BC_CALLABLE)
         {
             H2D(c->upperBcData.p, p.zUpperBc.bcData + l0 * p.zUpperBc.Nmu * c->Nx, Nla * p.zUpperBc.Nmu * (size_t)c->Nx);
-            HIP_TRY(hipMemcpyAsync(c->upperIdx.p, p.zUpperBc.idxs, Nr * 2 * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c->mem.h2d(c->upperIdx.p, p.zUpperBc.idxs, Nr * 2 * sizeof(int32_t)));
         }
         if (c->is2d && !p.grid2d->periodic)
         {
@@ -710,18 +819,18 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
             if (c->xbcLow.n < Nla * nLow || c->xbcUp.n < Nla * nUp || !c->xIdxLow.p)
                 HIP_TRY(hipStreamSynchronize(c->stream)); // nothing may still read a buffer about to be replaced
             if (c->xbcLow.n < Nla * nLow)
-                HIP_TRY(c->xbcLow.alloc(Nla * nLow));
+                HIP_TRY(c->xbcLow.alloc(c->mem, Nla * nLow));
             if (c->xbcUp.n < Nla * nUp)
-                HIP_TRY(c->xbcUp.alloc(Nla * nUp));
+                HIP_TRY(c->xbcUp.alloc(c->mem, Nla * nUp));
             if (!c->xIdxLow.p)
             {
-                HIP_TRY(c->xIdxLow.alloc(Nr * 2));
-                HIP_TRY(c->xIdxUp.alloc(Nr * 2));
+                HIP_TRY(c->xIdxLow.alloc(c->mem, Nr * 2));
+                HIP_TRY(c->xIdxUp.alloc(c->mem, Nr * 2));
             }
             H2D(c->xbcLow.p, g.xLowerBc->bcData + l0 * nLow, Nla * nLow);
             H2D(c->xbcUp.p, g.xUpperBc->bcData + l0 * nUp, Nla * nUp);
-            HIP_TRY(hipMemcpyAsync(c->xIdxLow.p, g.xLowerBc->idxs, Nr * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->xIdxUp.p, g.xUpperBc->idxs, Nr * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c->mem.h2d(c->xIdxLow.p, g.xLowerBc->idxs, Nr * 2 * sizeof(int32_t)));
+            HIP_TRY(c->mem.h2d(c->xIdxUp.p, g.xUpperBc->idxs, Nr * 2 * sizeof(int32_t)));
         }
     }
     if (mask & LWHIP_NSTAR)
@@ -729,27 +838,11 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
     std::vector<double> ratioHost;
     if (mask & LWHIP_NSTAR)
         ratioHost.assign((size_t)std::max(c->Ncont, 1) * Ns, 1.0);
-    // staging layout (doubles): [n pool][Gamma pool][C pool][Rij][Rji][nTotal][vBroad][aDamp][Qelast]
-    // (round 6: the per-atom / per-line rows of the LWHIP_NSTAR group and C ride in it too -- a column of a 1.5D batch made
-    // ~40 pageable 656-byte copies for them at creation, each a driver call)
-    const size_t nPool = (size_t)c->NlevTot * Ns, gPool = (size_t)c->gammaTot, rPool = (size_t)c->Ntrans * Ns;
-    const size_t aPool = (size_t)std::max(c->Natom, 1) * Ns, lPool = (size_t)std::max(c->Nline, 1) * Ns;
-    if (!c->stage)
-    {
-        c->stageDoubles = nPool + 2 * gPool + 2 * rPool + 2 * aPool + 2 * lPool + 8;
-        c->stage = (double*)pinned_acquire(c->device, c->stageDoubles * sizeof(double), nullptr);
-        if (!c->stage)
-            return fail(LWHIP_ERR_DEVICE, "lwhip_upload: no page-locked memory for the upload stage");
-    }
-    double* stN = c->stage;
-    double* stG = stN + nPool;
-    double* stC = stG + gPool;
-    double* stRij = stC + gPool;
-    double* stRji = stRij + rPool;
-    double* stNT = stRji + rPool;
-    double* stVB = stNT + aPool;
-    double* stAD = stVB + aPool;
-    double* stQE = stAD + lPool;
+    StageLayout L;
+    if (const int stl = stage_layout(c, L); stl != LWHIP_OK)
+        return stl;
+    const size_t nPool = L.nPool, gPool = L.gPool, rPool = L.rPool;
+    double *stN = L.n, *stG = L.G, *stC = L.C, *stRij = L.Rij, *stRji = L.Rji, *stNT = L.NT, *stVB = L.VB, *stAD = L.AD, *stQE = L.QE;
     bool anyR = false;
     // (a pool goes up as one copy when every row of it is given; otherwise row by row as before)
     bool allC = (mask & LWHIP_COLLISIONS) != 0, allAD = (mask & LWHIP_NSTAR) != 0, allQE = (mask & LWHIP_NSTAR) != 0;
@@ -865,8 +958,8 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
         H2D(c->ratio.p, ratioHost.data(), ratioHost.size());
     if (mask & LWHIP_PROFILES)
     {
-        if (H2DBatch* b = h2d_batch())
-            HIP_TRY(b->flush()); // (kernels that read what was uploaded follow)
+        if (c->mem.batch)
+            HIP_TRY(c->mem.batch->flush()); // (kernels that read what was uploaded follow)
         const int str = retile_profiles(c);
         if (str != LWHIP_OK)
             return str;
@@ -875,8 +968,9 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
     }
     else if ((mask & (LWHIP_ATMOS | LWHIP_NSTAR)) && c->deviceProfiles)
         c->profilesStale = true; // phi / wphi follow the new velocities and widths before the next sweep
-    if (!h2d_batch()) // (a gathered upload holds copies of the sources; lwhip_create sends it and waits)
-        HIP_TRY(hipStreamSynchronize(c->stream));
+    // (a gathered upload holds copies of its sources -- lwhip_create sends it and waits --, every other copy reads its source
+    // where it lies: the call-local ones among them must not outlive this call)
+    HIP_TRY(c->mem.settle());
     return LWHIP_OK;
 }
 
@@ -936,19 +1030,11 @@ static int download_impl(lwhip_context* c, uint32_t mask)
         D2H(p.depthEta + l0 * Nr * 2 * Ns, c->depthEta.p, Nla * Nr * 2 * Ns);
         D2H(p.depthI + l0 * Nr * 2 * Ns, c->depthI.p, Nla * Nr * 2 * Ns);
     }
-    const size_t nPool = (size_t)c->NlevTot * Ns, gPool = (size_t)c->gammaTot, rPool = (size_t)c->Ntrans * Ns;
-    if (!c->stage)
-    {
-        // (the same size as lwhip_upload's layout: whoever comes first allocates)
-        c->stageDoubles = nPool + 2 * gPool + 2 * rPool + 2 * (size_t)std::max(c->Natom, 1) * Ns + 2 * (size_t)std::max(c->Nline, 1) * Ns + 8;
-        c->stage = (double*)pinned_acquire(c->device, c->stageDoubles * sizeof(double), nullptr);
-        if (!c->stage)
-            return fail(LWHIP_ERR_DEVICE, "lwhip_upload: no page-locked memory for the upload stage");
-    }
-    double* stN = c->stage;
-    double* stG = stN + nPool;
-    double* stRij = stG + 2 * gPool;
-    double* stRji = stRij + rPool;
+    StageLayout L;
+    if (const int stl = stage_layout(c, L); stl != LWHIP_OK)
+        return stl;
+    const size_t nPool = L.nPool, gPool = L.gPool, rPool = L.rPool;
+    double *stN = L.n, *stG = L.G, *stRij = L.Rij, *stRji = L.Rji;
     if ((mask & LWHIP_POPS) && nPool)
         D2H(stN, c->n.p, nPool);
     if ((mask & LWHIP_GAMMA) && gPool)

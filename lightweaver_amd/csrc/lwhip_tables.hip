@@ -310,9 +310,9 @@ int build_tables(lwhip_context* c)
             rho.insert(rho.end(), H.rhoCoeffs[q], H.rhoCoeffs[q] + n);
         }
         rho.resize(rho.size() + 64, lwhip_rho_coeff{ 0, 0, 0.0 }); // (a ray's last block of depths reads past its row)
-        HIP_TRY(c->hRho.upload(rho));
+        HIP_TRY(c->hRho.upload(c->mem, rho));
         std::vector<int32_t> l2h(c->hLa2hHost.begin() + c->laStart, c->hLa2hHost.begin() + c->laEnd); // (indexed by the shard's wavelength)
-        HIP_TRY(c->hLa2h.upload(l2h));
+        HIP_TRY(c->hLa2h.upload(c->mem, l2h));
         if (H.NhPrd > 0)
         {
             const size_t ncell = (size_t)H.NhPrd * Nr * 2 * Ns;
@@ -324,10 +324,10 @@ int build_tables(lwhip_context* c)
                     return fail(LWHIP_ERR_INVALID, "hybrid PRD: JCoeffs row outside JRest");
             std::vector<lwhip_j_coeff> jc(H.jCoeffs, H.jCoeffs + nj);
             jc.resize(jc.size() + 1, lwhip_j_coeff{ 0.0, 0, 0 });
-            HIP_TRY(c->hJOff.upload(off));
-            HIP_TRY(c->hJCoef.upload(jc));
+            HIP_TRY(c->hJOff.upload(c->mem, off));
+            HIP_TRY(c->hJCoef.upload(c->mem, jc));
         }
-        HIP_TRY(c->JRest.alloc_zero((size_t)H.NprdLambda * Ns)); // (accumulated into by atomics)
+        HIP_TRY(c->JRest.alloc_zero(c->mem, (size_t)H.NprdLambda * Ns)); // (accumulated into by atomics)
     }
     c->trans.clear();
     c->Nline = c->Ncont = 0;
@@ -1309,17 +1309,17 @@ int build_tables(lwhip_context* c)
             };
             std::vector<int32_t> o, e;
             lists(tileSlotTr, c->nTileChunks, o, e);
-            HIP_TRY(c->detOff.upload_or_borrow(o, like ? &like->detOff : nullptr));
-            HIP_TRY(c->detEnt.upload_or_borrow(e, like ? &like->detEnt : nullptr));
+            HIP_TRY(c->detOff.upload_or_borrow(c->mem, o, like ? &like->detOff : nullptr));
+            HIP_TRY(c->detEnt.upload_or_borrow(c->mem, e, like ? &like->detEnt : nullptr));
             if (!tileListPrd.empty())
             {
                 lists(swPrd.slotTr, (int)swPrd.chunkTile.size() - 1, o, e);
-                HIP_TRY(c->detOffPrd.upload_or_borrow(o, like ? &like->detOffPrd : nullptr));
-                HIP_TRY(c->detEntPrd.upload_or_borrow(e, like ? &like->detEntPrd : nullptr));
+                HIP_TRY(c->detOffPrd.upload_or_borrow(c->mem, o, like ? &like->detOffPrd : nullptr));
+                HIP_TRY(c->detEntPrd.upload_or_borrow(c->mem, e, like ? &like->detEntPrd : nullptr));
             }
             const size_t nch = std::max<size_t>(c->nTileChunks, tileListPrd.empty() ? 0 : swPrd.chunkTile.size() - 1);
-            HIP_TRY(c->detSlab.alloc(nch * c->maxCTTile * 4 * Ns));
-            HIP_TRY(c->detPart.alloc(det_reduce_scratch_doubles((int)Ns, c->Ntrans)));
+            HIP_TRY(c->detSlab.alloc(c->mem, nch * c->maxCTTile * 4 * Ns));
+            HIP_TRY(c->detPart.alloc(c->mem, det_reduce_scratch_doubles((int)Ns, c->Ntrans)));
         }
         postChunkTile = po.chunkTile;
         postSlotTr = po.slotTr;
@@ -1407,36 +1407,36 @@ int build_tables(lwhip_context* c)
             lw.push_back(0.0);
             lq.push_back(0.0);
         }
-        HIP_TRY(c->lineWave.upload_or_borrow(lw, like ? &like->lineWave : nullptr));
-        HIP_TRY(c->lineWlam.upload_or_borrow(lq, like ? &like->lineWlam : nullptr));
+        HIP_TRY(c->lineWave.upload_or_borrow(c->mem, lw, like ? &like->lineWave : nullptr));
+        HIP_TRY(c->lineWlam.upload_or_borrow(c->mem, lq, like ? &like->lineWlam : nullptr));
     }
-    HIP_TRY(c->par.upload_or_borrow(par, like ? &like->par : nullptr));
-    HIP_TRY(c->dtrans.upload_or_borrow(dt, like ? &like->dtrans : nullptr));
-    HIP_TRY(c->laHdr.upload_or_borrow(hdr, like ? &like->laHdr : nullptr));
-    HIP_TRY(c->slots.upload_or_borrow(slots, like ? &like->slots : nullptr));
+    HIP_TRY(c->par.upload_or_borrow(c->mem, par, like ? &like->par : nullptr));
+    HIP_TRY(c->dtrans.upload_or_borrow(c->mem, dt, like ? &like->dtrans : nullptr));
+    HIP_TRY(c->laHdr.upload_or_borrow(c->mem, hdr, like ? &like->laHdr : nullptr));
+    HIP_TRY(c->slots.upload_or_borrow(c->mem, slots, like ? &like->slots : nullptr));
     {
         std::vector<int32_t> st32(slotTr.begin(), slotTr.end());
         if (st32.empty())
             st32.push_back(0);
-        HIP_TRY(c->slotTrD.upload_or_borrow(st32, like ? &like->slotTrD : nullptr));
+        HIP_TRY(c->slotTrD.upload_or_borrow(c->mem, st32, like ? &like->slotTrD : nullptr));
     }
     c->hdrHost = hdr;
     c->contLaHost = contLaHost;
-    HIP_TRY(c->progs.upload_or_borrow(progs, like ? &like->progs : nullptr));
-    HIP_TRY(c->progRows.upload_or_borrow(progRows, like ? &like->progRows : nullptr));
-    HIP_TRY(c->progEnts.upload_or_borrow(progEnts, like ? &like->progEnts : nullptr));
+    HIP_TRY(c->progs.upload_or_borrow(c->mem, progs, like ? &like->progs : nullptr));
+    HIP_TRY(c->progRows.upload_or_borrow(c->mem, progRows, like ? &like->progRows : nullptr));
+    HIP_TRY(c->progEnts.upload_or_borrow(c->mem, progEnts, like ? &like->progEnts : nullptr));
     if (contLaHost.empty())
         contLaHost.push_back(0);
     c->nContLa = (c->rowsTot > 0) ? (int)contLaHost.size() : 0;
-    HIP_TRY(c->contLa.upload_or_borrow(contLaHost, like ? &like->contLa : nullptr));
-    HIP_TRY(c->rayAll.upload_or_borrow(rayAll, like ? &like->rayAll : nullptr));
-    HIP_TRY(c->rayUp.upload_or_borrow(rayUp, like ? &like->rayUp : nullptr));
+    HIP_TRY(c->contLa.upload_or_borrow(c->mem, contLaHost, like ? &like->contLa : nullptr));
+    HIP_TRY(c->rayAll.upload_or_borrow(c->mem, rayAll, like ? &like->rayAll : nullptr));
+    HIP_TRY(c->rayUp.upload_or_borrow(c->mem, rayUp, like ? &like->rayUp : nullptr));
     if (c->tiled)
     {
-        auto up = [](auto& buf, auto& v, const auto* from) -> hipError_t {
+        auto up = [c](auto& buf, auto& v, const auto* from) -> hipError_t {
             if (v.empty())
                 v.resize(1);
-            return buf.upload_or_borrow(v, from);
+            return buf.upload_or_borrow(c->mem, v, from);
         };
         std::vector<DevContRec> cr(std::max<size_t>(slots.size(), 1), DevContRec{});
         std::vector<DevPostProg> pp;
@@ -1468,7 +1468,7 @@ int build_tables(lwhip_context* c)
                     cr[base + q] = r;
                 }
             }
-            HIP_TRY(c->contRec.upload_or_borrow(cr, like ? &like->contRec : nullptr));
+            HIP_TRY(c->contRec.upload_or_borrow(c->mem, cr, like ? &like->contRec : nullptr));
         }
         if (c->laneSweep)
         {
@@ -1481,7 +1481,7 @@ int build_tables(lwhip_context* c)
                     return fail(LWHIP_ERR_UNSUPPORTED, "lane sweep: post program");
                 ppWide[t] = wide ? 1 : 0;
             }
-            HIP_TRY(c->postProg.upload_or_borrow(pp, like ? &like->postProg : nullptr));
+            HIP_TRY(c->postProg.upload_or_borrow(c->mem, pp, like ? &like->postProg : nullptr));
             if (std::getenv("LWHIP_VERBOSE"))
             {
                 // which program words occur (the finish serves the common ones with fixed registers)
@@ -1632,10 +1632,13 @@ int build_tables(lwhip_context* c)
             if (c->chunkOrderOn)
             {
                 orderHost.resize(c->chunkOrder.n);
-                HIP_TRY(hipMemcpy(orderHost.data(), c->chunkOrder.p, orderHost.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (c->mem.batch)
+                    HIP_TRY(c->mem.batch->flush()); // (its upload may be in the gathered stage)
+                HIP_TRY(hipMemcpyAsync(orderHost.data(), c->chunkOrder.p, orderHost.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
             }
             auto wgs = wg_records(chunkTile, c->chunkOrderOn ? &orderHost : nullptr, c->chunkSplitOn ? &laneChunkSplit : nullptr, c->laneSplit);
-            HIP_TRY(c->laneWg.upload_or_borrow(wgs, like ? &like->laneWg : nullptr));
+            HIP_TRY(c->laneWg.upload_or_borrow(c->mem, wgs, like ? &like->laneWg : nullptr));
             // which tiles run the generic kind (no compiled kind for their line / mixed-continuum counts), and for those the
             // feed bytes of every (continuum, slot) pair -- DevLaneFin::feed holds two slots' worth
             std::vector<int32_t> genOf(std::max<size_t>(tiles.size(), 1), -1);
@@ -1687,11 +1690,11 @@ int build_tables(lwhip_context* c)
             if (c->momA > 0)
             {
                 const size_t nWg = std::max<size_t>(chunkTile.size(), chunkTilePrd.size());
-                HIP_TRY(c->momScratch.alloc(nWg * c->tileWaves * (size_t)c->momA * c->laneD * 64)); // (written before it is read: first ray / per point)
+                HIP_TRY(c->momScratch.alloc(c->mem, nWg * c->tileWaves * (size_t)c->momA * c->laneD * 64)); // (written before it is read: first ray / per point)
             }
             if (feedG.empty())
                 feedG.push_back(0);
-            HIP_TRY(c->laneFeedG.upload_or_borrow(feedG, like ? &like->laneFeedG : nullptr));
+            HIP_TRY(c->laneFeedG.upload_or_borrow(c->mem, feedG, like ? &like->laneFeedG : nullptr));
             auto tile_records = [&](const std::vector<DevTileSlot>& ts) {
                 std::vector<DevLaneTile> v(std::max<size_t>(tiles.size(), 1), DevLaneTile{});
                 for (size_t t = 0; t < tiles.size(); ++t)
@@ -1723,13 +1726,13 @@ int build_tables(lwhip_context* c)
             };
             {
                 auto v = tile_records(tslots);
-                HIP_TRY(c->laneTiles.upload_or_borrow(v, like ? &like->laneTiles : nullptr));
+                HIP_TRY(c->laneTiles.upload_or_borrow(c->mem, v, like ? &like->laneTiles : nullptr));
                 if (!tslotsPrd.empty() && tslotsPrd.size() == tslots.size() && !tileListPrd.empty())
                 {
                     v = tile_records(tslotsPrd);
-                    HIP_TRY(c->laneTilesPrd.upload_or_borrow(v, like ? &like->laneTilesPrd : nullptr));
+                    HIP_TRY(c->laneTilesPrd.upload_or_borrow(c->mem, v, like ? &like->laneTilesPrd : nullptr));
                     auto wp = wg_records(chunkTilePrd, nullptr, nullptr, c->laneSplitPrd);
-                    HIP_TRY(c->laneWgPrd.upload_or_borrow(wp, like ? &like->laneWgPrd : nullptr));
+                    HIP_TRY(c->laneWgPrd.upload_or_borrow(c->mem, wp, like ? &like->laneWgPrd : nullptr));
                 }
             }
             std::vector<DevLaneRay> rays(std::max<size_t>(tiles.size() * L, 1), DevLaneRay{});
@@ -1794,9 +1797,9 @@ int build_tables(lwhip_context* c)
                     }
                 }
             }
-            HIP_TRY(c->laneRays.upload_or_borrow(rays, like ? &like->laneRays : nullptr));
-            HIP_TRY(c->laneFin.upload_or_borrow(fin, like ? &like->laneFin : nullptr));
-            HIP_TRY(c->laneFinPar.upload_or_borrow(finPar, like ? &like->laneFinPar : nullptr));
+            HIP_TRY(c->laneRays.upload_or_borrow(c->mem, rays, like ? &like->laneRays : nullptr));
+            HIP_TRY(c->laneFin.upload_or_borrow(c->mem, fin, like ? &like->laneFin : nullptr));
+            HIP_TRY(c->laneFinPar.upload_or_borrow(c->mem, finPar, like ? &like->laneFinPar : nullptr));
         }
         HIP_TRY(up(c->chunkTilePrd, chunkTilePrd, like ? &like->chunkTilePrd : nullptr));
         HIP_TRY(up(c->tileListPrd, tileListPrd, like ? &like->tileListPrd : nullptr));
@@ -1807,12 +1810,12 @@ int build_tables(lwhip_context* c)
         HIP_TRY(up(c->postSlotTr, postSlotTr, like ? &like->postSlotTr : nullptr));
         HIP_TRY(up(c->postCs, postCs, like ? &like->postCs : nullptr));
     }
-    HIP_TRY(c->transLi.upload_or_borrow(li, like ? &like->transLi : nullptr));
-    HIP_TRY(c->transLj.upload_or_borrow(lj, like ? &like->transLj : nullptr));
-    HIP_TRY(c->atomNlevel.upload_or_borrow(aNl, like ? &like->atomNlevel : nullptr));
-    HIP_TRY(c->atomDetailed.upload_or_borrow(aDet, like ? &like->atomDetailed : nullptr));
-    HIP_TRY(c->atomTrOffD.upload_or_borrow(atomTrOff32, like ? &like->atomTrOffD : nullptr));
-    HIP_TRY(c->atomGammaOff.upload(c->gammaOff));
+    HIP_TRY(c->transLi.upload_or_borrow(c->mem, li, like ? &like->transLi : nullptr));
+    HIP_TRY(c->transLj.upload_or_borrow(c->mem, lj, like ? &like->transLj : nullptr));
+    HIP_TRY(c->atomNlevel.upload_or_borrow(c->mem, aNl, like ? &like->atomNlevel : nullptr));
+    HIP_TRY(c->atomDetailed.upload_or_borrow(c->mem, aDet, like ? &like->atomDetailed : nullptr));
+    HIP_TRY(c->atomTrOffD.upload_or_borrow(c->mem, atomTrOff32, like ? &like->atomTrOffD : nullptr));
+    HIP_TRY(c->atomGammaOff.upload(c->mem, c->gammaOff));
     tick("device tables, lane records");
     return LWHIP_OK;
 }

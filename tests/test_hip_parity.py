@@ -609,6 +609,38 @@ def test_column_batch_vs_oracle(gpu, fused, sweep, static):
         assert up.dJMax == pytest.approx(dj, rel=1e-6)
 
 
+def test_column_batch_on_a_side_stream_vs_oracle(gpu, monkeypatch):
+    """A batch made on the caller's own non-blocking stream (torch.cuda.Stream()) with the gathered upload off
+    (LWHIP_H2D_BATCH=0): every borrower's arena is cleared, and its uploads are separate copies, on that stream -- the
+    clearing fill must never land after a copy into the arena.  Every column must match its own CPU run, as in
+    test_column_batch_vs_oracle."""
+    import torch
+    from lightweaver_amd.batch import ColumnBatch
+    monkeypatch.setenv('LWHIP_H2D_BATCH', '0')
+    probs = [models.build_problem(models.perturbed(models.falc82(), seed=100 + i, dv=2.0e3),
+                                  [models.H_6(0.3), models.CaII_6(0.3)], Nrays=3) for i in range(4)]
+    refs = [p.copy() for p in probs]
+    dJref = []
+    for q in refs:
+        oc = OracleContext(q)
+        for it in range(5):
+            q.gamma_prefill()
+            dj = oc.formal_sol_gamma_matrices()
+            if it >= 3:
+                assert oc.stat_equil() == 0
+        dJref.append(dj)
+    side = torch.cuda.Stream()
+    with ColumnBatch(probs, stream=side.cuda_stream) as batch:
+        assert batch._batch is not None
+        ups = batch.iterate(5, nscatter=3)
+        batch.download()
+    side.synchronize()
+    for p, q in zip(probs, refs):
+        compare_problems(p, q, tol=1e-7, what=('J', 'Gamma', 'n'))
+    for up, (dj, _) in zip(ups, dJref):
+        assert up.dJMax == pytest.approx(dj, rel=1e-6)
+
+
 def test_column_batch_gathered_upload_equals_separate_copies(gpu, hip_lib, monkeypatch):
     """A borrower column of a batch uploads everything through ONE copy into a device inbox and ONE scatter kernel
     (H2DBatch / h2d_scatter_kernel); LWHIP_H2D_BATCH=0 (a debug knob) makes the same uploads as separate copies.  Same J and I to
