@@ -93,6 +93,8 @@ enum {
     LWHIP_RATES      = 1 << 10, /* Rij, Rji of every transition                         (down)   */
     LWHIP_DEPTHDATA  = 1 << 11, /* depthData chi, eta, I (only when requested at create)(down)   */
     LWHIP_COLLISIONS = 1 << 12, /* C of every active atom                               (up)     */
+    LWHIP_STOKES     = 1 << 13, /* lwhip_stokes: B, projections, J20 (up); phiQ..psiV of every polarised line (up/down);
+                                 * Quv, J20 (down).  Not part of LWHIP_ALL_*; ignored without lwhip_set_stokes           */
     LWHIP_ALL_INPUTS = (1 << 0) | (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 5) | (1 << 6) |
                        (1 << 7) | (1 << 8) | (1 << 12),
     LWHIP_ALL_OUTPUTS = (1 << 5) | (1 << 6) | (1 << 9) | (1 << 10)
@@ -581,6 +583,63 @@ int lwhip_build_intersections(const lwhip_grid2d* grid, lwhip_intersection* uw, 
 
 /* Voigt profiles phi and weights wphi of every line, on the device. */
 int lwhip_compute_profiles(lwhip_context* ctx);
+
+/* ---- full Stokes (Zeeman-polarised lines), 1D plane-parallel only ------------------------------------------------------
+ * What the reference keeps in Atmosphere (B, cosGamma, cos2chi, sin2chi: Source/LwAtmosphere.hpp:190-200), in every polarised
+ * Transition (phiQ..psiV, Source/LwTransition.hpp:44-51), in ZeemanComponents (Source/LwMisc.hpp:106-111) and in
+ * Spectrum::Quv (Source/LwMisc.hpp:94).  The projections are computed by the caller (Atmosphere::update_projections,
+ * Source/Atmosphere.cpp:47-82), as vlosMu is.  All host pointers are BORROWED as in lwhip_problem. */
+typedef struct lwhip_stokes_line {
+    int32_t atom;          /* index into prob->atoms                                                */
+    int32_t trans;         /* index into that atom's trans (a LWHIP_LINE)                           */
+    int32_t Ncomp;         /* Zeeman components                                                     */
+    int32_t _pad;
+    const int32_t* alpha;  /* [Ncomp] -1 sigma_b, 0 pi, 1 sigma_r                                   */
+    const double* shift;   /* [Ncomp] in Larmor units                                               */
+    const double* strength;/* [Ncomp]                                                               */
+    double* phiQ;          /* [Nred-Nblue, Nrays, 2, Nspace] each, in (LWHIP_STOKES up) / out        */
+    double* phiU;
+    double* phiV;
+    double* psiQ;
+    double* psiU;
+    double* psiV;
+} lwhip_stokes_line;
+
+typedef struct lwhip_stokes {
+    int32_t Nlines;
+    int32_t _pad;
+    const double* B;        /* [Nspace] field strength [T]                                           */
+    const double* cosGamma; /* [Nrays, Nspace]                                                       */
+    const double* cos2chi;  /* [Nrays, Nspace]                                                       */
+    const double* sin2chi;  /* [Nrays, Nspace]                                                       */
+    const lwhip_stokes_line* lines; /* [Nlines]                                                      */
+    double* Quv;            /* [3, Nlambda, Nrays] out: emergent Q, U, V at k = 0                    */
+    double* J20;            /* [Nlambda, Nspace] in (J20 dagger) / out, or NULL (ExtraParams "J20")   */
+} lwhip_stokes;
+
+/* Borrow `stokes` (NULL: forget it) and upload everything it holds (LWHIP_STOKES).  The descriptor and its line list are
+ * copied; the arrays they point to are borrowed for the life of the context or until the next call.  No counterpart in the
+ * reference (it shares host memory).  1D unsharded contexts only (LWHIP_ERR_UNSUPPORTED otherwise, also with hybrid PRD
+ * tables); LWHIP_ERR_INVALID for a line that is not a line or not in the problem. */
+int lwhip_set_stokes(lwhip_context* ctx, const lwhip_stokes* stokes);
+
+/* Transition::compute_polarised_profiles (Source/FormalStokes.cpp:9-117) of every polarised line, on the device: phi, wphi
+ * and phiQ..psiV from the complex Faddeeva function w(v + ia) = H + iF.  Overwrites phi and wphi of those lines on the
+ * device, as the reference does; lwhip_download(LWHIP_PROFILES | LWHIP_STOKES) brings them back. */
+int lwhip_compute_polarised_profiles(lwhip_context* ctx);
+
+/* formal_sol_full_stokes (FsIterationFns::full_stokes_fs, Source/LwFormalInterface.hpp:89; formal_sol_full_stokes_impl and
+ * stokes_fs_core, Source/FormalStokes.cpp:418-723): per (lambda, mu, direction) the DELO-Bezier3 march of the 4x4 system, or
+ * the scalar piecewise_bezier3_1d where no polarised line is active and there is no J20 -- whatever solver the context was
+ * built with.  I [Nlambda, Nrays] and Quv hold the emergent values of the up-going rays (the last ones written, also with
+ * upOnly = 0).  updateJ: J and J20 re-accumulated, res->dJMax and res->dJMaxIdx with the single-thread bookkeeping of
+ * lwhip_set_djmax_index_mode(1) (the reference's loop is serial: max_idx, Source/FormalStokes.cpp:713).
+ * Differences from the reference, stated:
+ *   - Q, U, V at a wavelength without a polarised line (and without J20) are exact zeros; the reference stores what the last
+ *     polarised ray left in its scratch array there (Source/FormalStokes.cpp:610-616).
+ * As in the reference, without updateJ the source function's scattering term uses J dagger = 0 (and J20 dagger = 0): JDag is
+ * only filled when J is updated (Source/FormalStokes.cpp:429-438).  Gamma and the rates are never touched.  res may be NULL. */
+int lwhip_full_stokes_fs(lwhip_context* ctx, int updateJ, int upOnly, lwhip_iter_result* res);
 
 /* Block until all work queued on the context's stream has finished. */
 int lwhip_synchronize(lwhip_context* ctx);

@@ -32,6 +32,7 @@ I = 1 << 9
 RATES = 1 << 10
 DEPTHDATA = 1 << 11
 COLLISIONS = 1 << 12
+STOKES = 1 << 13     # lwhip_stokes arrays (not part of ALL_INPUTS / ALL_OUTPUTS)
 ALL_INPUTS = ATMOS | BACKGROUND | PROFILES | POPS | NSTAR | J | GAMMA | BC | RHOPRD | COLLISIONS
 ALL_OUTPUTS = J | GAMMA | I | RATES
 
@@ -143,6 +144,19 @@ class lwhip_iter_result(C.Structure):
     _fields_ = [('updatedJ', C.c_int32), ('dJMaxIdx', C.c_int32), ('dJMax', C.c_double)]
 
 
+
+class lwhip_stokes_line(C.Structure):
+    """One Zeeman-polarised line of lwhip_stokes: (atom, trans), its components and its six polarised profiles."""
+    _fields_ = [('atom', C.c_int32), ('trans', C.c_int32), ('Ncomp', C.c_int32), ('_pad', C.c_int32),
+                ('alpha', i32p), ('shift', f64p), ('strength', f64p),
+                ('phiQ', f64p), ('phiU', f64p), ('phiV', f64p), ('psiQ', f64p), ('psiU', f64p), ('psiV', f64p)]
+
+
+class lwhip_stokes(C.Structure):
+    _fields_ = [('Nlines', C.c_int32), ('_pad', C.c_int32),
+                ('B', f64p), ('cosGamma', f64p), ('cos2chi', f64p), ('sin2chi', f64p),
+                ('lines', C.POINTER(lwhip_stokes_line)), ('Quv', f64p), ('J20', f64p)]
+
 _RAW = {}
 
 
@@ -233,6 +247,9 @@ SYMBOLS = [
     ('lwhip_sweep_time', C.c_int, [ctx_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ('lwhip_algorithmic_bytes', C.c_int, [ctx_p, C.POINTER(C.c_double)]),
     ('lwhip_sweep_kind', C.c_int, [ctx_p]),
+    ('lwhip_set_stokes', C.c_int, [ctx_p, C.POINTER(lwhip_stokes)]),
+    ('lwhip_compute_polarised_profiles', C.c_int, [ctx_p]),
+    ('lwhip_full_stokes_fs', C.c_int, [ctx_p, C.c_int, C.c_int, C.POINTER(lwhip_iter_result)]),
 ]
 
 

@@ -5,6 +5,8 @@ Names, argument meaning and error behaviour follow Source/LwMiddleLayer.pyx:
     Context.formal_sol                 <- LwContext.formal_sol                  (:3212-3242)
     Context.stat_equil                 <- LwContext.stat_equil                  (:3461-3531)
     Context.prd_redistribute           <- LwContext.prd_redistribute            (:3647-3684)
+    Context.compute_polarised_profiles <- LwContext.compute_profiles(polarised) (:3244-3288 -> Source/FormalStokes.cpp:9-117)
+    Context.single_stokes_fs           <- LwContext.single_stokes_fs            (:3605-3645)
     ExplodingMatrixError               <- lightweaver.utils.ExplodingMatrixError (raised :3509-3514)
 
 The HIP library is mandatory: if it cannot be loaded, or no gfx950 device is visible, construction
@@ -388,6 +390,54 @@ class Context:
         _check(self.lib, self.lib.lwhip_compute_profiles(self._h), 'lwhip_compute_profiles')
         if not deviceResident:
             self.download(abi.PROFILES)
+
+    # -- full Stokes (1D, unsharded) --------------------------------------------------------------------------------------
+    def _stokes_attach(self, J20=None):
+        """Hand prob.stokes (with `J20` as its ExtraParams "J20" array when given) to the library: lwhip_set_stokes
+        uploads everything it holds.  Re-attached whenever the J20 array changes."""
+        st = self.prob.stokes
+        if st is None:
+            raise LwHipError('full Stokes needs Problem.set_stokes(StokesData(...)) first')
+        if J20 is None and st.J20 is not None:
+            st.J20 = None   # (ExtraParams "J20" belongs to one call: without it the next call is an ordinary one)
+        elif J20 is not None and J20 is not st.J20:
+            st.J20 = np.ascontiguousarray(J20, dtype=np.float64)
+            if st.J20.shape != (self.prob.Nlambda, self.prob.Nspace):
+                raise ValueError('J20 must be [Nlambda, Nspace]')
+        key = (id(st), id(st.J20), id(self.prob.Quv))
+        if getattr(self, '_stokes_key', None) != key:
+            self._stokes_desc = self.prob.stokes_descriptor()
+            _check(self.lib, self.lib.lwhip_set_stokes(self._h, C.byref(self._stokes_desc)), 'lwhip_set_stokes')
+            self._stokes_key = key
+            return True
+        return False
+
+    def compute_polarised_profiles(self, deviceResident=False):
+        """Transition::compute_polarised_profiles of every polarised line on the device: phi, wphi and phiQ..psiV.
+        Overwrites phi and wphi of those lines, as the reference does; downloaded unless deviceResident."""
+        fresh = self._stokes_attach(self.prob.stokes.J20 if self.prob.stokes is not None else None)
+        if not deviceResident:
+            self.upload(abi.ATMOS | abi.NSTAR | (0 if fresh else abi.STOKES))
+        _check(self.lib, self.lib.lwhip_compute_polarised_profiles(self._h), 'lwhip_compute_polarised_profiles')
+        if not deviceResident:
+            self.download(abi.PROFILES | abi.STOKES)
+
+    def single_stokes_fs(self, updateJ=False, upOnly=True, J20=None, deviceResident=False) -> IterationUpdate:
+        """formal_sol_full_stokes (LwContext.single_stokes_fs, Source/LwMiddleLayer.pyx:3605-3645): fills prob.I and
+        prob.Quv [3, Nlambda, Nrays] with the emergent Stokes vector; with updateJ also J (and J20) and dJMax / dJMaxIdx
+        (the index the reference's serial loop records).  Q, U, V are exact zeros at wavelengths without a polarised line
+        (and without J20), where the reference leaves an artefact.  J20: [Nlambda, Nspace], read as J20 dagger and
+        overwritten when updateJ."""
+        fresh = self._stokes_attach(J20)
+        if not deviceResident:
+            self.upload(abi.J | abi.POPS | abi.BC | abi.RHOPRD | (0 if fresh else abi.STOKES))
+        res = abi.lwhip_iter_result()
+        st = self.lib.lwhip_full_stokes_fs(self._h, int(bool(updateJ)), int(bool(upOnly)), C.byref(res))
+        _check(self.lib, st, 'lwhip_full_stokes_fs')
+        if not deviceResident:
+            self.download(abi.I | abi.STOKES | (abi.J if updateJ else 0))
+        return IterationUpdate(updatedJ=bool(updateJ), dJMax=res.dJMax if updateJ else 0.0,
+                               dJMaxIdx=res.dJMaxIdx if updateJ else 0, crsw=self.crsw)
 
     # -- multi-GPU split ----------------------------------------------------------------------------------
     def fs_partial(self, lambdaIterate=False):

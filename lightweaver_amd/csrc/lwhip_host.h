@@ -283,6 +283,36 @@ struct HostTrans
 }
 using namespace lwhip;
 
+namespace lwhip
+{
+// full Stokes (lwhip_stokes.hip): one transition as the Stokes gather reads it
+struct StokesTrans
+{
+    int32_t type, gi, gj, Nblue; // (gi, gj: global level rows into the n pool)
+    int32_t prd, row, pol, _pad; // row: ratio row (continua); pol: ordinal among the polarised lines, or -1
+    int64_t parOff, phiOff, rhoOff; // (rhoOff: of the line's own-grid row 0)
+    int64_t polOff, polStride;   // polarised lines: phiQ of the line in the pol pool; the six arrays are polStride apart
+};
+// what lwhip_set_stokes borrowed and its device copies
+struct StokesState
+{
+    bool on = false;
+    lwhip_stokes desc{};
+    std::vector<lwhip_stokes_line> lines;
+    std::vector<int> lineTr;       // global transition index of each polarised line
+    std::vector<int64_t> polOff;   // offset of each line's six arrays in `pol`
+    std::vector<int32_t> laPolHost;// per wavelength: a polarised line is active
+    int64_t polTot = 0;
+    bool polOnDevice = false;      // phiQ..psiV were computed on the device since the last LWHIP_STOKES transfer
+    DevBuf<double> B, proj, pol, Quv, J20, comp, scratch, Isc, dJ;
+    DevBuf<int32_t> alpha, laOff, laTr, laPol, singular;
+    DevBuf<StokesTrans> tr;
+    DevBuf<PolLineArgs> args;
+    std::vector<PolLineArgs> argsHost;
+};
+int stokes_transfer(lwhip_context* c, bool up); // lwhip_upload / lwhip_download of LWHIP_STOKES
+}
+
 struct lwhip_context;
 namespace lwhip
 {
@@ -473,6 +503,7 @@ struct lwhip_context
     DevBuf<double> red, red8, dJ;
     std::vector<double> gatherHost;
     DevBuf<int32_t> status;
+    StokesState stokes;           // lwhip_set_stokes (lwhip_stokes.hip)
 
     bool profiling = false;
     int profEvery = 1, profCount = 0; // time every profEvery-th sweep launch (lwhip_profile_enable(ctx, n))

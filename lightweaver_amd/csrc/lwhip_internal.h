@@ -494,6 +494,32 @@ hipError_t launch_voigt_line(const VoigtLineArgs& a, hipStream_t stream);
 // every line of the list in one launch pair (same Ns and slice count; hostList = what devList holds)
 hipError_t launch_voigt_lines(const VoigtLineArgs* devList, const VoigtLineArgs* hostList, int nLines, hipStream_t stream);
 
+// One polarised line's Zeeman-split profiles (lwhip_voigt.hip; Transition::compute_polarised_profiles,
+// Source/FormalStokes.cpp:9-117).  The whole line's grid (the Stokes path runs on unsharded contexts only).
+struct PolLineArgs
+{
+    int32_t Ns, Nrays, nlt, nComp;
+    double lambda0;
+    const double* wave;     // [nlt] the line's own wavelength grid
+    const double* wlam;     // [nlt] Transition::wlambda
+    const double* vlosMu;   // [Nrays, Ns]
+    const double* wmu;      // [Nrays]
+    const double* vBroad;   // [Ns] of the line's atom
+    const double* aDamp;    // [Ns]
+    const double* B;        // [Ns]
+    const double* cosGamma; // [Nrays, Ns]
+    const double* cos2chi;
+    const double* sin2chi;
+    const int32_t* alpha;   // [nComp]
+    const double* shift;
+    const double* strength;
+    double* phi;            // [nlt, Nrays, 2, Ns]
+    double* wphi;           // [Ns]
+    double* pol;            // [6][nlt, Nrays, 2, Ns]: phiQ, phiU, phiV, psiQ, psiU, psiV
+};
+// every line of the list (device copy devList, host copy hostList): the profiles, then wphi
+hipError_t launch_polarised_profiles(const PolLineArgs* devList, const PolLineArgs* hostList, int nLines, hipStream_t stream);
+
 // one piece of a gathered upload (H2DBatch, lwhip_host.h): `bytes` from offset `off` of the inbox to `dst`
 struct H2DRec
 {

@@ -680,7 +680,9 @@ int lwhip_upload(lwhip_context* c, uint32_t mask)
         return fail(LWHIP_ERR_INVALID, "null context");
     // (the sources of the queued copies are the caller's arrays and this call's own temporaries: on an error path too the
     // stream has drained before either can go away)
-    const int st = upload_impl(c, mask);
+    int st = upload_impl(c, mask);
+    if (st == LWHIP_OK && (mask & LWHIP_STOKES))
+        st = stokes_transfer(c, true);
     if (st != LWHIP_OK)
         (void)c->mem.settle();
     return st;
@@ -981,7 +983,9 @@ int lwhip_download(lwhip_context* c, uint32_t mask)
         return fail(LWHIP_ERR_INVALID, "null context");
     // The caller's arrays are the targets of queued device-to-host copies: whatever path the call leaves by, none of them is
     // still in flight when the caller has its arrays back (it may free them the next moment).
-    const int st = download_impl(c, mask);
+    int st = download_impl(c, mask);
+    if (st == LWHIP_OK && (mask & LWHIP_STOKES))
+        st = stokes_transfer(c, false);
     if (st != LWHIP_OK)
         (void)hipStreamSynchronize(c->stream);
     return st;

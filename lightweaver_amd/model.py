@@ -91,6 +91,73 @@ class Boundary:
     bcData: Optional[np.ndarray] = None    # [Nlambda, Nmu]
 
 
+def update_projections(muz, mux, muy, gammaB, chiB):
+    """cosGamma, cos2chi, sin2chi [Nrays, Nspace] of the field (gammaB, chiB) [Nspace] seen along each ray:
+    Atmosphere::update_projections (Source/Atmosphere.cpp:47-82), with its exact branch for muz == 1."""
+    muz, mux, muy = (np.asarray(v, dtype=np.float64) for v in (muz, mux, muy))
+    gammaB, chiB = np.asarray(gammaB, dtype=np.float64), np.asarray(chiB, dtype=np.float64)
+    Nr, Ns = muz.shape[0], gammaB.shape[0]
+    # (the C library's sin / cos, element by element: numpy's vectorised ones may differ from them in the last bit)
+    import math
+    _cos = lambda x: np.array([math.cos(v) for v in x])
+    _sin = lambda x: np.array([math.sin(v) for v in x])
+    cosGamma, cos2chi, sin2chi = np.empty((Nr, Ns)), np.empty((Nr, Ns)), np.empty((Nr, Ns))
+    for mu in range(Nr):
+        if muz[mu] == 1.0:
+            cosGamma[mu] = _cos(gammaB)
+            cos2chi[mu] = _cos(2.0 * chiB)
+            sin2chi[mu] = _sin(2.0 * chiB)
+            continue
+        cscTheta = 1.0 / np.sqrt(1.0 - muz[mu] ** 2)
+        sinGamma = _sin(gammaB)
+        bx = sinGamma * _cos(chiB)
+        by = sinGamma * _sin(chiB)
+        bz = _cos(gammaB)
+        b3 = mux[mu] * bx + muy[mu] * by + muz[mu] * bz
+        b1 = cscTheta * (bz - muz[mu] * b3)
+        b2 = cscTheta * (muy[mu] * bx - mux[mu] * by)
+        cosGamma[mu] = b3
+        cos2chi[mu] = (b1 ** 2 - b2 ** 2) / (1.0 - b3 ** 2)
+        sin2chi[mu] = 2.0 * b1 * b2 / (1.0 - b3 ** 2)
+    return cosGamma, cos2chi, sin2chi
+
+
+@dataclass
+class StokesLine:
+    """One Zeeman-polarised line: prob.atoms[atom].trans[trans] with its components (ZeemanComponents,
+    Source/LwMisc.hpp:106-111) and its polarised profiles (Transition::phiQ..psiV, Source/LwTransition.hpp:44-51)."""
+    atom: int
+    trans: int
+    alpha: np.ndarray                      # [Ncomp] int32: -1 sigma_b, 0 pi, 1 sigma_r
+    shift: np.ndarray                      # [Ncomp] in Larmor units
+    strength: np.ndarray                   # [Ncomp]
+    phiQ: Optional[np.ndarray] = None      # [NlaT, Nrays, 2, Nspace] each
+    phiU: Optional[np.ndarray] = None
+    phiV: Optional[np.ndarray] = None
+    psiQ: Optional[np.ndarray] = None
+    psiU: Optional[np.ndarray] = None
+    psiV: Optional[np.ndarray] = None
+
+    PROFILES = ('phiQ', 'phiU', 'phiV', 'psiQ', 'psiU', 'psiV')
+
+
+@dataclass
+class StokesData:
+    """The magnetic field and the polarised lines of a full-Stokes problem (Atmosphere B, gammaB, chiB, mux, muy;
+    Source/LwAtmosphere.hpp:190-200).  `Problem.set_stokes` derives the projections."""
+    B: np.ndarray                          # [Nspace] T
+    gammaB: np.ndarray                     # [Nspace] inclination
+    chiB: np.ndarray                       # [Nspace] azimuth
+    mux: np.ndarray                        # [Nrays]
+    muy: np.ndarray                        # [Nrays]
+    lines: List[StokesLine] = field(default_factory=list)
+    cosGamma: Optional[np.ndarray] = None  # [Nrays, Nspace]
+    cos2chi: Optional[np.ndarray] = None
+    sin2chi: Optional[np.ndarray] = None
+    J20: Optional[np.ndarray] = None       # [Nlambda, Nspace] ExtraParams "J20", or None
+    vz: Optional[np.ndarray] = None        # [Nspace] vertical velocity vlosMu was made from (Atmosphere::vz), or None
+
+
 class Problem:
     """Everything `Context&` reaches on the hot path, as owned numpy arrays."""
 
@@ -135,6 +202,56 @@ class Problem:
         for a in self.atoms:
             self._normalise_atom(a)
         self._keepalive = None
+        self.stokes: Optional[StokesData] = None
+        self.Quv = None
+
+    def set_stokes(self, stokes: Optional[StokesData]):
+        """Attach (or drop) the full-Stokes data; computes the projections (update_projections) and allocates Quv
+        [3, Nlambda, Nrays] and every missing polarised profile."""
+        self.stokes = stokes
+        if stokes is None:
+            self.Quv = None
+            return
+        Ns, Nr = self.Nspace, self.Nrays
+        stokes.B = _f64(stokes.B, (Ns,))
+        stokes.gammaB = _f64(stokes.gammaB, (Ns,))
+        stokes.chiB = _f64(stokes.chiB, (Ns,))
+        stokes.mux = _f64(stokes.mux, (Nr,))
+        stokes.muy = _f64(stokes.muy, (Nr,))
+        stokes.cosGamma, stokes.cos2chi, stokes.sin2chi = update_projections(
+            self.muz, stokes.mux, stokes.muy, stokes.gammaB, stokes.chiB)
+        if stokes.J20 is not None:
+            stokes.J20 = _f64(stokes.J20, (self.Nlambda, Ns))
+        for L in stokes.lines:
+            t = self.atoms[L.atom].trans[L.trans]
+            if t.type != abi.LINE:
+                raise ValueError('a polarised transition must be a line')
+            L.alpha = np.ascontiguousarray(L.alpha, dtype=np.int32)
+            L.shift = _f64(L.shift, L.alpha.shape)
+            L.strength = _f64(L.strength, L.alpha.shape)
+            for name in StokesLine.PROFILES:
+                a = getattr(L, name)
+                setattr(L, name, _f64(a, t.phi.shape) if a is not None else np.zeros(t.phi.shape))
+        self.Quv = np.zeros((3, self.Nlambda, Nr))
+
+    def stokes_descriptor(self):
+        """The lwhip_stokes descriptor of `self.stokes` (borrows its arrays; keep the Problem alive)."""
+        st = self.stokes
+        lines = (abi.lwhip_stokes_line * max(len(st.lines), 1))()
+        for i, L in enumerate(st.lines):
+            cl = abi.raw_view(lines[i])
+            cl.atom, cl.trans, cl.Ncomp = int(L.atom), int(L.trans), int(L.alpha.shape[0])
+            cl.alpha, cl.shift, cl.strength = abi.addr(L.alpha), abi.addr(L.shift), abi.addr(L.strength)
+            for name in StokesLine.PROFILES:
+                setattr(cl, name, abi.addr(getattr(L, name)))
+        d = abi.lwhip_stokes()
+        d.Nlines = len(st.lines)
+        d.B, d.cosGamma, d.cos2chi, d.sin2chi = _ptr(st.B), _ptr(st.cosGamma), _ptr(st.cos2chi), _ptr(st.sin2chi)
+        d.lines = C.cast(lines, C.POINTER(abi.lwhip_stokes_line))
+        d.Quv = _ptr(self.Quv)
+        d.J20 = _ptr(st.J20)
+        self._stokes_keepalive = (lines, d)
+        return d
 
     # -- normalisation / allocation of outputs -------------------------------------------------
     def _normalise_atom(self, a: AtomData):
@@ -288,7 +405,7 @@ class Problem:
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k == '_keepalive':
+            if k in ('_keepalive', '_stokes_keepalive'):
                 setattr(new, k, None)
             else:
                 setattr(new, k, copy.deepcopy(v, memo))
