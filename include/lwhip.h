@@ -641,6 +641,19 @@ int lwhip_compute_polarised_profiles(lwhip_context* ctx);
  * only filled when J is updated (Source/FormalStokes.cpp:429-438).  Gamma and the rates are never touched.  res may be NULL. */
 int lwhip_full_stokes_fs(lwhip_context* ctx, int updateJ, int upOnly, lwhip_iter_result* res);
 
+/* Full Stokes of a 1.5D column batch (lwhip_batch_create): what the two calls above do for one context, for every column of
+ * the batch in one set of launches on the batch's stream; each column's results are those of the single-context call on it.
+ * Every column needs Stokes data (lwhip_set_stokes) with the polarised lines of column 0 -- the same transitions with the same
+ * component counts; B, the projections, J20 and the component values may differ.  No device: LWHIP_ERR_DEVICE; a null
+ * batch, a column without Stokes data or with other polarised lines: LWHIP_ERR_INVALID, before anything is launched.
+ * lwhip_batch_compute_polarised_profiles: Transition::compute_polarised_profiles of the polarised lines of every column,
+ * after the plain profiles of the columns whose atmosphere was uploaded since (as lwhip_compute_polarised_profiles). */
+int lwhip_batch_compute_polarised_profiles(lwhip_batch* batch);
+/* formal_sol_full_stokes of every column.  results: [n] or NULL (dJMax / dJMaxIdx when updateJ, as res of
+ * lwhip_full_stokes_fs).  updateJ while a column has a mapped host J: LWHIP_ERR_UNSUPPORTED.  A singular 4 x 4 system:
+ * LWHIP_ERR_SINGULAR naming the first singular column, every column's outputs written all the same. */
+int lwhip_batch_full_stokes_fs(lwhip_batch* batch, int updateJ, int upOnly, lwhip_iter_result* results);
+
 /* Block until all work queued on the context's stream has finished. */
 int lwhip_synchronize(lwhip_context* ctx);
 

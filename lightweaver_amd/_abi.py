@@ -250,6 +250,8 @@ SYMBOLS = [
     ('lwhip_set_stokes', C.c_int, [ctx_p, C.POINTER(lwhip_stokes)]),
     ('lwhip_compute_polarised_profiles', C.c_int, [ctx_p]),
     ('lwhip_full_stokes_fs', C.c_int, [ctx_p, C.c_int, C.c_int, C.POINTER(lwhip_iter_result)]),
+    ('lwhip_batch_compute_polarised_profiles', C.c_int, [C.c_void_p]),
+    ('lwhip_batch_full_stokes_fs', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(lwhip_iter_result)]),
 ]
 
 

@@ -157,6 +157,53 @@ class ColumnBatch:
                 callback(it, ups)
         return ups
 
+    # -- full Stokes (every column with its own prob.stokes, the polarised lines of the first column) -----------------------
+    def compute_polarised_profiles(self, deviceResident=True):
+        """Context.compute_polarised_profiles of every column: phi, wphi and phiQ..psiV of the polarised lines, all columns'
+        lines in one launch list (lwhip_batch_compute_polarised_profiles; per column where the batch is not fused).  Each
+        column's prob.stokes is attached first, with its J20 when it holds one; downloaded unless deviceResident."""
+        if self._batch is None:
+            for c in self.contexts:
+                c.compute_polarised_profiles(deviceResident=deviceResident)
+            return
+        fresh = [c._stokes_attach(c.prob.stokes.J20 if c.prob.stokes is not None else None) for c in self.contexts]
+        if not deviceResident:
+            for c, f in zip(self.contexts, fresh):
+                c.upload(abi.ATMOS | abi.NSTAR | (0 if f else abi.STOKES))
+        lib = self.contexts[0].lib
+        _check(lib, lib.lwhip_batch_compute_polarised_profiles(self._batch), 'lwhip_batch_compute_polarised_profiles')
+        if not deviceResident:
+            for c in self.contexts:
+                c.download(abi.PROFILES | abi.STOKES)
+
+    def single_stokes_fs(self, updateJ=False, upOnly=True, deviceResident=False, sync_host=True):
+        """Context.single_stokes_fs of every column in one set of launches (lwhip_batch_full_stokes_fs): fills each column's
+        prob.I and prob.Quv, with updateJ also its J (and J20).  A column's J20 is its prob.stokes.J20 (None: an ordinary
+        call).  Returns one IterationUpdate per column, or None when sync_host is False.  Not deviceResident: each column's
+        inputs go up and its outputs come back as Context.single_stokes_fs moves them.  An unfused batch runs the columns
+        one after the other."""
+        if self._batch is None:
+            ups = [c.single_stokes_fs(updateJ=updateJ, upOnly=upOnly, J20=c.prob.stokes.J20 if c.prob.stokes is not None else None,
+                                      deviceResident=deviceResident) for c in self.contexts]
+            return ups if sync_host else None
+        import ctypes as C
+        from .context import IterationUpdate
+        fresh = [c._stokes_attach(c.prob.stokes.J20 if c.prob.stokes is not None else None) for c in self.contexts]
+        if not deviceResident:
+            for c, f in zip(self.contexts, fresh):
+                c.upload(abi.J | abi.POPS | abi.BC | abi.RHOPRD | (0 if f else abi.STOKES))
+        lib = self.contexts[0].lib
+        res = (abi.lwhip_iter_result * len(self.contexts))() if sync_host else None
+        _check(lib, lib.lwhip_batch_full_stokes_fs(self._batch, int(bool(updateJ)), int(bool(upOnly)), res),
+               'lwhip_batch_full_stokes_fs')
+        if not deviceResident:
+            for c in self.contexts:
+                c.download(abi.I | abi.STOKES | (abi.J if updateJ else 0))
+        if not sync_host:
+            return None
+        return [IterationUpdate(updatedJ=bool(updateJ), dJMax=r.dJMax if updateJ else 0.0,
+                                dJMaxIdx=r.dJMaxIdx if updateJ else 0, crsw=c.crsw) for r, c in zip(res, self.contexts)]
+
     def download(self, mask=abi.ALL_OUTPUTS | abi.POPS):
         for c in self.contexts:
             c.download(mask)

@@ -2,26 +2,7 @@
 // contexts in one set of launches.
 #include "lwhip_host.h"
 
-// ---- 1.5D column batches: one iteration of n structurally identical contexts in one set of launches ----------
-struct lwhip_batch
-{
-    std::vector<lwhip_context*> ctxs;
-    std::vector<hipStream_t> ownStreams; // what the columns ran on before they joined the batch
-    DevBuf<const TileArgs*> apList;
-    DevBuf<ReduceArgs> rList;
-    DevBuf<ApplyArgs> aList;
-    DevBuf<double> tail;       // [n][2] (dJMax, idx) of every column
-    PinnedBlock tailPinned;
-    std::vector<ApplyArgs> aHost;
-    double aCrsw = 0.0;        // what the device copy of the apply blocks was built with
-    bool aValid = false;
-    DevBuf<StatEqArgs> seList; // stat_equil of all active atoms of every column
-    StatEqArgs se0{};
-    int seMaxNl = 0;
-    DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
-    DevBuf<RetileArgs> retileList;   // ... and their retile arguments
-};
-
+// (struct lwhip_batch: lwhip_host.h)
 
 // device profiles of the batch's columns: every line of every column that needs them (all = the explicit
 // lwhip_batch_compute_profiles, else those whose atmosphere was uploaded since) in ONE launch pair on the batch's stream
@@ -57,12 +38,23 @@ static int batch_compute_profiles(lwhip_batch* b, bool all)
         }
     }
     // ... and their tile-blocked copies, one grid slice per column
-    std::vector<RetileArgs> rl;
     for (lwhip_context* c : todo)
     {
         c->deviceProfiles = true;
         c->profilesStale = false;
         c->phiSym = c->vlosZero;
+    }
+    return batch_retile(b, todo);
+}
+
+namespace lwhip
+{
+int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols)
+{
+    lwhip_context* c0 = b->ctxs[0];
+    std::vector<RetileArgs> rl;
+    for (lwhip_context* c : cols)
+    {
         RetileArgs r;
         if (retile_args(c, r))
             rl.push_back(r);
@@ -81,7 +73,8 @@ static int batch_compute_profiles(lwhip_batch* b, bool all)
     }
     return LWHIP_OK;
 }
-static int batch_ensure_profiles(lwhip_batch* b) { return batch_compute_profiles(b, false); }
+int batch_ensure_profiles(lwhip_batch* b) { return batch_compute_profiles(b, false); }
+}
 
 extern "C"
 {
@@ -206,6 +199,8 @@ void lwhip_batch_destroy(lwhip_batch* b)
         (void)hipSetDevice(b->ctxs[0]->device);
         (void)hipStreamSynchronize(b->ctxs[0]->stream);
         b->tailPinned.release();
+        stokes_batch_release(b->stokes);
+        b->stokes = nullptr;
         for (size_t i = 0; i < b->ctxs.size() && i < b->ownStreams.size(); ++i)
             b->ctxs[i]->stream = b->ownStreams[i];
     }

@@ -311,6 +311,10 @@ struct StokesState
     std::vector<PolLineArgs> argsHost;
 };
 int stokes_transfer(lwhip_context* c, bool up); // lwhip_upload / lwhip_download of LWHIP_STOKES
+// the refusals the Stokes entry points share, the device check first (lwhip_stokes.hip)
+int check_stokes_ctx(lwhip_context* c, const char* what, bool needStokes);
+struct StokesBatch; // what a column batch keeps for its full-Stokes calls (lwhip_stokes_batch.hip)
+void stokes_batch_release(StokesBatch* s);
 }
 
 struct lwhip_context;
@@ -636,4 +640,33 @@ int voigt_line_list(lwhip_context* c, std::vector<VoigtLineArgs>& out);
 int stat_equil_impl(lwhip_context* c, int atom, bool wait, double* dPops = nullptr, int32_t* dPopsMaxIdx = nullptr);
 // lwhip_api2d.hip
 int run_2d(lwhip_context* c, int lambdaIterate, int mode = 0);
+}
+
+// ---- 1.5D column batches: one iteration of n structurally identical contexts in one set of launches (lwhip_batch.hip;
+// their full-Stokes calls: lwhip_stokes_batch.hip) ----------
+struct lwhip_batch
+{
+    std::vector<lwhip_context*> ctxs;
+    std::vector<hipStream_t> ownStreams; // what the columns ran on before they joined the batch
+    DevBuf<const TileArgs*> apList;
+    DevBuf<ReduceArgs> rList;
+    DevBuf<ApplyArgs> aList;
+    DevBuf<double> tail;       // [n][2] (dJMax, idx) of every column
+    PinnedBlock tailPinned;
+    std::vector<ApplyArgs> aHost;
+    double aCrsw = 0.0;        // what the device copy of the apply blocks was built with
+    bool aValid = false;
+    DevBuf<StatEqArgs> seList; // stat_equil of all active atoms of every column
+    StatEqArgs se0{};
+    int seMaxNl = 0;
+    DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
+    DevBuf<RetileArgs> retileList;   // ... and their retile arguments
+    StokesBatch* stokes = nullptr;   // made by the first full-Stokes call
+};
+
+namespace lwhip
+{
+// lwhip_batch.hip
+int batch_ensure_profiles(lwhip_batch* b);                                  // the columns whose profiles went stale
+int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols); // tile-blocked copies of their phi, one launch list
 }

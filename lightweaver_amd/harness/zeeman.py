@@ -107,3 +107,31 @@ def falc_h_ca_stokes(Nrays=3, lineScale=0.2, B=None, gammaB=None, chiB=None, dis
                                lines=polarise_lines(prob, 1)))
     prob.stokes.vz = np.ascontiguousarray(atmos.vlos, dtype=np.float64)
     return prob
+
+
+def stokes_columns(ncol, Nrays=5, lineScale=3.1, seed0=1234):
+    """`ncol` columns of a 1.5D batch for polarised synthesis: seeded perturbed FAL-C (models.perturbed, seeds seed0,
+    seed0 + 1, ...), H + Ca II with the Ca II lines polarised, each column with its own smooth seeded B, gammaB and chiB.
+    The profiles are left to the device (computeProfiles=False)."""
+    from . import models
+    from ..model import StokesData
+    base = models.falc82()
+    ker = np.ones(9) / 9.0
+    probs = []
+    for c in range(ncol):
+        seed = seed0 + c
+        atmos = models.perturbed(base, seed=seed)
+        prob = models.build_problem(atmos, [models.H_6(lineScale), models.CaII_6(lineScale)], Nrays=Nrays,
+                                    computeProfiles=False)
+        rng = np.random.default_rng([seed, 7])
+        Ns = prob.Nspace
+        z = np.linspace(0.0, 1.0, Ns)
+        sm = lambda a: np.convolve(np.pad(a, 4, mode='edge'), ker, mode='valid')  # noqa: E731
+        B = rng.uniform(0.02, 0.2) * (0.5 + z) * (1.0 + 0.2 * sm(rng.standard_normal(Ns)))
+        gammaB = rng.uniform(0.1, 1.4) + rng.uniform(-0.6, 0.6) * z + 0.1 * sm(rng.standard_normal(Ns))
+        chiB = rng.uniform(0.0, 2.0 * np.pi) + rng.uniform(-1.0, 1.0) * z + 0.1 * sm(rng.standard_normal(Ns))
+        prob.set_stokes(StokesData(B=B, gammaB=gammaB, chiB=chiB, mux=np.sqrt(1.0 - prob.muz ** 2),
+                                   muy=np.zeros(Nrays), lines=polarise_lines(prob, 1)))
+        prob.stokes.vz = np.ascontiguousarray(atmos.vlos, dtype=np.float64)
+        probs.append(prob)
+    return probs
