@@ -654,6 +654,42 @@ int lwhip_batch_compute_polarised_profiles(lwhip_batch* batch);
  * LWHIP_ERR_SINGULAR naming the first singular column, every column's outputs written all the same. */
 int lwhip_batch_full_stokes_fs(lwhip_batch* batch, int updateJ, int upOnly, lwhip_iter_result* results);
 
+/* ---- emergent spectra along observer rays (1D) --------------------------------------------------------------------------
+ * LwContext.compute_rays(mus, upOnly=True) (Source/LwMiddleLayer.pyx:3898-4002) from the state resident on the device: for
+ * every wavelength of [laStart, laEnd) and every direction cosine muz[m] the up-going ray is traced with piecewise_bezier3_1d
+ * through chi and S built as lwhip_formal_sol builds them (lines and continua of the active and detailed atoms from the
+ * resident n, background chi / eta / sca, S = (eta + sca J) / chi with the resident J, gij rhoPrd for PRD lines), except that
+ * each line's profile is evaluated inside the kernel for the new direction: phi = H(aDamp, v) / (sqrt(pi) vBroad),
+ * v = ((lambda - lambda0) c / lambda0 + mu v_z) / vBroad.  The directions need not be quadrature nodes and carry no weights.
+ * Nothing of the context changes (phi, wphi, I, J, Gamma, the rates, its rays, its profile bookkeeping), nothing is created,
+ * and only this request crosses to the device.  All pointers are host pointers. */
+#define LWHIP_RAYS_MAX_MU 16
+typedef struct lwhip_rays {
+    int32_t Nmu;            /* 1 .. LWHIP_RAYS_MAX_MU directions                                                    */
+    int32_t laStart, laEnd; /* rows [laStart, laEnd) of the GLOBAL wavelength grid, inside the context's own rows
+                             * (its shard); 0, 0 = all the context holds.  Nla = laEnd - laStart below             */
+    int32_t _pad;
+    const double* muz;      /* [Nmu] direction cosines, 0 < mu <= 1                                                 */
+    const double* vz;       /* [Nspace] vertical velocity, or NULL: vlosMu[0] / muz[0] of the resident atmosphere
+                             * (the 1D convention vlosMu = muz (x) v_z), read on the device                         */
+    const double* lowerBc;  /* [Nla, Nmu] intensity entering at the bottom: required with a CALLABLE lower boundary
+                             * (which has no data for new directions), ignored otherwise                            */
+    double* I;              /* [Nla, Nmu] out: emergent intensity (k = 0)                                           */
+    double* depthChi;       /* [Nla, Nmu, Nspace] out or NULL (all three or none): chi, eta and I along each ray,   */
+    double* depthEta;       /* what DepthData holds for the to-observer direction                                   */
+    double* depthI;
+} lwhip_rays;
+/* Refusals, before anything is queued: no device LWHIP_ERR_DEVICE; a 2D context, hybrid PRD tables, another formal solver
+ * than piecewise_bezier3_1d, Nmu above LWHIP_RAYS_MAX_MU: LWHIP_ERR_UNSUPPORTED; a direction
+ * cosine outside (0, 1], a range outside the context's rows, a CALLABLE lower boundary without lowerBc, a line without aDamp,
+ * neither vz nor vlosMu, one or two of the three depth arrays: LWHIP_ERR_INVALID.  The call returns when the outputs are
+ * in place (one copy back, one wait). */
+int lwhip_compute_rays(lwhip_context* ctx, const lwhip_rays* rays);
+/* The same for every column of a batch in one launch: perColumn [n], each with its own arrays; Nmu, the wavelength range and
+ * the presence of the depth arrays are the same for every column (LWHIP_ERR_INVALID otherwise), the directions, vz and
+ * lowerBc may differ.  Each column's results are the bits of lwhip_compute_rays on it. */
+int lwhip_batch_compute_rays(lwhip_batch* batch, const lwhip_rays* perColumn);
+
 /* Block until all work queued on the context's stream has finished. */
 int lwhip_synchronize(lwhip_context* ctx);
 

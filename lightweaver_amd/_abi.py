@@ -157,6 +157,17 @@ class lwhip_stokes(C.Structure):
                 ('B', f64p), ('cosGamma', f64p), ('cos2chi', f64p), ('sin2chi', f64p),
                 ('lines', C.POINTER(lwhip_stokes_line)), ('Quv', f64p), ('J20', f64p)]
 
+RAYS_MAX_MU = 16     # LWHIP_RAYS_MAX_MU
+
+
+class lwhip_rays(C.Structure):
+    """Observer rays of lwhip_compute_rays: Nmu direction cosines, a range of the global wavelength grid, optional v_z and
+    lower-boundary data, the output arrays (host pointers)."""
+    _fields_ = [('Nmu', C.c_int32), ('laStart', C.c_int32), ('laEnd', C.c_int32), ('_pad', C.c_int32),
+                ('muz', f64p), ('vz', f64p), ('lowerBc', f64p), ('I', f64p),
+                ('depthChi', f64p), ('depthEta', f64p), ('depthI', f64p)]
+
+
 _RAW = {}
 
 
@@ -252,6 +263,8 @@ SYMBOLS = [
     ('lwhip_full_stokes_fs', C.c_int, [ctx_p, C.c_int, C.c_int, C.POINTER(lwhip_iter_result)]),
     ('lwhip_batch_compute_polarised_profiles', C.c_int, [C.c_void_p]),
     ('lwhip_batch_full_stokes_fs', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(lwhip_iter_result)]),
+    ('lwhip_compute_rays', C.c_int, [ctx_p, C.POINTER(lwhip_rays)]),
+    ('lwhip_batch_compute_rays', C.c_int, [C.c_void_p, C.POINTER(lwhip_rays)]),
 ]
 
 

@@ -204,6 +204,34 @@ class ColumnBatch:
         return [IterationUpdate(updatedJ=bool(updateJ), dJMax=r.dJMax if updateJ else 0.0,
                                 dJMaxIdx=r.dJMaxIdx if updateJ else 0, crsw=c.crsw) for r, c in zip(res, self.contexts)]
 
+    # -- emergent spectra along observer rays ------------------------------------------------------------------------------
+    def compute_rays(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False):
+        """Context.compute_rays of every column from its device-resident state, all columns in one set of launches and
+        one copy back (lwhip_batch_compute_rays; an unfused batch runs the columns one after the other).  The same
+        directions and wavelength range for every column; `vz` / `lowerBc`: None, or one array per column.  Returns I
+        [Ncolumns, Nla, Nmu], or with depthData a RaysResult whose I, chi, eta, Idepth carry the column axis first."""
+        import ctypes as C
+        import numpy as np
+        from .context import RaysResult
+        n = len(self.contexts)
+        per = lambda a, i: None if a is None else a[i]  # noqa: E731
+        reqs = [c._rays_request(mus, laStart, laEnd, per(vz, i), per(lowerBc, i), depthData)
+                for i, c in enumerate(self.contexts)]
+        if self._batch is not None:
+            lib = self.contexts[0].lib
+            arr = (abi.lwhip_rays * n)(*[r for r, _, _ in reqs])
+            _check(lib, lib.lwhip_batch_compute_rays(self._batch, arr), 'lwhip_batch_compute_rays')
+        else:
+            for c, (r, _, _) in zip(self.contexts, reqs):
+                _check(c.lib, c.lib.lwhip_compute_rays(c._h, C.byref(r)), 'lwhip_compute_rays')
+        outs = [o for _, o, _ in reqs]
+        I = np.stack([o.I for o in outs]) if outs else np.zeros((0, 0, 0))
+        if not depthData:
+            return I
+        return RaysResult(I=I, mus=outs[0].mus, laStart=outs[0].laStart, laEnd=outs[0].laEnd,
+                          chi=np.stack([o.chi for o in outs]), eta=np.stack([o.eta for o in outs]),
+                          Idepth=np.stack([o.Idepth for o in outs]))
+
     def download(self, mask=abi.ALL_OUTPUTS | abi.POPS):
         for c in self.contexts:
             c.download(mask)

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _abi as abi
-from .model import Problem
+from .model import Problem, check_mus
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('LWHIP_LIB') or os.path.join(_PKG, 'liblwhip.so')  # LWHIP_LIB: an experiment build of the same library
@@ -79,6 +79,18 @@ class IterationUpdate:
     dRhoMaxIdx: Optional[np.ndarray] = None
     dJPrdMax: Optional[np.ndarray] = None     # [NprdSubIter]
     dJPrdMaxIdx: Optional[np.ndarray] = None
+
+
+@dataclass
+class RaysResult:
+    """What compute_rays(depthData=True) returns: the emergent intensity and the run of every ray with depth."""
+    I: np.ndarray                         # [Nla, Nmu] (or [Ncolumns, Nla, Nmu])
+    mus: np.ndarray
+    laStart: int = 0
+    laEnd: int = 0
+    chi: Optional[np.ndarray] = None      # [Nla, Nmu, Nspace]
+    eta: Optional[np.ndarray] = None
+    Idepth: Optional[np.ndarray] = None
 
 
 class Context:
@@ -438,6 +450,55 @@ class Context:
             self.download(abi.I | abi.STOKES | (abi.J if updateJ else 0))
         return IterationUpdate(updatedJ=bool(updateJ), dJMax=res.dJMax if updateJ else 0.0,
                                dJMaxIdx=res.dJMaxIdx if updateJ else 0, crsw=self.crsw)
+
+    # -- emergent spectra along observer rays (1D) ------------------------------------------------------------------------
+    def _rays_request(self, mus, laStart, laEnd, vz, lowerBc, depthData):
+        """The lwhip_rays block of one compute_rays call and the arrays it points to: (struct, RaysResult, keepalive)."""
+        mus = check_mus(mus)
+        Nmu, Ns = mus.shape[0], self.prob.Nspace
+        la0 = int(laStart) if (laStart or laEnd) else self.laStart
+        la1 = int(laEnd) if laEnd else self.laEnd
+        nla = max(la1 - la0, 0)
+        r = abi.lwhip_rays()
+        r.Nmu, r.laStart, r.laEnd = Nmu, la0, la1
+        keep = [mus]
+        r.muz = mus.ctypes.data_as(abi.f64p)
+        if vz is not None:
+            vz = np.ascontiguousarray(vz, dtype=np.float64)
+            if vz.shape != (Ns,):
+                raise ValueError('vz must be [Nspace]')
+            keep.append(vz)
+            r.vz = vz.ctypes.data_as(abi.f64p)
+        if lowerBc is not None:
+            lowerBc = np.ascontiguousarray(lowerBc, dtype=np.float64)
+            if lowerBc.shape != (nla, Nmu):
+                raise ValueError('lowerBc must be [Nla, Nmu] of the requested wavelength range')
+            keep.append(lowerBc)
+            r.lowerBc = lowerBc.ctypes.data_as(abi.f64p)
+        out = RaysResult(I=np.zeros((nla, Nmu)), mus=mus, laStart=la0, laEnd=la1)
+        r.I = out.I.ctypes.data_as(abi.f64p)
+        if depthData:
+            out.chi, out.eta, out.Idepth = (np.zeros((nla, Nmu, Ns)) for _ in range(3))
+            r.depthChi, r.depthEta, r.depthI = (a.ctypes.data_as(abi.f64p) for a in (out.chi, out.eta, out.Idepth))
+        return r, out, keep
+
+    def compute_rays(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False, squeeze=True):
+        """LwContext.compute_rays(mus, upOnly=True) (Source/LwMiddleLayer.pyx:3898-4002) from the state that is resident on
+        the device: the emergent intensity I [Nla, Nmu] of the up-going rays with direction cosines `mus` (any values in
+        (0, 1], no weights), over the wavelengths [laStart, laEnd) of the global grid (default: all this context holds).
+        The line profiles of the new directions are evaluated inside the kernel (v = v_rest + mu v_z); `vz` [Nspace]
+        defaults to vlosMu[0] / muz[0] of the resident atmosphere.  Nothing of the context changes, and nothing but the
+        request crosses to the device: upload what the host changed first.  A CALLABLE lower boundary needs `lowerBc`
+        [Nla, Nmu].  depthData: returns a RaysResult whose chi, eta and Idepth [Nla, Nmu, Nspace] are the run of each ray
+        with depth (DepthData of the to-observer direction).  squeeze: a scalar `mus` drops the Nmu axis."""
+        r, out, keep = self._rays_request(mus, laStart, laEnd, vz, lowerBc, depthData)
+        _check(self.lib, self.lib.lwhip_compute_rays(self._h, C.byref(r)), 'lwhip_compute_rays')
+        del keep
+        if squeeze and np.ndim(mus) == 0:
+            out.I = out.I[:, 0]
+            if depthData:
+                out.chi, out.eta, out.Idepth = out.chi[:, 0], out.eta[:, 0], out.Idepth[:, 0]
+        return out if depthData else out.I
 
     # -- multi-GPU split ----------------------------------------------------------------------------------
     def fs_partial(self, lambdaIterate=False):

@@ -201,6 +201,8 @@ void lwhip_batch_destroy(lwhip_batch* b)
         b->tailPinned.release();
         stokes_batch_release(b->stokes);
         b->stokes = nullptr;
+        rays_release(b->rays);
+        b->rays = nullptr;
         for (size_t i = 0; i < b->ctxs.size() && i < b->ownStreams.size(); ++i)
             b->ctxs[i]->stream = b->ownStreams[i];
     }

@@ -8,6 +8,7 @@
 //     lwhip_api2d.hip    the 2D iteration's launch sequence, the 2D primitives
 //     lwhip_batch.hip    1.5D column batches
 //     lwhip_api_prd.hip  PRD sub-iterations
+//     lwhip_rays.hip     emergent spectra along observer rays
 //
 // There is no CPU fallback: without a HIP device every compute entry point fails with LWHIP_ERR_DEVICE.
 #pragma once
@@ -315,6 +316,8 @@ int stokes_transfer(lwhip_context* c, bool up); // lwhip_upload / lwhip_download
 int check_stokes_ctx(lwhip_context* c, const char* what, bool needStokes);
 struct StokesBatch; // what a column batch keeps for its full-Stokes calls (lwhip_stokes_batch.hip)
 void stokes_batch_release(StokesBatch* s);
+struct RaysState; // observer rays (lwhip_rays.hip): the gather tables of a context, the staging of its -- or a batch's -- calls
+void rays_release(RaysState* s);
 }
 
 struct lwhip_context;
@@ -508,6 +511,7 @@ struct lwhip_context
     std::vector<double> gatherHost;
     DevBuf<int32_t> status;
     StokesState stokes;           // lwhip_set_stokes (lwhip_stokes.hip)
+    RaysState* rays = nullptr;    // made by the first lwhip_compute_rays (lwhip_rays.hip)
 
     bool profiling = false;
     int profEvery = 1, profCount = 0; // time every profEvery-th sweep launch (lwhip_profile_enable(ctx, n))
@@ -564,6 +568,7 @@ struct lwhip_context
             (void)hipStreamSynchronize(stream);
         for (PinnedBlock* b : { &stage, &gatherPinned, &prdPinned, &prdPinnedPipe, &fpPinned, &lsDbg })
             b->release(); // (before the stream they were used on goes back to its pool)
+        rays_release(rays);
         for (auto& pr : pending)
         {
             (void)hipEventDestroy(pr.first);
@@ -662,6 +667,7 @@ struct lwhip_batch
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments
     StokesBatch* stokes = nullptr;   // made by the first full-Stokes call
+    RaysState* rays = nullptr;       // made by the first lwhip_batch_compute_rays
 };
 
 namespace lwhip

@@ -1,0 +1,639 @@
+// lwhip_rays.hip -- emergent intensity along observer rays (1D plane-parallel): what LwContext.compute_rays(mus, upOnly=True)
+// (Source/LwMiddleLayer.pyx:3898-4002) computes, from the state that is resident on the device.  lwhip_compute_rays for one
+// context, lwhip_batch_compute_rays for every column of a 1.5D batch.
+//
+// The reference copies the problem, replaces its rays, makes a second context, recomputes and stores phi for the new rays
+// and runs formal_sol.  Here nothing is created: the directions are not quadrature nodes, so the stored phi does not
+// apply, and instead of storing another one the kernel evaluates phi = H(a, v) / (sqrt(pi) vBroad) where it gathers,
+// v = ((lambda - lambda0) c / lambda0 + mu v_z) / vBroad (the to-observer sign of voigt_phi_kernel).  No phi pool, no rows in
+// HBM, no second context; the context's own phi, wphi, I, J, Gamma and rates are not touched.
+//
+// rays_kernel: one launch for the whole call.  A workgroup of 256 threads owns R consecutive rays (lambda, mu) of one
+// column, the column outermost in the grid.  Its R x Ns depth points are spread over the threads -- depth across lanes: the
+// Voigt evaluations, the expensive part, are independent per depth point, and n, aDamp, vBroad and the background rows are
+// read along k -- in five passes through LDS separated by barriers:
+//   1  chi and S of every point (intensity_core's gather, SimdFullIterationTemplates.hpp:59-179, with the in-kernel phi);
+//   2  the Steffen derivative of chi at every point (linear at the two ends);
+//   3  the optical depth of every interval (Bezier3 control points), the upwind intensity of the lower boundary;
+//   4  the derivative of S in optical depth at every point;
+//   5  the five terms of every point's step: I_k = I_uw edt + alpha S_uw + beta S_k + gamma C_uw + delta C_0;
+// then one lane per ray adds them up the atmosphere in the reference's order (piecewise_bezier3_1d_impl,
+// FormalScalar.cpp:209-325: five dependent operations per depth point) and stores I(k = 0).  Every quantity is formed by
+// the operations of the serial algorithm, only not in its order in time.  R is chosen by the host so that R x Ns fills
+// whole passes of 256 threads within 40 KB of LDS (eight arrays of R x Ns doubles): 6 rays at 82 depth points.
+#include "lwhip_host.h"
+#include "lwhip_device.h"
+// H(a, v) under the same contraction setting as the stored profiles' unit: the same argument gives the same bits
+#include "lwhip_voigt_dev.h"
+
+// As in lwhip_stokes.hip: no fused multiply-adds from here on, so that the operations match the reference's one for one.
+#pragma clang fp contract(off)
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+namespace lwhip
+{
+namespace
+{
+enum { RAYS_THREADS = 256, RAYS_ARRAYS = 8, RAYS_MAX_NS = 1024, RAYS_LDS_TARGET = 40 << 10 };
+
+// one transition as the gather reads it
+struct RayTrans
+{
+    int32_t type, gi, gj, Nblue; // (gi, gj: global level rows of the n pool; Nblue: first row of the context's grid)
+    int32_t prd, row, atom, ltStart; // row: aDamp row (lines) / ratio row (continua); ltStart: own-grid index of Nblue
+    int64_t parOff, rhoOff, waveOff; // (rhoOff: of the row of Nblue)
+    double lambda0;
+};
+
+// one column: the context's resident state, the request's staged inputs and its outputs
+struct RayCol
+{
+    const double* height;
+    const double* temperature;
+    const double* wavelength;
+    const double* bgChi;
+    const double* bgEta;
+    const double* bgSca;
+    const double* J;
+    const double* n;
+    const double* ratio;
+    const double* par;
+    const double* rho;
+    const double* vlosMu;
+    const double* muzCtx;
+    const double* vBroad;
+    const double* aDamp;
+    const double* lineWave;
+    const RayTrans* tr;
+    const int32_t* laOff; // [Nla + 1] the transitions active at each of the context's rows, reference order
+    const int32_t* laTr;
+    const double* vz;      // [Ns] staged, or null: vlosMu[0] / muz[0] of the resident atmosphere
+    const double* lowerBc; // [nla, Nmu] staged (CALLABLE lower boundary)
+    double* I;             // [nla, Nmu]
+    double* depthChi;      // [nla, Nmu, Ns] each, or null
+    double* depthEta;
+    double* depthI;
+    int32_t lowerType, _pad;
+    double mu[LWHIP_RAYS_MAX_MU];
+};
+
+struct RaysArgs
+{
+    const RayCol* cols;
+    int32_t Ns, Nmu, la0, nla; // la0: first row of the context's grid
+    int32_t R, blocksPerCol;
+};
+
+__global__ void __launch_bounds__(RAYS_THREADS) rays_kernel(const RaysArgs g)
+{
+    dbg_poison_lds();
+    extern __shared__ double lds[];
+    const int Ns = g.Ns, Nmu = g.Nmu;
+    const RayCol* a = g.cols + blockIdx.x / g.blocksPerCol;
+    const int ray0 = (blockIdx.x % g.blocksPerCol) * g.R;
+    const int nRay = min(g.R, g.nla * Nmu - ray0);
+    const int nPt = nRay * Ns;
+    const size_t W = (size_t)g.R * Ns;
+    double* sChi = lds;         // chi; from pass 5 on: edt of the step into k, then I(k)
+    double* sS = lds + W;       // S
+    double* sD = lds + 2 * W;   // d chi / ds; from pass 5 on: the step's first term
+    double* sTau = lds + 3 * W; // [k] optical depth of the interval k + 1 -> k; [Ns - 1]: of the last step's linear rule
+    double* sDS = lds + 4 * W;  // [k] dS / dtau at k (k >= 1); [0]: the upwind intensity at the lower boundary
+    double* sT2 = lds + 5 * W;
+    double* sT3 = lds + 6 * W;
+    double* sT4 = lds + 7 * W;
+    const double* h = a->height;
+
+    // ---- 1: chi and S ---------------------------------------------------------------------------------------------------
+    {
+        const double sqrtPi = 1.772453850905516027298167483341145182798;
+        const double* temperature = a->temperature;
+        const double* nPool = a->n;
+        const double* par = a->par;
+        const double* vBroad = a->vBroad;
+        const double* aDamp = a->aDamp;
+        const double* lineWave = a->lineWave;
+        const RayTrans* tr = a->tr;
+        const int32_t* laOff = a->laOff;
+        const int32_t* laTr = a->laTr;
+        const double* vzIn = a->vz;
+        for (int idx = threadIdx.x; idx < nPt; idx += RAYS_THREADS)
+        {
+            const int r = idx / Ns, k = idx - r * Ns;
+            const int ray = ray0 + r;
+            const int l = ray / Nmu, m = ray - l * Nmu;
+            const int la = g.la0 + l;
+            const double vz = vzIn ? vzIn[k] : a->vlosMu[k] / a->muzCtx[0];
+            const double vlos = a->mu[m] * vz;
+            const double T = temperature[k];
+            const size_t lk = (size_t)la * Ns + k;
+            double chi = a->bgChi[lk], eta = a->bgEta[lk];
+            for (int q = laOff[la]; q < laOff[la + 1]; ++q)
+            {
+                const RayTrans t = tr[laTr[q]];
+                const int l0 = la - t.Nblue;
+                const double* p = par + t.parOff + 4 * (size_t)l0;
+                double Vij, Vji, Uji;
+                if (t.type == LWHIP_LINE)
+                {
+                    // Transition::uv (LwTransition.hpp:98-127) with gij of Atom::setup_wavelength (LwAtom.hpp:99-123); phi of
+                    // compute_phi_la (FormalScalar.cpp:28-51) for this direction
+                    const double vb = vBroad[(size_t)t.atom * Ns + k];
+                    const double vBase = (lineWave[t.waveOff + t.ltStart + l0] - t.lambda0) * CLight / t.lambda0;
+                    const double vk = (vBase + vlos) / vb;
+                    const double phi = d_voigt_H(aDamp[(size_t)t.row * Ns + k], vk) / (sqrtPi * vb);
+                    Vij = p[0] * phi;
+                    double gij = p[2];
+                    if (t.prd)
+                        gij *= a->rho[t.rhoOff + (size_t)l0 * Ns + k];
+                    Vji = gij * Vij;
+                    Uji = p[3] * Vji;
+                }
+                else
+                {
+                    const double hc_kl = HC_K / a->wavelength[la];
+                    const double gij = a->ratio[(size_t)t.row * Ns + k] * exp(-hc_kl / T);
+                    Vij = p[0];
+                    Vji = gij * Vij;
+                    Uji = p[2] * Vji;
+                }
+                const double ni = nPool[(size_t)t.gi * Ns + k], nj = nPool[(size_t)t.gj * Ns + k];
+                chi += ni * Vij - nj * Vji;
+                eta += nj * Uji;
+            }
+            sChi[idx] = chi;
+            sS[idx] = (eta + a->bgSca[lk] * a->J[lk]) / chi;
+            if (a->depthChi)
+            {
+                // (rays are consecutive in the output: [nla, Nmu, Ns])
+                a->depthChi[(size_t)ray0 * Ns + idx] = chi;
+                a->depthEta[(size_t)ray0 * Ns + idx] = eta;
+            }
+        }
+    }
+    __syncthreads();
+    // The ray goes up: from k = Ns - 1 (upwind end) to k = 0; the upwind neighbour of k is k + 1.
+    // ---- 2: d chi / ds (cent_deriv inside, the one-sided difference at the two ends) -------------------------------------
+    for (int idx = threadIdx.x; idx < nPt; idx += RAYS_THREADS)
+    {
+        const int r = idx / Ns, k = idx - r * Ns;
+        const double zmu = 1.0 / a->mu[(ray0 + r) % Nmu];
+        const double* c = sChi + r * Ns;
+        double D;
+        if (k == Ns - 1)
+            D = (c[Ns - 2] - c[Ns - 1]) / (fabs(h[Ns - 2] - h[Ns - 1]) * zmu);
+        else if (k == 0)
+            D = (c[0] - c[1]) / (fabs(h[0] - h[1]) * zmu);
+        else
+            D = d_cent_deriv(fabs(h[k] - h[k + 1]) * zmu, fabs(h[k - 1] - h[k]) * zmu, c[k + 1], c[k], c[k - 1]);
+        sD[idx] = D;
+    }
+    __syncthreads();
+    // ---- 3: optical depths; the upwind intensity ---------------------------------------------------------------------------
+    for (int idx = threadIdx.x; idx < nPt; idx += RAYS_THREADS)
+    {
+        const int r = idx / Ns, k = idx - r * Ns;
+        const int ray = ray0 + r;
+        const int l = ray / Nmu, m = ray - l * Nmu;
+        const double zmu = 1.0 / a->mu[m];
+        const double* c = sChi + r * Ns;
+        const double* D = sD + r * Ns;
+        if (k < Ns - 1)
+        {
+            const double ds = fabs(h[k] - h[k + 1]) * zmu;
+            const double Cuw = c[k + 1] + (ds / 3.0) * D[k + 1];
+            const double C0 = c[k] - (ds / 3.0) * D[k];
+            sTau[idx] = ds * (c[k] + c[k + 1] + Cuw + C0) * 0.25;
+        }
+        else
+        {
+            // the last step (into k = 0) is linear; the boundary (FormalScalar.cpp:551-597)
+            sTau[idx] = 0.5 * zmu * (c[0] + c[1]) * fabs(h[0] - h[1]);
+            double Iupw = 0.0;
+            if (a->lowerType == LWHIP_BC_THERMALISED)
+            {
+                const double dtau_uw = 0.5 * zmu * (c[Ns - 1] + c[Ns - 2]) * fabs(h[Ns - 1] - h[Ns - 2]);
+                const double wav = a->wavelength[g.la0 + l];
+                const double B0 = d_planck(a->temperature[Ns - 2], wav), B1 = d_planck(a->temperature[Ns - 1], wav);
+                Iupw = B1 - (B0 - B1) / dtau_uw;
+            }
+            else if (a->lowerType == LWHIP_BC_CALLABLE)
+                Iupw = a->lowerBc[ray];
+            sDS[r * Ns] = Iupw;
+        }
+    }
+    __syncthreads();
+    // ---- 4: dS / dtau ------------------------------------------------------------------------------------------------------
+    for (int idx = threadIdx.x; idx < nPt; idx += RAYS_THREADS)
+    {
+        const int r = idx / Ns, k = idx - r * Ns;
+        const double* S = sS + r * Ns;
+        const double* tau = sTau + r * Ns;
+        if (k == Ns - 1)
+            sDS[idx] = (S[Ns - 2] - S[Ns - 1]) / tau[Ns - 2];
+        else if (k > 0)
+            sDS[idx] = d_cent_deriv(tau[k], tau[k - 1], S[k + 1], S[k], S[k - 1]);
+    }
+    __syncthreads();
+    // ---- 5: the terms of every step (nothing below reads chi or its derivative: their arrays take the first two) ------------
+    for (int idx = threadIdx.x; idx < nPt; idx += RAYS_THREADS)
+    {
+        const int r = idx / Ns, k = idx - r * Ns;
+        const double* S = sS + r * Ns;
+        const double* tau = sTau + r * Ns;
+        const double* DS = sDS + r * Ns;
+        if (k == Ns - 1)
+            continue;
+        double E, t1, t2, t3 = 0.0, t4 = 0.0;
+        if (k > 0)
+        {
+            const double dt = tau[k];
+            double alpha, beta, gamma, delta, edt;
+            d_bezier3_coeffs(dt, alpha, beta, gamma, delta, edt);
+            const double Cuw = S[k + 1] + (dt / 3.0) * DS[k + 1];
+            const double C0 = S[k] - (dt / 3.0) * DS[k];
+            E = edt;
+            t1 = alpha * S[k + 1];
+            t2 = beta * S[k];
+            t3 = gamma * Cuw;
+            t4 = delta * C0;
+        }
+        else
+        {
+            const double dt = tau[Ns - 1];
+            const double dS_uw = (S[0] - S[1]) / dt;
+            double w0, w1;
+            d_w2(dt, w0, w1);
+            E = 1.0 - w0;
+            t1 = w0 * S[0];
+            t2 = -(w1 * dS_uw);
+        }
+        sChi[idx] = E;
+        sD[idx] = t1;
+        sT2[idx] = t2;
+        sT3[idx] = t3;
+        sT4[idx] = t4;
+    }
+    __syncthreads();
+    // ---- the recurrence: one lane per ray ------------------------------------------------------------------------------------
+    if ((int)threadIdx.x < nRay)
+    {
+        const int o = threadIdx.x * Ns;
+        double I = sDS[o];
+        sChi[o + Ns - 1] = I;
+        for (int k = Ns - 2; k >= 0; --k)
+        {
+            I = I * sChi[o + k] + sD[o + k] + sT2[o + k] + sT3[o + k] + sT4[o + k];
+            sChi[o + k] = I;
+        }
+        a->I[ray0 + threadIdx.x] = I;
+    }
+    if (a->depthI)
+    {
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < nPt; idx += RAYS_THREADS)
+            a->depthI[(size_t)ray0 * Ns + idx] = sChi[idx];
+    }
+}
+
+// rays per workgroup: the R whose R x Ns points waste the fewest lanes of the passes, the largest such R, within the LDS target
+int rays_per_group(int Ns)
+{
+    int best = 1;
+    double bestUse = 0.0;
+    for (int R = 1; R <= 64 && (size_t)R * Ns * RAYS_ARRAYS * sizeof(double) <= (size_t)RAYS_LDS_TARGET; ++R)
+    {
+        const int pts = R * Ns;
+        const double use = (double)pts / (double)(((pts + RAYS_THREADS - 1) / RAYS_THREADS) * RAYS_THREADS);
+        if (use >= bestUse)
+        {
+            bestUse = use;
+            best = R;
+        }
+    }
+    return best;
+}
+} // namespace
+
+// The structure tables of the gather and the staging of a call.  The tables depend on the structure alone: a context made with
+// lwhip_create_like uses its table owner's.
+struct RaysState
+{
+    std::mutex lock;
+    bool built = false;
+    DevBuf<RayTrans> tr;
+    DevBuf<int32_t> laOff, laTr;
+    DevBuf<unsigned char> in, out; // [RayCol per column | staged vz | staged lowerBc], [per column: I | chi | eta | I(k)]
+    PinnedBlock inPinned, outPinned;
+};
+
+void rays_release(RaysState* s)
+{
+    if (s)
+    {
+        s->inPinned.release();
+        s->outPinned.release();
+    }
+    delete s;
+}
+
+namespace
+{
+std::mutex g_raysCreate;
+
+RaysState* rays_state(RaysState*& slot)
+{
+    std::lock_guard<std::mutex> g(g_raysCreate);
+    if (!slot)
+        slot = new RaysState();
+    return slot;
+}
+
+hipError_t rays_init_table(int device)
+{
+    static std::atomic<bool> done[64];
+    if (device >= 0 && device < 64 && done[device].load())
+        return hipSuccess;
+    const hipError_t e = voigt_fill_table();
+    if (e == hipSuccess && device >= 0 && device < 64)
+        done[device].store(true);
+    return e;
+}
+
+// the gather tables of `o` (a table owner), made on first use
+int rays_tables(lwhip_context* o, RaysState*& out)
+{
+    RaysState* s = rays_state(o->rays);
+    out = s;
+    std::lock_guard<std::mutex> g(s->lock);
+    if (s->built)
+        return LWHIP_OK;
+    const int Ns = o->Ns;
+    std::vector<RayTrans> trs(std::max<size_t>(o->trans.size(), 1));
+    for (size_t i = 0; i < o->trans.size(); ++i)
+    {
+        const HostTrans& h = o->trans[i];
+        RayTrans& t = trs[i];
+        t = RayTrans{};
+        t.type = h.t.type;
+        t.gi = o->levelOff[h.atom] + h.t.i;
+        t.gj = o->levelOff[h.atom] + h.t.j;
+        t.Nblue = h.NblueLoc;
+        t.prd = (h.t.type == LWHIP_LINE && h.t.prd && h.rhoOff >= 0) ? 1 : 0;
+        t.row = h.row;
+        t.atom = h.atom;
+        t.ltStart = h.ltStart;
+        t.parOff = h.parOff;
+        t.rhoOff = h.rhoOff >= 0 ? h.rhoOff + (int64_t)(h.ltStart - h.rhoLt0) * Ns : 0;
+        t.waveOff = h.waveOff >= 0 ? h.waveOff : 0;
+        t.lambda0 = h.t.lambda0;
+    }
+    std::vector<int32_t> laOff(o->Nla + 1, 0), laTr;
+    for (int la = 0; la < o->Nla; ++la)
+    {
+        laOff[la] = (int32_t)laTr.size();
+        for (size_t i = 0; i < o->trans.size(); ++i)
+            if (la >= o->trans[i].NblueLoc && la < o->trans[i].NredLoc)
+                laTr.push_back((int32_t)i);
+    }
+    laOff[o->Nla] = (int32_t)laTr.size();
+    if (laTr.empty())
+        laTr.push_back(0);
+    HIP_TRY(hipSetDevice(o->device));
+    // (outside any arena and any gathered upload: the tables outlive lwhip_create)
+    HIP_TRY(s->tr.upload(o->mem, trs));
+    HIP_TRY(s->laOff.upload(o->mem, laOff));
+    HIP_TRY(s->laTr.upload(o->mem, laTr));
+    HIP_TRY(hipStreamSynchronize(o->stream)); // (borrowers may run on other streams)
+    s->built = true;
+    return LWHIP_OK;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Every refusal of a request, before anything is queued.  la0 / la1: the rows of the global grid.
+int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, int& la0, int& la1)
+{
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, what + ": null context");
+    if (!r)
+        return fail(LWHIP_ERR_INVALID, what + ": null request");
+    if (c->is2d)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": observer rays are 1D plane-parallel only");
+    if (c->hprd)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": not with hybrid PRD tables (rho there is tied to the quadrature rays)");
+    if (c->prob.formalSolver != LWHIP_FS_BEZIER3_1D)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": piecewise_bezier3_1d contexts only");
+    if (c->Ns < 3)
+        return fail(LWHIP_ERR_INVALID, what + ": needs at least 3 depth points");
+    if (c->Ns > RAYS_MAX_NS) // (lwhip_create admits no deeper 1D column: a guard for the LDS rows, should that change)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": more than " + std::to_string((int)RAYS_MAX_NS) + " depth points");
+    if (r->Nmu < 1 || !r->muz || !r->I)
+        return fail(LWHIP_ERR_INVALID, what + ": Nmu >= 1, muz and I are required");
+    if (r->Nmu > LWHIP_RAYS_MAX_MU)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": Nmu above LWHIP_RAYS_MAX_MU (" + std::to_string(LWHIP_RAYS_MAX_MU)
+                                               + " directions per call)");
+    for (int m = 0; m < r->Nmu; ++m)
+        if (!(r->muz[m] > 0.0 && r->muz[m] <= 1.0))
+            return fail(LWHIP_ERR_INVALID, what + ": direction cosine " + std::to_string(m) + " is outside (0, 1]");
+    la0 = (r->laStart == 0 && r->laEnd == 0) ? c->laStart : r->laStart;
+    la1 = (r->laEnd == 0) ? c->laEnd : r->laEnd;
+    if (la0 < c->laStart || la1 > c->laEnd || la1 <= la0)
+        return fail(LWHIP_ERR_INVALID, what + ": wavelength range [" + std::to_string(la0) + ", " + std::to_string(la1)
+                                           + ") is not inside the context's rows [" + std::to_string(c->laStart) + ", "
+                                           + std::to_string(c->laEnd) + ")");
+    if (c->prob.zLowerBc.type == LWHIP_BC_CALLABLE && !r->lowerBc)
+        return fail(LWHIP_ERR_INVALID, what + ": a CALLABLE lower boundary has no data for new directions (pass lowerBc [Nla, Nmu])");
+    const int nDepth = (r->depthChi ? 1 : 0) + (r->depthEta ? 1 : 0) + (r->depthI ? 1 : 0);
+    if (nDepth != 0 && nDepth != 3)
+        return fail(LWHIP_ERR_INVALID, what + ": depthChi, depthEta and depthI go together");
+    if (!r->vz && !c->prob.vlosMu)
+        return fail(LWHIP_ERR_INVALID, what + ": needs vz, or vlosMu in the descriptor");
+    for (const HostTrans& h : c->trans)
+        if (h.t.type == LWHIP_LINE && !h.t.aDamp)
+            return fail(LWHIP_ERR_INVALID, what + ": needs aDamp for every line (the profiles are evaluated in the kernel)");
+    return LWHIP_OK;
+}
+
+// The call: cols[i] with request reqs[i], everything on cols[0]'s stream, staged through `st`.
+int rays_run(lwhip_context* const* cols, int n, const lwhip_rays* reqs, RaysState*& slot, const char* whatC)
+{
+    const std::string what(whatC);
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, what + ": no gfx950 device");
+    if (n <= 0 || !cols || !reqs)
+        return fail(LWHIP_ERR_INVALID, what + ": null " + (n > 1 ? "batch" : "context") + " or request");
+    int la0 = 0, la1 = 0;
+    for (int i = 0; i < n; ++i)
+    {
+        int a0 = 0, a1 = 0;
+        const int chk = rays_check(cols[i], reqs + i, what, a0, a1);
+        if (chk != LWHIP_OK)
+            return n > 1 ? fail(chk, std::string(lwhip_last_error()) + " (column " + std::to_string(i) + ")") : chk;
+        if (i == 0)
+        {
+            la0 = a0;
+            la1 = a1;
+        }
+        const lwhip_context* c = cols[i];
+        if (c->Ns != cols[0]->Ns || c->device != cols[0]->device || reqs[i].Nmu != reqs[0].Nmu || a0 != la0 || a1 != la1
+            || (reqs[i].depthI != nullptr) != (reqs[0].depthI != nullptr))
+            return fail(LWHIP_ERR_INVALID, what + ": column " + std::to_string(i)
+                                               + " differs from column 0 (depth points, Nmu, wavelength range and depth outputs "
+                                                 "are the same for every column)");
+    }
+    lwhip_context* c0 = cols[0];
+    const int Ns = c0->Ns, Nmu = reqs[0].Nmu, nla = la1 - la0;
+    const bool depth = reqs[0].depthI != nullptr;
+    HIP_TRY(hipSetDevice(c0->device));
+    HIP_TRY(rays_init_table(c0->device));
+    std::vector<RaysState*> tabs(n);
+    for (int i = 0; i < n; ++i)
+    {
+        lwhip_context* o = cols[i]->tablesFrom ? cols[i]->tablesFrom : cols[i];
+        const int stp = rays_tables(o, tabs[i]);
+        if (stp != LWHIP_OK)
+            return stp;
+    }
+    RaysState& st = *rays_state(slot);
+    // ---- the staged request: [RayCol x n | vz | lowerBc], one copy up ------------------------------------------------------
+    const size_t nRayCol = (size_t)nla * Nmu;
+    const size_t colsBytes = align256((size_t)n * sizeof(RayCol));
+    size_t inBytes = colsBytes;
+    std::vector<size_t> vzOff(n, 0), bcOff(n, 0);
+    for (int i = 0; i < n; ++i)
+    {
+        if (reqs[i].vz)
+        {
+            vzOff[i] = inBytes;
+            inBytes += align256((size_t)Ns * sizeof(double));
+        }
+        if (cols[i]->prob.zLowerBc.type == LWHIP_BC_CALLABLE)
+        {
+            bcOff[i] = inBytes;
+            inBytes += align256(nRayCol * sizeof(double));
+        }
+    }
+    const size_t perColOut = (nRayCol + (depth ? 3 * nRayCol * Ns : 0)) * sizeof(double);
+    const size_t outBytes = (size_t)n * perColOut;
+    if (st.in.n < inBytes || st.out.n < outBytes)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        if (st.in.n < inBytes)
+            HIP_TRY(st.in.alloc(c0->mem, inBytes, false));
+        if (st.out.n < outBytes)
+            HIP_TRY(st.out.alloc(c0->mem, outBytes, false));
+    }
+    HIP_TRY(st.inPinned.reserve(c0->device, inBytes, c0->stream));
+    HIP_TRY(st.outPinned.reserve(c0->device, outBytes, c0->stream));
+    unsigned char* hin = st.inPinned.as<unsigned char>();
+    RayCol* hc = (RayCol*)hin;
+    for (int i = 0; i < n; ++i)
+    {
+        lwhip_context* c = cols[i];
+        const lwhip_rays& r = reqs[i];
+        RayCol a{};
+        a.height = c->height.p;
+        a.temperature = c->temperature.p;
+        a.wavelength = c->wavelength.p;
+        a.bgChi = c->bgChi.p;
+        a.bgEta = c->bgEta.p;
+        a.bgSca = c->bgSca.p;
+        a.J = c->J.p;
+        a.n = c->n.p;
+        a.ratio = c->ratio.p;
+        a.par = c->par.p;
+        a.rho = c->rho.p;
+        a.vlosMu = c->vlosMu.p;
+        a.muzCtx = c->muz.p;
+        a.vBroad = c->vBroad.p;
+        a.aDamp = c->aDamp.p;
+        a.lineWave = c->lineWave.p;
+        a.tr = tabs[i]->tr.p;
+        a.laOff = tabs[i]->laOff.p;
+        a.laTr = tabs[i]->laTr.p;
+        if (r.vz)
+        {
+            std::memcpy(hin + vzOff[i], r.vz, (size_t)Ns * sizeof(double));
+            a.vz = (const double*)(st.in.p + vzOff[i]);
+        }
+        a.lowerType = c->prob.zLowerBc.type;
+        if (a.lowerType == LWHIP_BC_CALLABLE)
+        {
+            std::memcpy(hin + bcOff[i], r.lowerBc, nRayCol * sizeof(double));
+            a.lowerBc = (const double*)(st.in.p + bcOff[i]);
+        }
+        double* o = (double*)(st.out.p + (size_t)i * perColOut);
+        a.I = o;
+        if (depth)
+        {
+            a.depthChi = o + nRayCol;
+            a.depthEta = o + nRayCol + nRayCol * Ns;
+            a.depthI = o + nRayCol + 2 * nRayCol * Ns;
+        }
+        for (int m = 0; m < Nmu; ++m)
+            a.mu[m] = r.muz[m];
+        hc[i] = a;
+    }
+    HIP_TRY(c0->mem.h2d(st.in.p, hin, inBytes));
+    // ---- one launch ------------------------------------------------------------------------------------------------------------
+    RaysArgs g{};
+    g.cols = (const RayCol*)st.in.p;
+    g.Ns = Ns;
+    g.Nmu = Nmu;
+    g.la0 = la0 - c0->laStart;
+    g.nla = nla;
+    g.R = rays_per_group(Ns);
+    g.blocksPerCol = (int)((nRayCol + g.R - 1) / g.R);
+    const size_t ldsBytes = (size_t)RAYS_ARRAYS * g.R * Ns * sizeof(double);
+    const size_t nBlk = (size_t)n * g.blocksPerCol;
+    if (nBlk > 0x7fffffffu)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": too many rays for one launch");
+    LWHIP_LAUNCH(rays_kernel, dim3((unsigned)nBlk), dim3(RAYS_THREADS), ldsBytes, c0->stream, g);
+    HIP_TRY(hipGetLastError());
+    // ---- one copy back, one wait -------------------------------------------------------------------------------------------------
+    unsigned char* hout = st.outPinned.as<unsigned char>();
+    HIP_TRY(hipMemcpyAsync(hout, st.out.p, outBytes, hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    for (int i = 0; i < n; ++i)
+    {
+        const double* o = (const double*)(hout + (size_t)i * perColOut);
+        std::memcpy(reqs[i].I, o, nRayCol * sizeof(double));
+        if (depth)
+        {
+            std::memcpy(reqs[i].depthChi, o + nRayCol, nRayCol * Ns * sizeof(double));
+            std::memcpy(reqs[i].depthEta, o + nRayCol + nRayCol * Ns, nRayCol * Ns * sizeof(double));
+            std::memcpy(reqs[i].depthI, o + nRayCol + 2 * nRayCol * Ns, nRayCol * Ns * sizeof(double));
+        }
+    }
+    return LWHIP_OK;
+}
+} // namespace
+} // namespace lwhip
+
+extern "C"
+{
+int lwhip_compute_rays(lwhip_context* c, const lwhip_rays* rays)
+{
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, "lwhip_compute_rays: no gfx950 device");
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, "lwhip_compute_rays: null context");
+    lwhip_context* cols[1] = { c };
+    return rays_run(cols, 1, rays, c->rays, "lwhip_compute_rays");
+}
+
+int lwhip_batch_compute_rays(lwhip_batch* b, const lwhip_rays* perColumn)
+{
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, "lwhip_batch_compute_rays: no gfx950 device");
+    if (!b || b->ctxs.empty())
+        return fail(LWHIP_ERR_INVALID, "lwhip_batch_compute_rays: null batch");
+    return rays_run(b->ctxs.data(), (int)b->ctxs.size(), perColumn, b->rays, "lwhip_batch_compute_rays");
+}
+}

@@ -39,164 +39,12 @@
 
 #include <cmath>
 
+// d_voigt_H and its table (shared with the observer rays, lwhip_rays.hip); this unit owns them
+#define LWHIP_VOIGT_LINKAGE
+#include "lwhip_voigt_dev.h"
+
 namespace lwhip
 {
-__constant__ double c_expa2n2[64];
-
-__device__ __forceinline__ double v_sinc(double x, double sinx)
-{
-    return fabs(x) < 1e-4 ? 1 - (0.1666666666666666666667) * x * x : sinx / x;
-}
-
-__device__ __forceinline__ double v_sinh_taylor(double x)
-{
-    return x * (1 + (x * x) * (0.1666666666666666666667 + 0.00833333333333333333333 * (x * x)));
-}
-
-__device__ double d_voigt_H(double av, double v)
-{
-    const double a = 0.518321480430085929872;
-    const double c = 0.329973702884629072537;
-    const double a2 = 0.268657157075235951582;
-    const double relerr = 2.2204460492503131e-16;
-    const double x = fabs(v);
-    const double y = av, ya = fabs(av);
-    if (v == 0.0)
-        return erfcx(y);
-    if (y == 0.0)
-        return exp(-x * x);
-
-    double ret = 0.0;
-    double sum1 = 0, sum2 = 0, sum3 = 0, sum5 = 0;
-    if (ya > 7 || (x > 6 && (ya > 0.1 || (x > 8 && ya > 1e-10) || x > 28)))
-    {
-        const double ispi = 0.56418958354775628694807945156;
-        const double xs = v;
-        if (x + ya > 4000)
-        {
-            if (x + ya > 1e7)
-            {
-                if (x > ya)
-                {
-                    const double yax = ya / xs;
-                    const double denom = ispi / (xs + yax * ya);
-                    return denom * yax;
-                }
-                const double xya = xs / ya;
-                return ispi / (xya * xs + ya);
-            }
-            const double dr = xs * xs - ya * ya - 0.5, di = 2 * xs * ya;
-            const double denom = ispi / (dr * dr + di * di);
-            return denom * (xs * di - ya * dr);
-        }
-        const double c0 = 3.9, c1 = 11.398, c2 = 0.08254, c3 = 0.1421, c4 = 0.2023;
-        double nu = floor(c0 + c1 / (c2 * x + c3 * ya + c4));
-        double wr = xs, wi = ya;
-        for (nu = 0.5 * (nu - 1); nu > 0.4; nu -= 0.5)
-        {
-            const double denom = nu / (wr * wr + wi * wi);
-            wr = xs - wr * denom;
-            wi = ya + wi * denom;
-        }
-        const double denom = ispi / (wr * wr + wi * wi);
-        return denom * wi;
-    }
-    else if (x < 10)
-    {
-        double prod2ax = 1, prodm2ax = 1;
-        double expx2;
-        if (x < 5e-4)
-        {
-            const double x2 = x * x;
-            expx2 = 1 - x2 * (1 - 0.5 * x2);
-            const double ax2 = 1.036642960860171859744 * x;
-            const double exp2ax = 1 + ax2 * (1 + ax2 * (0.5 + 0.166666666666666666667 * ax2));
-            const double expm2ax = 1 - ax2 * (1 - ax2 * (0.5 - 0.166666666666666666667 * ax2));
-            for (int n = 1; n < 60; ++n)
-            {
-                const double coef = c_expa2n2[n - 1] * expx2 / (a2 * (n * n) + y * y);
-                prod2ax *= exp2ax;
-                prodm2ax *= expm2ax;
-                sum1 += coef;
-                sum2 += coef * prodm2ax;
-                sum3 += coef * prod2ax;
-                sum5 += coef * (2 * a) * n * v_sinh_taylor((2 * a) * n * x);
-                if (coef * prod2ax < relerr * sum3)
-                    break;
-            }
-        }
-        else
-        {
-            expx2 = exp(-x * x);
-            const double exp2ax = exp((2 * a) * x), expm2ax = 1 / exp2ax;
-            for (int n = 1; n < 60; ++n)
-            {
-                const double coef = c_expa2n2[n - 1] * expx2 / (a2 * (n * n) + y * y);
-                prod2ax *= exp2ax;
-                prodm2ax *= expm2ax;
-                sum1 += coef;
-                sum2 += coef * prodm2ax;
-                sum3 += coef * prod2ax;
-                sum5 += (coef * prod2ax) * (a * n);
-                if ((coef * prod2ax) * (a * n) < relerr * sum5)
-                    break;
-            }
-        }
-        const double expx2erfcxy = expx2 * erfcx(y);
-        if (y > 5)
-        {
-            const double sinxy = sin(x * y);
-            ret = (expx2erfcxy - c * y * sum1) * cos(2 * x * y) + (c * x * expx2) * sinxy * v_sinc(x * y, sinxy);
-        }
-        else
-        {
-            const double xs = v;
-            const double sinxy = sin(xs * y);
-            const double cos2xy = cos(2 * xs * y);
-            const double coef1 = expx2erfcxy - c * y * sum1;
-            const double coef2 = c * xs * expx2;
-            ret = coef1 * cos2xy + coef2 * sinxy * v_sinc(xs * y, sinxy);
-        }
-    }
-    else
-    {
-        ret = exp(-x * x);
-        const double n0 = floor(x / a + 0.5);
-        const double dx = a * n0 - x;
-        sum3 = exp(-dx * dx) / (a2 * (n0 * n0) + y * y);
-        sum5 = a * n0 * sum3;
-        const double exp1 = exp(4 * a * dx);
-        double exp1dn = 1;
-        int dn;
-        bool done = false;
-        for (dn = 1; n0 - dn > 0; ++dn)
-        {
-            const double np = n0 + dn, nm = n0 - dn;
-            double tp = exp(-(a * dn + dx) * (a * dn + dx));
-            double tm = tp * (exp1dn *= exp1);
-            tp /= (a2 * (np * np) + y * y);
-            tm /= (a2 * (nm * nm) + y * y);
-            sum3 += tp + tm;
-            sum5 += a * (np * tp + nm * tm);
-            if (a * (np * tp + nm * tm) < relerr * sum5)
-            {
-                done = true;
-                break;
-            }
-        }
-        while (!done)
-        {
-            const double np = n0 + dn++;
-            const double tp = exp(-(a * dn + dx) * (a * dn + dx)) / (a2 * (np * np) + y * y);
-            sum3 += tp;
-            sum5 += a * np * tp;
-            if (a * np * tp < relerr * sum5)
-                break;
-        }
-    }
-    return ret + (0.5 * c) * y * (sum2 + sum3);
-}
-
 // The complex w(v + i av) = H + i F of voigt_HF (Source/LwMisc.hpp:21-27), the same restatement of Faddeeva.cc's w(z) as
 // d_voigt_H above, branch for branch, keeping the imaginary part as well (d_voigt_H is left as it is: the unpolarised
 // profiles keep their bits).  The damping parameter is never negative here, so the y < 0 continuations of Faddeeva.cc are

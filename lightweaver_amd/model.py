@@ -410,3 +410,52 @@ class Problem:
             else:
                 setattr(new, k, copy.deepcopy(v, memo))
         return new
+
+
+def check_mus(mus):
+    """`mus` of compute_rays / observer_problem as a float64 vector of direction cosines in (0, 1]."""
+    mus = np.ascontiguousarray(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
+    if mus.size == 0 or not np.all((mus > 0.0) & (mus <= 1.0)):
+        raise ValueError('mus must be direction cosines in (0, 1]')
+    return mus
+
+
+def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None) -> Problem:
+    """The problem LwContext.compute_rays (Source/LwMiddleLayer.pyx:3898-4002) hands to its second context: a deep copy
+    of `prob` (populations, J, background, rhoPrd: equal, not shared) whose rays are `mus`, with wmu = 0 as
+    Atmosphere.rays leaves it unless `wmu` is given, and vlosMu = mu (x) v_z.  `vz` [Nspace] defaults to
+    vlosMu[0] / muz[0] of `prob` (the 1D convention vlosMu = muz (x) v_z).  Every line's phi is dropped for a zero array of
+    the new ray count (make it with compute_profiles); full-Stokes data is not carried over.  A CALLABLE lower boundary
+    has no data for a new direction: pass `lowerBc` [Nlambda, Nmu] (it feeds the up-going rays); a CALLABLE upper
+    boundary becomes ZERO, which an up-going ray never reads.  What Context.compute_rays computes on the device without any
+    of this is formal_sol(upOnly=True) of this problem."""
+    if prob.grid2d is not None:
+        raise ValueError('observer_problem: 1D plane-parallel problems only')
+    mus = check_mus(mus)
+    Nr, Ns = mus.shape[0], prob.Nspace
+    vz = (prob.vlosMu[0] / prob.muz[0]) if vz is None else _f64(vz, (Ns,))
+    new = prob.copy()
+    new.muz = mus.copy()
+    new.Nrays = Nr
+    new.wmu = np.zeros(Nr) if wmu is None else _f64(wmu, (Nr,)).copy()
+    new.vlosMu = np.ascontiguousarray(mus[:, None] * vz[None, :])
+    new.I = np.zeros((prob.Nlambda, Nr))
+    if new.storeDepthData:
+        dshape = (prob.Nlambda, Nr, 2, Ns)
+        new.depthChi, new.depthEta, new.depthI = np.zeros(dshape), np.zeros(dshape), np.zeros(dshape)
+    for a in new.atoms:
+        for t in a.trans:
+            if t.type == abi.LINE:
+                t.phi = np.zeros((t.Nlambda, Nr, 2, Ns))   # (the stored one carries the old ray count)
+    if new.zLowerBc.type == abi.BC_CALLABLE:
+        if lowerBc is None:
+            raise ValueError('observer_problem: a CALLABLE lower boundary has no data for new directions: pass lowerBc '
+                             '[Nlambda, Nmu]')
+        idxs = np.full((Nr, 2), -1, dtype=np.int32)
+        idxs[:, 1] = np.arange(Nr)
+        new.zLowerBc = Boundary(abi.BC_CALLABLE, idxs=idxs, bcData=_f64(lowerBc, (prob.Nlambda, Nr)).copy())
+    if new.zUpperBc.type == abi.BC_CALLABLE:
+        new.zUpperBc = Boundary(abi.BC_ZERO)
+    new.stokes = None
+    new.Quv = None
+    return new
