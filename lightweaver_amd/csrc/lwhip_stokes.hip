@@ -329,9 +329,13 @@ int lwhip_full_stokes_fs(lwhip_context* c, int updateJ, int upOnly, lwhip_iter_r
     StokesState& s = c->stokes;
     const int Ns = c->Ns, Nr = c->Nrays, Nla = c->Nla;
     const int nDir = upOnly ? 1 : 2;
-    // wavelength chunks: the rows of a chunk's rays stay within 256 MB
+    // wavelength chunks: the rows of a chunk's rays stay within 256 MB; LWHIP_STOKES_CHUNK_LA (LWHIP_DEBUG) sets the
+    // wavelengths of a chunk instead (the results are the same bits for any chunking, tested)
     const size_t perLa = (size_t)Nr * nDir * (ST_ROWS + (updateJ ? 2 : 0)) * Ns * sizeof(double);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)Nla, ((size_t)256 << 20) / perLa));
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)Nla, ((size_t)256 << 20) / perLa));
+    const int dbgChunk = dbg_env_int("LWHIP_STOKES_CHUNK_LA", 0);
+    if (dbgChunk > 0)
+        chunk = std::max(1, std::min(Nla, dbgChunk));
     const size_t raysChunk = (size_t)chunk * Nr * nDir;
     if (s.scratch.n < raysChunk * ST_ROWS * Ns)
         HIP_TRY(s.scratch.alloc(c->mem, raysChunk * ST_ROWS * Ns));

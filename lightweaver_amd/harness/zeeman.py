@@ -109,13 +109,16 @@ def falc_h_ca_stokes(Nrays=3, lineScale=0.2, B=None, gammaB=None, chiB=None, dis
     return prob
 
 
-def stokes_columns(ncol, Nrays=5, lineScale=3.1, seed0=1234):
+def stokes_columns(ncol, Nrays=5, lineScale=3.1, seed0=1234, Nspace=None):
     """`ncol` columns of a 1.5D batch for polarised synthesis: seeded perturbed FAL-C (models.perturbed, seeds seed0,
     seed0 + 1, ...), H + Ca II with the Ca II lines polarised, each column with its own smooth seeded B, gammaB and chiB.
-    The profiles are left to the device (computeProfiles=False)."""
+    The profiles are left to the device (computeProfiles=False).  Nspace: FAL-C resampled to that many depth points
+    before it is perturbed (default: its own 82)."""
     from . import models
     from ..model import StokesData
     base = models.falc82()
+    if Nspace is not None:
+        base = models.resample(base, Nspace)
     ker = np.ones(9) / 9.0
     probs = []
     for c in range(ncol):

@@ -1,13 +1,14 @@
-"""Generate tests/golden/falc_stokes_small.npz by running the REAL Lightweaver core's full-Stokes path.
+"""Generate tests/golden/falc_stokes_small.npz and falc_stokes_matrix.npz by running the REAL Lightweaver core's
+full-Stokes path.
 
 Runs only where the reference sources exist (/root/reference/Source, or LW_REFERENCE_SOURCE): it compiles
 tests/golden/stokes_driver.cpp (which builds on oracle/ref_driver.cpp) together with the reference's own sources, with the
 flags of oracle/Makefile, into a temporary directory; no compiled file enters the tree.  The Zeeman components come from
 the reference's lightweaver/zeeman.py, loaded by file path.
 
-    python tests/golden/make_stokes_golden.py
+    python tests/golden/make_stokes_golden.py [small] [matrix]      (default: both)
 
-Problem: harness.zeeman.falc_h_ca_stokes() -- FAL-C, H_6 + CaII_6 at lineScale 0.2, 3 rays (the last one mu = 1), a
+falc_stokes_small.npz.  Problem: harness.zeeman.falc_h_ca_stokes() -- FAL-C, H_6 + CaII_6 at lineScale 0.2, 3 rays (the last one mu = 1), a
 depth-varying B, gammaB, chiB; Ca II H, K and the IR triplet polarised.  The atmosphere and atoms are rebuilt from the
 harness by the tests (the fixture holds a few of their arrays to check that); the field, the rays, the components and
 the projections are stored.  Keys:
@@ -19,6 +20,17 @@ the projections are stored.  Keys:
   out/up/{I,Quv}                             formal_sol_full_stokes(updateJ=False, upOnly=True)
   out/j/{I,Quv,J,dJMax,dJMaxIdx}             updateJ=True, upOnly=False
   out/j20/{I,Quv,J,J20,dJMax,dJMaxIdx}       the same with ExtraParams "J20"
+
+falc_stokes_matrix.npz.  The cases of tests/stokes_cases.py (velocities, 3 to 130 depth points, 1 to 7 rays, CALLABLE
+and THERMALISED boundaries on either side, a PRD line's rho, strong / zero / edge-on fields, J20), each rebuilt by the tests
+from stokes_cases.build.  Keys:
+  in/alpha<i>, in/shift<i>, in/strength<i>   Zeeman components of polarised line i (the same lines in every case)
+  in/<case>/muz, in/<case>/vlosMu            rebuild check; in/<case>/bcData, in/<case>/J20: wavelength row ROW of them
+  prof/<case>/<name><i>                      moving82 and fastv: phi, phiQ..psiV of line i at every DEPTH_STRIDE-th depth, wphi
+  out/<case>/<variant>/{I,Quv}               variants up (updateJ False, upOnly True), j (True, False) and, for two cases,
+                                             all (False, False) and jup (True, True).  Quv is stored as zero at
+                                             wavelengths without a polarised line: the core leaves it unspecified there
+  out/<case>/<variant>/{J,dJMax,dJMaxIdx}    with updateJ; J (and J20 of case j20) at the depths stokes_cases.j_depths
 """
 import ctypes as C
 import importlib.util
@@ -41,6 +53,7 @@ from lightweaver_amd.harness import zeeman  # noqa: E402
 REF = os.environ.get('LW_REFERENCE_SOURCE', '/root/reference/Source')
 REF_PY = os.path.join(os.path.dirname(REF), 'lightweaver', 'zeeman.py')
 OUT = os.path.join(HERE, 'falc_stokes_small.npz')
+OUT_MATRIX = os.path.join(HERE, 'falc_stokes_matrix.npz')
 DEPTH_STRIDE = 8
 
 
@@ -81,8 +94,8 @@ def reference_components(prob):
     return out
 
 
-def run_variant(lib, comps, updateJ, upOnly, J20=None):
-    prob = zeeman.falc_h_ca_stokes()
+def run_variant(lib, comps, updateJ, upOnly, J20=None, prob=None):
+    prob = zeeman.falc_h_ca_stokes() if prob is None else prob
     for L, (al, st, sh) in zip(prob.stokes.lines, comps):
         L.alpha, L.strength, L.shift = al, st, sh
     st = prob.stokes
@@ -105,7 +118,7 @@ def run_variant(lib, comps, updateJ, upOnly, J20=None):
     return prob, res, j20
 
 
-def main():
+def make_small():
     if not os.path.exists(os.path.join(REF, 'LightweaverAmalgamated.cpp')) or not os.path.exists(REF_PY):
         print(f'reference sources not present at {REF}: nothing generated')
         return
@@ -146,5 +159,59 @@ def main():
     print(f'wrote {OUT}: {os.path.getsize(OUT)} bytes')
 
 
+def make_matrix():
+    if not os.path.exists(os.path.join(REF, 'LightweaverAmalgamated.cpp')) or not os.path.exists(REF_PY):
+        print(f'reference sources not present at {REF}: nothing generated')
+        return
+    from tests import stokes_cases as sc
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        lib = build_driver(tmp)
+        comps = reference_components(sc.build('n3'))
+        for i, (al, sg, sh) in enumerate(comps):
+            out[f'in/alpha{i}'], out[f'in/strength{i}'], out[f'in/shift{i}'] = al, sg, sh
+        for case in sc.CASES:
+            base = sc.build(case)
+            out[f'in/{case}/muz'] = base.muz.copy()
+            out[f'in/{case}/vlosMu'] = base.vlosMu.copy()
+            for bc in (base.zLowerBc, base.zUpperBc):
+                if bc.type == abi.BC_CALLABLE:
+                    out[f'in/{case}/bcData'] = bc.bcData[sc.MATRIX_ROW].copy()
+            J20 = base.stokes.J20
+            if J20 is not None:
+                out[f'in/{case}/J20'] = J20[sc.MATRIX_ROW].copy()
+            pol = sc.polarised_mask(base, j20=J20 is not None)
+            kd = sc.j_depths(base.Nspace)
+            for variant in sc.variants(case):
+                updateJ, upOnly = sc.VARIANTS[variant]
+                prob, res, j20 = run_variant(lib, comps, updateJ, upOnly, J20=J20, prob=sc.build(case))
+                key = f'out/{case}/{variant}'
+                out[f'{key}/I'] = prob.I.copy()
+                out[f'{key}/Quv'] = np.where(pol[None, :, None], prob.Quv, 0.0)
+                if updateJ:
+                    out[f'{key}/J'] = prob.J[:, kd].copy()
+                    out[f'{key}/dJMax'], out[f'{key}/dJMaxIdx'] = np.array(res.dJMax), np.array(res.dJMaxIdx)
+                    if j20 is not None:
+                        out[f'{key}/J20'] = j20[:, kd].copy()
+                if case in sc.PROFILE_CASES and variant == 'up':
+                    ks = slice(None, None, sc.DEPTH_STRIDE)
+                    for i, L in enumerate(prob.stokes.lines):
+                        t = prob.atoms[L.atom].trans[L.trans]
+                        out[f'prof/{case}/phi{i}'] = t.phi[..., ks].copy()
+                        out[f'prof/{case}/wphi{i}'] = t.wphi.copy()
+                        for name in sc.PROFILE_NAMES:
+                            out[f'prof/{case}/{name}{i}'] = getattr(L, name)[..., ks].copy()
+    np.savez_compressed(OUT_MATRIX, **out)
+    print(f'wrote {OUT_MATRIX}: {os.path.getsize(OUT_MATRIX)} bytes')
+
+
+def main(argv):
+    what = argv or ['small', 'matrix']
+    if 'small' in what:
+        make_small()
+    if 'matrix' in what:
+        make_matrix()
+
+
 if __name__ == '__main__':
-    main()
+    main(sys.argv[1:])

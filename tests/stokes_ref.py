@@ -1,7 +1,7 @@
 """numpy restatement of formal_sol_full_stokes (Source/FormalStokes.cpp:166-723) for the tests: the chi[7] / eta[4]
 gather of stokes_fs_core, the DELO-Bezier3 march of piecewise_stokes_bezier3_1d_impl (vectorised over rays) and the
 scalar piecewise_bezier3_1d where a wavelength is not polarised.  Pinned to the reference by tests/test_stokes_ref.py
-(falc_stokes_small.npz); the GPU tests use it where the fixture cannot reach (the timed grid).  The profiles (phi and
+(falc_stokes_small.npz and every case of falc_stokes_matrix.npz); the GPU tests use it where the fixture cannot reach (the timed grid).  The profiles (phi and
 phiQ..psiV of the problem's lines) are inputs.  Q, U, V are zero at unpolarised wavelengths, as on the device."""
 import numpy as np
 
@@ -132,7 +132,8 @@ def _iupw(prob, chi0, la, mu, d, zmu):
         Bk0, Bk1 = _planck(T[k0], wav), _planck(T[k1], wav)
         return Bk0 - (Bk1 - Bk0) / dtau
     if bc.type == abi.BC_CALLABLE:
-        return bc.bcData[la, bc.idxs[mu, d]]
+        m = bc.idxs[mu, d]
+        return np.where(m >= 0, bc.bcData[la, np.maximum(m, 0)], 0.0)
     return np.zeros(chi0.shape[0])
 
 

@@ -4,7 +4,9 @@ CPU: the struct layout against the header, the refusals without a device, the pr
 GPU: the profiles against a numpy restatement of Transition::compute_polarised_profiles built on scipy's Faddeeva
 function, and exact properties of the transfer problem that need no oracle: the scalar solver at unpolarised
 wavelengths, the symmetries of field reversal and azimuth rotation on the disc-centre ray, no side effects, and a clean
-run at the timed size."""
+run at the timed size.  Then the device against the reference: the static fixture (falc_stokes_small.npz) and the parity
+matrix of tests/stokes_cases.py (falc_stokes_matrix.npz: velocities, 3 to 130 depth points, every boundary branch, a PRD
+line's rho, field edge cases, all four (updateJ, upOnly) variants), and the wavelength chunking, which must be invisible."""
 import ctypes as C
 import subprocess
 from fractions import Fraction
@@ -17,6 +19,7 @@ from lightweaver_amd.harness import models
 from lightweaver_amd.harness import zeeman
 from lightweaver_amd.model import StokesData, update_projections
 
+from tests import stokes_cases as sc
 from tests import stokes_ref
 
 STRUCTS = [abi.lwhip_stokes_line, abi.lwhip_stokes]
@@ -334,17 +337,158 @@ def test_stale_device_profiles_do_not_replace_polarised_phi(gpu):
 
 @pytest.mark.gpu
 def test_timed_size_against_numpy_march(gpu):
+    from lightweaver_amd.context import Context
     prob = models.throughput_grid()
     Ns = prob.Nspace
     z = np.linspace(0.0, 1.0, Ns)
     prob.set_stokes(StokesData(B=0.1 * (0.5 + z), gammaB=0.3 + 0.9 * z, chiB=0.2 + 1.1 * z,
                                mux=np.sqrt(1.0 - prob.muz ** 2), muy=np.zeros(prob.Nrays),
                                lines=zeeman.polarise_lines(prob, 1)))
-    _run(prob, upOnly=True)
-    pol = _polarised_mask(prob)
-    rng = np.random.default_rng(5)
-    las = np.sort(np.concatenate([rng.choice(np.flatnonzero(pol), 48, replace=False),
-                                  rng.choice(np.flatnonzero(~pol), 16, replace=False)]))
-    I, Quv, *_ = stokes_ref.full_stokes(prob, updateJ=False, upOnly=True, las=las)
+    J0 = prob.J.copy()
+    with Context(prob) as ctx:
+        ctx.compute_polarised_profiles()
+        ctx.single_stokes_fs(upOnly=True)
+        pol = _polarised_mask(prob)
+        rng = np.random.default_rng(5)
+        las = np.sort(np.concatenate([rng.choice(np.flatnonzero(pol), 48, replace=False),
+                                      rng.choice(np.flatnonzero(~pol), 16, replace=False)]))
+        I, Quv, *_ = stokes_ref.full_stokes(prob, updateJ=False, upOnly=True, las=las)
+        assert np.max(np.abs(prob.I[las] / I - 1.0)) <= 1e-9
+        assert np.max(np.abs(prob.Quv[:, las] - Quv) / I[None]) <= 1e-9
+        # both directions with J updated: several 256 MB wavelength chunks, each with its own rows of I and Q at every
+        # depth for stokes_j_kernel
+        chunk = (256 << 20) // (prob.Nrays * 2 * 13 * Ns * 8)
+        assert prob.Nlambda > 2 * chunk
+        res = ctx.single_stokes_fs(updateJ=True, upOnly=False)
+    las = np.unique(np.concatenate([las, [0, prob.Nlambda - 1]]))
+    # (the wavelengths sampled lie in more than one chunk, the last one included)
+    assert len(set(las // chunk)) >= 3 and (prob.Nlambda - 1) // chunk in set(las // chunk)
+    ref = prob.copy()
+    ref.J[...] = J0     # (J dagger of the restatement is the J the call read, not the one it wrote)
+    I, Quv, J, _, dJ = stokes_ref.full_stokes(ref, updateJ=True, upOnly=False, las=las)
+    print('timed size, updateJ: I', np.max(np.abs(prob.I[las] / I - 1.0)), 'Quv',
+          np.max(np.abs(prob.Quv[:, las] - Quv) / I[None]), 'J', np.max(np.abs(prob.J[las] / J - 1.0)))
     assert np.max(np.abs(prob.I[las] / I - 1.0)) <= 1e-9
     assert np.max(np.abs(prob.Quv[:, las] - Quv) / I[None]) <= 1e-9
+    assert np.max(np.abs(prob.J[las] / J - 1.0)) <= 1e-9
+    assert np.all(np.isfinite(prob.J)) and res.dJMax >= dJ.max() * (1.0 - 1e-9)
+
+
+# ---- the parity matrix (falc_stokes_matrix.npz, tests/stokes_cases.py) --------------------------------------------------
+
+@pytest.fixture(scope='module')
+def matrix():
+    return sc.load_fixture()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case,variant', sc.case_variants())
+def test_matrix_against_reference(gpu, matrix, case, variant):
+    """The device against the real core on every case and variant of the matrix, to the project's device-vs-reference
+    tolerance of 1e-9 (the numpy restatement meets the same bound on the CPU, tests/test_stokes_ref.py)."""
+    from lightweaver_amd.context import Context
+    updateJ, upOnly = sc.VARIANTS[variant]
+    prob = sc.fixture_problem(matrix, case)
+    J20 = prob.stokes.J20          # (an argument of the call, as in test_parity_with_reference)
+    prob.stokes.J20 = None
+    with Context(prob) as ctx:
+        ctx.compute_polarised_profiles()
+        res = ctx.single_stokes_fs(updateJ=updateJ, upOnly=upOnly, J20=J20)
+    pol = sc.polarised_mask(prob, j20=J20 is not None)
+    err = sc.errors_against(matrix, case, variant, prob.I, prob.Quv, J=prob.J if updateJ else None,
+                            dJMax=res.dJMax if updateJ else None,
+                            J20=prob.stokes.J20 if updateJ and J20 is not None else None, pol=pol)
+    print('matrix', case, variant, err)
+    assert set(err) >= ({'I', 'Quv', 'J', 'dJMax'} if updateJ else {'I', 'Quv'})
+    assert all(v <= 1e-9 for v in err.values()), err
+    if updateJ:
+        assert res.dJMaxIdx == int(matrix[f'out/{case}/{variant}/dJMaxIdx'])
+    assert np.all(prob.Quv[:, ~pol] == 0.0)
+    if case != 'B0':
+        assert np.abs(prob.Quv[:, pol]).max() > 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', sc.PROFILE_CASES)
+def test_moving_profiles_against_faddeeva(gpu, matrix, case):
+    """The device's polarised profiles on a moving atmosphere, both directions: against the numpy restatement built on
+    scipy's Faddeeva function at every depth, and against the core's own (every 8th depth)."""
+    from lightweaver_amd.context import Context
+    prob = sc.fixture_problem(matrix, case)
+    with Context(prob) as ctx:
+        ctx.compute_polarised_profiles()
+    ks = slice(None, None, sc.DEPTH_STRIDE)
+    for i, L in enumerate(prob.stokes.lines):
+        t = prob.atoms[L.atom].trans[L.trans]
+        # the two directions differ: otherwise the sign of the velocity term is invisible
+        assert not np.array_equal(t.phi[:, :, 0], t.phi[:, :, 1])
+        assert np.max(np.abs(t.phi[:, :, 0] / t.phi[:, :, 1] - 1.0)) > 1e-2
+        ref = stokes_ref.ref_profiles(prob, L)
+        scale = np.abs(ref['phi'])
+        pscale = scale + np.abs(ref['psiQ']) + np.abs(ref['psiU']) + np.abs(ref['psiV'])
+        assert np.max(np.abs(t.phi - ref['phi']) / scale) <= 1e-12
+        for name in sc.PROFILE_NAMES:
+            got = getattr(L, name)
+            for d in (0, 1):
+                e = np.max(np.abs(got[:, :, d] - ref[name][:, :, d]) / (scale if name.startswith('phi') else pscale)[:, :, d])
+                assert e <= 1e-12, (name, d, e)
+            assert np.abs(got).max() > 0.0, name
+        assert np.max(np.abs(t.wphi / ref['wphi'] - 1.0)) <= 1e-12
+        got = {name: getattr(L, name)[..., ks] for name in sc.PROFILE_NAMES}
+        got['phi'], got['wphi'] = t.phi[..., ks], t.wphi
+        err = sc.profile_errors(matrix, case, i, got)
+        print('profiles', case, i, err)
+        assert all(v <= 1e-12 for v in err.values()), err
+
+
+CHUNK_VARIANTS = [(False, True), (False, False), (True, False), (True, True)]
+
+
+@pytest.mark.gpu
+def test_wavelength_chunks_are_invisible(gpu, matrix, monkeypatch):
+    """LWHIP_STOKES_CHUNK_LA (a debug knob) sets the wavelengths of a chunk of lwhip_full_stokes_fs: every output is the
+    same bits for 1, 7 (no divisor of 208) and 64 wavelengths per chunk as for the whole grid in one."""
+    from lightweaver_amd.context import Context
+    prob = sc.fixture_problem(matrix, 'moving82')
+    rng = np.random.default_rng(11)
+    J0 = prob.J.copy()
+    J20dag = 0.05 * J0 * (rng.random(J0.shape) - 0.5)
+    assert prob.Nlambda == 208
+    monkeypatch.delenv('LWHIP_STOKES_CHUNK_LA', raising=False)
+    with Context(prob) as ctx:
+        ctx.compute_polarised_profiles()
+        for updateJ, upOnly in CHUNK_VARIANTS:
+            base = None
+            for chunk in (None, 1, 7, 64):
+                if chunk is None:
+                    monkeypatch.delenv('LWHIP_STOKES_CHUNK_LA', raising=False)
+                else:
+                    monkeypatch.setenv('LWHIP_STOKES_CHUNK_LA', str(chunk))
+                prob.J[...] = J0
+                res = ctx.single_stokes_fs(updateJ=updateJ, upOnly=upOnly, J20=J20dag.copy())
+                got = dict(I=prob.I.copy(), Quv=prob.Quv.copy(), J=prob.J.copy(), J20=prob.stokes.J20.copy(),
+                           dJMax=np.array(res.dJMax), dJMaxIdx=np.array(res.dJMaxIdx))
+                if base is None:
+                    base = got
+                    assert np.abs(got['Quv']).max() > 0.0 and (not updateJ or not np.array_equal(got['J'], J0))
+                    continue
+                for k in base:
+                    assert np.array_equal(got[k], base[k]), (updateJ, upOnly, chunk, k)
+    monkeypatch.delenv('LWHIP_STOKES_CHUNK_LA', raising=False)
+
+
+def test_stokes_needs_three_depth_points(hip_lib):
+    """A 2-point column is refused with ERR_INVALID.  Every context needs Nspace >= 3, so the refusal comes from
+    lwhip_create: lwhip_full_stokes_fs, which repeats the check, is never reached with such a column and there is no
+    device I or Quv that it could have touched; the 3-point column next to it runs (test_matrix_against_reference[n3-*])."""
+    from lightweaver_amd.context import Context, LwHipError
+    atmos = models.resample(models.falc82(), 2)
+    prob = models.build_problem(atmos, [models.H_6(0.2), models.CaII_6(0.2)], Nrays=3)
+    prob.set_stokes(StokesData(B=np.full(2, 0.1), gammaB=np.full(2, 0.3), chiB=np.full(2, 0.2),
+                               mux=np.sqrt(1.0 - prob.muz ** 2), muy=np.zeros(3), lines=zeeman.polarise_lines(prob, 1)))
+    I0, Q0 = prob.I.copy(), prob.Quv.copy()
+    with pytest.raises(LwHipError, match=r'\(%d\).*Nspace >= 3' % abi.ERR_INVALID):
+        with Context(prob) as ctx:
+            ctx.compute_polarised_profiles()
+            ctx.single_stokes_fs(upOnly=True)
+    assert np.array_equal(prob.I, I0) and np.array_equal(prob.Quv, Q0)

@@ -141,6 +141,23 @@ def test_batch_matches_single_context(gpu):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('Ns', (3, 24, 130))
+def test_batch_other_depth_counts(gpu, Ns):
+    """The batch kernels at other depth counts than FAL-C's 82: the first step, the last-but-one step and the last point of
+    the marches fall onto each other at 3 points.  The single context is held to the reference at these depths by
+    tests/test_stokes.py::test_matrix_against_reference."""
+    probs = zeeman.stokes_columns(3, Nspace=Ns, **SMALL)
+    assert all(p.Nspace == Ns for p in probs)
+    singles = [_single(p, VARIANTS) for p in [q.copy() for q in probs]]
+    got = _batched(probs, VARIANTS)
+    for v, (updateJ, upOnly) in enumerate(VARIANTS):
+        for i in range(len(probs)):
+            _assert_same(got[v][i], singles[i][v], (Ns, updateJ, upOnly, i))
+    pol = _polarised_mask(probs[0])
+    assert np.abs(got[0][0]['Quv'][:, pol]).max() > 0.0 and got[2][0]['dJMax'] > 0.0
+
+
+@pytest.mark.gpu
 def test_batch_with_j20_matches_single_context(gpu):
     probs = _with_j20(zeeman.stokes_columns(8, **SMALL))
     probs[3].stokes.J20 = None   # (a column without J20 in the same batch: an ordinary call for it)
