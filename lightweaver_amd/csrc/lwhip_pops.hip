@@ -3,8 +3,19 @@
 // variant assembles a small dense system and solves it with the reference's solver:
 // Crout LU with implicit row scaling and partial pivoting + one residual-correction pass
 // (solve_lin_eq / lu_decompose / lu_backsub, Source/LuSolve.cpp:8-132).  The systems are tiny
-// (N = Nlevel = 6, or sum Nlevel + 1 = 13), so this is latency-, not throughput-bound (< 1 % of an
+// (N = Nlevel for statistical equilibrium and the time-dependent update, 1 <= N <= 32; N = sum Nlevel + 1
+// <= 64 for the Newton-Raphson step), so this is latency-, not throughput-bound (< 1 % of an
 // iteration); coalescing comes from the depth index being the fastest axis of every array.
+// Two paths:
+//  - registers, 2 <= N <= 6 (SOLVE_REG_MAXN): d_solve_lin_eq_reg<N> of lwhip_lu.h, one unrolled instantiation
+//    per N picked by a switch; stat_eq and time_dep only (the NR system is assembled in LDS at every size);
+//  - LDS, N = 1 and N >= 7, and every NR system: d_solve_lin_eq below on a per-thread workspace of
+//    2 N^2 + 5 N doubles.  The block size is the largest power of two <= 64 whose workspaces fit 150 KB
+//    (solve_block_threads: 64 threads up to N = 11, 32 up to 16, 16 up to 23, 8 up to 33, 4 up to 47, 2 up to
+//    64); above 48 KB the kernel's dynamic-LDS limit is raised first (solve_set_lds).  A stat_eq launch takes
+//    block size and LDS from its largest atom; smaller atoms take the register path inside those blocks.
+// Both paths, every register instantiation and every block-size class (11, 13, 21, 32, 40 and 64 equations) are
+// tested against the oracle and an extended-precision solution (tests/test_pops_levels.py).
 #include "lwhip_device.h"
 #include "../../include/lwhip.h"
 
