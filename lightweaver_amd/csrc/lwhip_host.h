@@ -281,12 +281,33 @@ struct HostTrans
     int64_t parOff, phiOff, rhoOff;
     int64_t waveOff; // lines: offset of the full own grid / wlambda in the lineWave / lineWlam pools
 };
+// The transitions active at each wavelength row, in the reference's order (active atoms, then detailed ones; kr order): row la
+// has laTr[laOff[la] .. laOff[la + 1]).  local: the rows of the context's own grid (NblueLoc / NredLoc), or of the global one.
+inline void active_trans_lists(const std::vector<HostTrans>& trans, int Nla, bool local, std::vector<int32_t>& laOff,
+                               std::vector<int32_t>& laTr)
+{
+    laOff.assign(Nla + 1, 0);
+    laTr.clear();
+    for (int la = 0; la < Nla; ++la)
+    {
+        laOff[la] = (int32_t)laTr.size();
+        for (size_t tr = 0; tr < trans.size(); ++tr)
+        {
+            const HostTrans& h = trans[tr];
+            if (la >= (local ? h.NblueLoc : h.t.Nblue) && la < (local ? h.NredLoc : h.t.Nred))
+                laTr.push_back((int32_t)tr);
+        }
+    }
+    laOff[Nla] = (int32_t)laTr.size();
+    if (laTr.empty())
+        laTr.push_back(0); // (never an empty upload)
+}
 }
 using namespace lwhip;
 
 namespace lwhip
 {
-// full Stokes (lwhip_stokes.hip): one transition as the Stokes gather reads it
+// full Stokes (lwhip_stokes.hip, lwhip_stokes_fs.hip): one transition as the Stokes gather reads it
 struct StokesTrans
 {
     int32_t type, gi, gj, Nblue; // (gi, gj: global level rows into the n pool)
@@ -305,8 +326,8 @@ struct StokesState
     std::vector<int32_t> laPolHost;// per wavelength: a polarised line is active
     int64_t polTot = 0;
     bool polOnDevice = false;      // phiQ..psiV were computed on the device since the last LWHIP_STOKES transfer
-    DevBuf<double> B, proj, pol, Quv, J20, comp, scratch, Isc, dJ;
-    DevBuf<int32_t> alpha, laOff, laTr, laPol, singular;
+    DevBuf<double> B, proj, pol, Quv, J20, comp;
+    DevBuf<int32_t> alpha, laOff, laTr, laPol;
     DevBuf<StokesTrans> tr;
     DevBuf<PolLineArgs> args;
     std::vector<PolLineArgs> argsHost;
@@ -314,7 +335,7 @@ struct StokesState
 int stokes_transfer(lwhip_context* c, bool up); // lwhip_upload / lwhip_download of LWHIP_STOKES
 // the refusals the Stokes entry points share, the device check first (lwhip_stokes.hip)
 int check_stokes_ctx(lwhip_context* c, const char* what, bool needStokes);
-struct StokesBatch; // what a column batch keeps for its full-Stokes calls (lwhip_stokes_batch.hip)
+struct StokesBatch; // what a context, or a column batch, keeps for its full-Stokes formal solutions (lwhip_stokes_fs.hip)
 void stokes_batch_release(StokesBatch* s);
 struct RaysState; // observer rays (lwhip_rays.hip): the gather tables of a context, the staging of its -- or a batch's -- calls
 void rays_release(RaysState* s);
@@ -511,6 +532,7 @@ struct lwhip_context
     std::vector<double> gatherHost;
     DevBuf<int32_t> status;
     StokesState stokes;           // lwhip_set_stokes (lwhip_stokes.hip)
+    StokesBatch* stokesFs = nullptr; // made by the first lwhip_full_stokes_fs (lwhip_stokes_fs.hip)
     RaysState* rays = nullptr;    // made by the first lwhip_compute_rays (lwhip_rays.hip)
 
     bool profiling = false;
@@ -568,6 +590,7 @@ struct lwhip_context
             (void)hipStreamSynchronize(stream);
         for (PinnedBlock* b : { &stage, &gatherPinned, &prdPinned, &prdPinnedPipe, &fpPinned, &lsDbg })
             b->release(); // (before the stream they were used on goes back to its pool)
+        stokes_batch_release(stokesFs);
         rays_release(rays);
         for (auto& pr : pending)
         {
@@ -648,7 +671,7 @@ int run_2d(lwhip_context* c, int lambdaIterate, int mode = 0);
 }
 
 // ---- 1.5D column batches: one iteration of n structurally identical contexts in one set of launches (lwhip_batch.hip;
-// their full-Stokes calls: lwhip_stokes_batch.hip) ----------
+// their full-Stokes calls: lwhip_stokes_batch.hip, lwhip_stokes_fs.hip) ----------
 struct lwhip_batch
 {
     std::vector<lwhip_context*> ctxs;
@@ -666,7 +689,9 @@ struct lwhip_batch
     int seMaxNl = 0;
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments
-    StokesBatch* stokes = nullptr;   // made by the first full-Stokes call
+    DevBuf<PolLineArgs> polList;     // every column's polarised lines, as polHost (lwhip_batch_compute_polarised_profiles)
+    std::vector<PolLineArgs> polHost;
+    StokesBatch* stokes = nullptr;   // made by the first lwhip_batch_full_stokes_fs
     RaysState* rays = nullptr;       // made by the first lwhip_batch_compute_rays
 };
 
@@ -675,4 +700,6 @@ namespace lwhip
 // lwhip_batch.hip
 int batch_ensure_profiles(lwhip_batch* b);                                  // the columns whose profiles went stale
 int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols); // tile-blocked copies of their phi, one launch list
+// lwhip_stokes_batch.hip: the refusals the batch's Stokes entry points share
+int check_stokes_batch(lwhip_batch* b, const char* what);
 }

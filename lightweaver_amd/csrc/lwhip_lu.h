@@ -1,6 +1,6 @@
 // lwhip_lu.h -- the reference's dense solver with the system in registers: solve_lin_eq (Source/LuSolve.cpp:8-132), Crout LU
 // with implicit row scaling, partial pivoting and one residual-correction pass.  Used by the population updates
-// (lwhip_pops.hip, N <= 6) and by the 4 x 4 DELO-Bezier3 step of the Stokes march (lwhip_stokes.hip).  Both units include it
+// (lwhip_pops.hip, N <= 6) and by the 4 x 4 DELO-Bezier3 step of the Stokes march (lwhip_stokes_fs.hip).  Both units include it
 // after `#pragma clang fp contract(off)`, so that its operations match the reference's one for one.
 #pragma once
 #include "lwhip_device.h"

@@ -26,7 +26,7 @@
 // H(a, v) under the same contraction setting as the stored profiles' unit: the same argument gives the same bits
 #include "lwhip_voigt_dev.h"
 
-// As in lwhip_stokes.hip: no fused multiply-adds from here on, so that the operations match the reference's one for one.
+// As in lwhip_stokes_fs.hip: no fused multiply-adds from here on, so that the operations match the reference's one for one.
 #pragma clang fp contract(off)
 
 #include <algorithm>
@@ -393,17 +393,8 @@ int rays_tables(lwhip_context* o, RaysState*& out)
         t.waveOff = h.waveOff >= 0 ? h.waveOff : 0;
         t.lambda0 = h.t.lambda0;
     }
-    std::vector<int32_t> laOff(o->Nla + 1, 0), laTr;
-    for (int la = 0; la < o->Nla; ++la)
-    {
-        laOff[la] = (int32_t)laTr.size();
-        for (size_t i = 0; i < o->trans.size(); ++i)
-            if (la >= o->trans[i].NblueLoc && la < o->trans[i].NredLoc)
-                laTr.push_back((int32_t)i);
-    }
-    laOff[o->Nla] = (int32_t)laTr.size();
-    if (laTr.empty())
-        laTr.push_back(0);
+    std::vector<int32_t> laOff, laTr;
+    active_trans_lists(o->trans, o->Nla, true, laOff, laTr);
     HIP_TRY(hipSetDevice(o->device));
     // (outside any arena and any gathered upload: the tables outlive lwhip_create)
     HIP_TRY(s->tr.upload(o->mem, trs));

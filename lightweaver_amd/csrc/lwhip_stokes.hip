@@ -1,80 +1,13 @@
-// lwhip_stokes.hip -- the full-Stokes formal solution for Zeeman-polarised lines (1D plane-parallel): formal_sol_full_stokes
-// (Source/FormalStokes.cpp:166-723) and the entry points of include/lwhip.h that drive it and the polarised profiles
-// (whose kernels live with the other Voigt kernels in lwhip_voigt.hip).
-//
-// Layout.  A wavelength chunk runs as up to three launches on the context's stream:
-//   stokes_gather_kernel  one thread per (lambda, mu, direction, depth): chi[7] and eta[4] summed over the transitions
-//                         active at lambda (stokes_fs_core :496-602), stored as the ray's rows chi[0..6], S[0..3];
-//   stokes_march_kernel   one thread per (lambda, mu, direction): the DELO-Bezier3 march of piecewise_stokes_bezier3_1d_impl
-//                         (:166-340) down the ray with a 4 x 4 Crout LU per depth point (lwhip_lu.h), or the scalar
-//                         piecewise_bezier3_1d (FormalScalar.cpp:209-325) where the wavelength is not polarised;
-//   stokes_j_kernel       (updateJ) one thread per lambda: J, J20 and dJ, the rays added in the reference's order.
-// The march is serial in depth, so a ray is one lane.  10 240 x 5 up-going rays are 800 wavefronts, fewer than the chip's
-// 1 024 SIMDs: the march is latency-bound whatever its register count, and one lane per ray needs no exchange between
-// lanes.  K is carried as its six independent entries (stokes_K :119-142) and expanded where a step uses it; no scratch
-// memory ("Full Stokes").  The device functions the kernels call are shared with the column-batch kernels
-// (lwhip_stokes_dev.h, lwhip_stokes_batch.hip).
+// lwhip_stokes.hip -- the Stokes data of a context for Zeeman-polarised lines (1D plane-parallel): lwhip_set_stokes, its
+// transfers, the refusals the Stokes entry points share and lwhip_compute_polarised_profiles (whose kernels live with the
+// other Voigt kernels in lwhip_voigt.hip).  The formal solution that reads all this is lwhip_stokes_fs.hip.
 #include "lwhip_host.h"
-#include "lwhip_device.h"
-
-// As in lwhip_pops.hip: no fused multiply-adds, so that the operations match the reference's one for one.
-#pragma clang fp contract(off)
-
-#include "lwhip_stokes_dev.h"
 
 #include <algorithm>
-#include <cmath>
 #include <vector>
 
 namespace lwhip
 {
-namespace
-{
-__global__ void stokes_gather_kernel(const StokesArgs a)
-{
-    const size_t nRay = (size_t)a.nla * a.Nr * a.nDir;
-    const size_t total = nRay * a.Ns;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x)
-    {
-        const int Ns = a.Ns;
-        const int k = (int)(idx % Ns);
-        const size_t ray = idx / Ns;
-        const int d = a.dir0 + (int)(ray % a.nDir);
-        const int mu = (int)((ray / a.nDir) % a.Nr);
-        const int la = a.la0 + (int)(ray / ((size_t)a.nDir * a.Nr));
-        stokes_gather_point(a, la, mu, d, k, a.scratch + ray * ST_ROWS * Ns + k);
-    }
-}
-
-__global__ void __launch_bounds__(64) stokes_march_kernel(const StokesArgs a)
-{
-    const size_t nRay = (size_t)a.nla * a.Nr * a.nDir;
-    const size_t ray = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (ray >= nRay)
-        return;
-    const int Ns = a.Ns;
-    const int d = a.dir0 + (int)(ray % a.nDir);
-    const int mu = (int)((ray / a.nDir) % a.Nr);
-    const int la = a.la0 + (int)(ray / ((size_t)a.nDir * a.Nr));
-    const double* row = a.scratch + ray * ST_ROWS * Ns;
-    double* out0 = a.updateJ ? a.Isc + ray * 2 * Ns : nullptr;
-    double* out1 = a.updateJ ? out0 + Ns : nullptr;
-    stokes_march_ray(a, row, out0, out1, la, mu, d, a.nDir);
-}
-
-// J, J20 and dJ (stokes_j_lambda), one thread per wavelength
-__global__ void stokes_j_kernel(const StokesArgs a)
-{
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= a.nla)
-        return;
-    const int Ns = a.Ns;
-    stokes_j_lambda(a, a.la0 + l, a.nDir, [&](int mu, int dd, int q, int k) {
-        return a.Isc[(((size_t)l * a.Nr + mu) * a.nDir + dd) * 2 * Ns + (size_t)q * Ns + k];
-    });
-}
-} // namespace
-
 int check_stokes_ctx(lwhip_context* c, const char* what, bool needStokes)
 {
     if (lwhip_device_count() <= 0)
@@ -193,7 +126,7 @@ int lwhip_set_stokes(lwhip_context* c, const lwhip_stokes* st)
         }
     // the transitions active at each wavelength, in the reference's order (active atoms, then detailed ones; kr order)
     std::vector<StokesTrans> trs(c->trans.size());
-    std::vector<int32_t> laOff(Nla + 1, 0), laTr, laPol(Nla, 0);
+    std::vector<int32_t> laOff, laTr, laPol(Nla, 0);
     for (size_t tr = 0; tr < c->trans.size(); ++tr)
     {
         const HostTrans& h = c->trans[tr];
@@ -215,23 +148,11 @@ int lwhip_set_stokes(lwhip_context* c, const lwhip_stokes* st)
             t.polStride = (int64_t)(h.t.Nred - h.t.Nblue) * Nr * 2 * Ns;
         }
     }
+    active_trans_lists(c->trans, Nla, false, laOff, laTr);
     for (int la = 0; la < Nla; ++la)
-    {
-        laOff[la] = (int32_t)laTr.size();
-        for (size_t tr = 0; tr < c->trans.size(); ++tr)
-        {
-            const HostTrans& h = c->trans[tr];
-            if (la >= h.t.Nblue && la < h.t.Nred)
-            {
-                laTr.push_back((int32_t)tr);
-                if (polOfTr[tr] >= 0)
-                    laPol[la] = 1;
-            }
-        }
-    }
-    laOff[Nla] = (int32_t)laTr.size();
-    if (laTr.empty())
-        laTr.push_back(0);
+        for (int q = laOff[la]; q < laOff[la + 1]; ++q)
+            if (polOfTr[laTr[q]] >= 0)
+                laPol[la] = 1;
     s.laPolHost = laPol;
     HIP_TRY(s.tr.upload(c->mem, trs));
     HIP_TRY(s.laOff.upload(c->mem, laOff));
@@ -249,8 +170,6 @@ int lwhip_set_stokes(lwhip_context* c, const lwhip_stokes* st)
         HIP_TRY(s.J20.alloc(c->mem, (size_t)Nla * Ns));
     else
         s.J20.release();
-    HIP_TRY(s.dJ.alloc_zero(c->mem, (size_t)Nla));
-    HIP_TRY(s.singular.alloc_zero(c->mem, 1));
     // the profile kernels' argument blocks
     s.argsHost.clear();
     for (int i = 0; i < st->Nlines; ++i)
@@ -309,128 +228,5 @@ int lwhip_compute_polarised_profiles(lwhip_context* c)
     // phi of the polarised lines changed: the two directions of an angle stay alike only without line-of-sight velocities
     c->phiSym = c->phiSym && c->vlosZero;
     return retile_profiles(c);
-}
-
-int lwhip_full_stokes_fs(lwhip_context* c, int updateJ, int upOnly, lwhip_iter_result* res)
-{
-    int chk = check_stokes_ctx(c, "lwhip_full_stokes_fs", true);
-    if (chk != LWHIP_OK)
-        return chk;
-    HIP_TRY(hipSetDevice(c->device));
-    if (updateJ && c->JhostReg)
-        return fail(LWHIP_ERR_UNSUPPORTED, "lwhip_full_stokes_fs: updateJ with a mapped host J (lwhip_map_host_J(ctx, 0) first)");
-    if (c->Ns < 3)
-        return fail(LWHIP_ERR_INVALID, "lwhip_full_stokes_fs: needs at least 3 depth points");
-    {
-        const int stp = ensure_profiles(c);
-        if (stp != LWHIP_OK)
-            return stp;
-    }
-    StokesState& s = c->stokes;
-    const int Ns = c->Ns, Nr = c->Nrays, Nla = c->Nla;
-    const int nDir = upOnly ? 1 : 2;
-    // wavelength chunks: the rows of a chunk's rays stay within 256 MB; LWHIP_STOKES_CHUNK_LA (LWHIP_DEBUG) sets the
-    // wavelengths of a chunk instead (the results are the same bits for any chunking, tested)
-    const size_t perLa = (size_t)Nr * nDir * (ST_ROWS + (updateJ ? 2 : 0)) * Ns * sizeof(double);
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)Nla, ((size_t)256 << 20) / perLa));
-    const int dbgChunk = dbg_env_int("LWHIP_STOKES_CHUNK_LA", 0);
-    if (dbgChunk > 0)
-        chunk = std::max(1, std::min(Nla, dbgChunk));
-    const size_t raysChunk = (size_t)chunk * Nr * nDir;
-    if (s.scratch.n < raysChunk * ST_ROWS * Ns)
-        HIP_TRY(s.scratch.alloc(c->mem, raysChunk * ST_ROWS * Ns));
-    if (updateJ && s.Isc.n < raysChunk * 2 * Ns)
-        HIP_TRY(s.Isc.alloc(c->mem, raysChunk * 2 * Ns));
-    StokesArgs a{};
-    a.Ns = Ns;
-    a.Nr = Nr;
-    a.Nla = Nla;
-    a.nDir = nDir;
-    a.dir0 = upOnly ? 1 : 0;
-    a.updateJ = updateJ ? 1 : 0;
-    a.hasJ20 = s.desc.J20 ? 1 : 0;
-    a.lowerType = c->prob.zLowerBc.type;
-    a.upperType = c->prob.zUpperBc.type;
-    a.lowerNmu = c->prob.zLowerBc.Nmu;
-    a.upperNmu = c->prob.zUpperBc.Nmu;
-    a.height = c->height.p;
-    a.temperature = c->temperature.p;
-    a.muz = c->muz.p;
-    a.wmu = c->wmu.p;
-    a.wavelength = c->wavelength.p;
-    a.bgChi = c->bgChi.p;
-    a.bgEta = c->bgEta.p;
-    a.bgSca = c->bgSca.p;
-    a.J = c->J.p;
-    a.J20 = s.J20.p;
-    a.n = c->n.p;
-    a.ratio = c->ratio.p;
-    a.par = c->par.p;
-    a.phi = c->phi.p;
-    a.rho = c->rho.p;
-    a.pol = s.pol.p;
-    a.lowerBc = c->lowerBcData.p;
-    a.upperBc = c->upperBcData.p;
-    a.lowerIdx = c->lowerIdx.p;
-    a.upperIdx = c->upperIdx.p;
-    a.laOff = s.laOff.p;
-    a.laTr = s.laTr.p;
-    a.laPol = s.laPol.p;
-    a.tr = s.tr.p;
-    a.scratch = s.scratch.p;
-    a.Isc = s.Isc.p;
-    a.I = c->I.p;
-    a.Quv = s.Quv.p;
-    a.dJ = s.dJ.p;
-    a.singular = s.singular.p;
-    HIP_TRY(hipMemsetAsync(s.singular.p, 0, sizeof(int32_t), c->stream));
-    for (int la0 = 0; la0 < Nla; la0 += chunk)
-    {
-        a.la0 = la0;
-        a.nla = std::min(chunk, Nla - la0);
-        const size_t nRay = (size_t)a.nla * Nr * nDir;
-        const int gBlocks = (int)std::min<size_t>((nRay * Ns + 255) / 256, 16384);
-        LWHIP_LAUNCH(stokes_gather_kernel, dim3(gBlocks), dim3(256), 0, c->stream, a);
-        LWHIP_LAUNCH(stokes_march_kernel, dim3((unsigned)((nRay + 63) / 64)), dim3(64), 0, c->stream, a);
-        if (updateJ)
-            LWHIP_LAUNCH(stokes_j_kernel, dim3((a.nla + 63) / 64), dim3(64), 0, c->stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (updateJ)
-        c->fpJValid = false;
-    int32_t singular = 0;
-    HIP_TRY(hipMemcpyAsync(&singular, s.singular.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (res)
-    {
-        res->updatedJ = updateJ ? 1 : 0;
-        res->dJMax = 0.0;
-        res->dJMaxIdx = 0;
-    }
-    if (updateJ)
-    {
-        // formal_sol_full_stokes_impl's serial loop: dJMax = max_idx(dJ, dJMax, maxIdx, la) (FormalStokes.cpp:708-714)
-        std::vector<double> dJ(Nla);
-        HIP_TRY(hipMemcpyAsync(dJ.data(), s.dJ.p, Nla * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        double dJMax = 0.0;
-        int maxIdx = 0;
-        for (int la = 0; la < Nla; ++la)
-        {
-            if (dJ[la] < dJMax)
-                maxIdx = la;
-            else
-                dJMax = dJ[la];
-        }
-        if (res)
-        {
-            res->dJMax = dJMax;
-            res->dJMaxIdx = maxIdx;
-        }
-    }
-    else
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    if (singular)
-        return fail(LWHIP_ERR_SINGULAR, "lwhip_full_stokes_fs: Singular Matrix in the 4 x 4 DELO-Bezier3 step");
-    return LWHIP_OK;
 }
 }

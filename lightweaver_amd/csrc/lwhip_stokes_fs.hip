@@ -1,31 +1,48 @@
-// lwhip_stokes_dev.h -- the device side of the full-Stokes formal solution that the single-context kernels (lwhip_stokes.hip)
-// and the column-batch kernels (lwhip_stokes_batch.hip) share: the per-column argument block, the gather of one depth point,
-// the upwind intensity, the DELO-Bezier3 and scalar Bezier3 marches of one ray, and the J / J20 / dJ sums of one wavelength.
+// lwhip_stokes_fs.hip -- the full-Stokes formal solution for Zeeman-polarised lines (1D plane-parallel): formal_sol_full_stokes
+// (Source/FormalStokes.cpp:166-723) of one context (lwhip_full_stokes_fs) or of every column of a 1.5D batch
+// (lwhip_batch_full_stokes_fs).  One driver, stokes_fs_run, serves both: a context on its own is a batch of one column.
 //
-// The marches are templated on how a ray's rows are read and its I / Q profile is written: a plain pointer (the
-// single-context layout, row m at depth k is row[m * Ns + k]) or a LaneRow (the batch's layout, the same element 64
-// doubles further per index, so that the 64 rays of a wavefront sit side by side).  Only the addressing differs; every
-// operation, and its order, is the same in both, so a column of a batch gets the bits of its own context.
-//
-// Both units include this after `#pragma clang fp contract(off)` (repeated here): no fused multiply-adds, so that the
-// operations match the reference's one for one.
-#pragma once
-#pragma clang fp contract(off)
-
+// A chunk of (columns x wavelength range) runs as up to three launches on the first column's stream, each over ALL columns
+// of the chunk, the column outermost in the work index:
+//   stokes_gather_kernel  one workgroup per block of 64 rays: chi[7] and eta[4] of every depth point summed over the
+//                         transitions active at lambda (stokes_fs_core :496-602), stored as the rays' rows chi[0..6], S[0..3];
+//   stokes_march_kernel   one lane per ray, one wavefront per block of 64 rays: the DELO-Bezier3 march of
+//                         piecewise_stokes_bezier3_1d_impl (:166-340) down the ray with a 4 x 4 Crout LU per depth point
+//                         (lwhip_lu.h), or the scalar piecewise_bezier3_1d (FormalScalar.cpp:209-325) where the wavelength
+//                         is not polarised;
+//   stokes_j_kernel       (updateJ) one thread per (column, lambda): J, J20 and dJ, the rays added in the reference's order.
+// The march is serial in depth, so a ray is one lane and needs no exchange between lanes.  K is carried as its six
+// independent entries (stokes_K :119-142) and expanded where a step uses it; no scratch memory ("Full Stokes").
+// Layout.  A column's rays of the chunk (its nla x Nr x nDir rays: lambda outermost, then mu, then direction) are cut into
+// blocks of 64, the last one padded, so that every wavefront belongs to one column and reads its argument block with scalar
+// loads.  A block's rows are [ST_ROWS][Ns][64]: at each depth point the 64 lanes read 64 consecutive doubles.  The I / Q
+// profiles of updateJ are [2][Ns][64] per block.
+// Scratch.  The rows of a chunk belong to the caller's slot (the context's, or the batch's) and are capped by the caller:
+// they do not grow with the number of columns.  A chunk takes as many whole columns as fit, or one column's wavelength
+// range when a single column does not fit.  The results are the same bits for any chunking (tested).
 #include "lwhip_host.h"
 #include "lwhip_device.h"
+
+// As in lwhip_pops.hip: no fused multiply-adds, so that the operations match the reference's one for one.
+#pragma clang fp contract(off)
+
 #include "lwhip_lu.h"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
 
 namespace lwhip
 {
 namespace
 {
 enum { ST_ROWS = 11 }; // per ray: chi[0..6], S[0..3]
+enum { SB_LANES = 64 };
 
+// one column: its context's resident state and where its results go
 struct StokesArgs
 {
-    int32_t Ns, Nr, la0, nla;
-    int32_t Nla, nDir, dir0, updateJ;
+    int32_t Ns, Nr, Nla, updateJ;
     int32_t hasJ20, _pad;
     int32_t lowerType, upperType, lowerNmu, upperNmu;
     const double* height;
@@ -52,28 +69,29 @@ struct StokesArgs
     const int32_t* laTr;
     const int32_t* laPol;
     const StokesTrans* tr;
-    double* scratch; // [nla * Nr * nDir][ST_ROWS][Ns] (single context)
-    double* Isc;     // [nla * Nr * nDir][2][Ns]: I and Q at every depth (updateJ; single context)
     double* I;       // [Nla, Nr]
     double* Quv;     // [3, Nla, Nr]
     double* dJ;      // [Nla]
     int32_t* singular; // set when a depth point's 4 x 4 system is singular (solve_lin_eq throws there, LuSolve.cpp:22-23)
 };
 
-// One element of a ray's rows in the batch layout: index i is 64 doubles (one per lane of the wavefront's rays) after i - 1
+// One ray's rows within its block: index i is 64 doubles (one per lane of the wavefront's rays) after i - 1, so row m at
+// depth k is row[m * Ns + k]
 template <typename T> struct LaneRow
 {
     T* p;
-    DEVINL T& operator[](int i) const { return p[(size_t)i * 64]; }
-    DEVINL LaneRow operator+(int i) const { return LaneRow{ p + (size_t)i * 64 }; }
+    DEVINL T& operator[](int i) const { return p[(size_t)i * SB_LANES]; }
+    DEVINL LaneRow operator+(int i) const { return LaneRow{ p + (size_t)i * SB_LANES }; }
     DEVINL explicit operator bool() const { return p != nullptr; }
 };
+using RowIn = LaneRow<const double>;
+using RowOut = LaneRow<double>;
 
 DEVINL bool polarised_la(const StokesArgs& a, int la) { return a.laPol[la] != 0 || a.hasJ20; }
 
 // chi[7] and eta[4] of (la, mu, d) at depth k summed over the transitions active at la (stokes_fs_core :496-602), stored as
 // the ray's rows chi[0..6], S[0..3]: row[m * Ns] is row m at this depth
-template <typename W> DEVINL void stokes_gather_point(const StokesArgs& a, int la, int mu, int d, int k, W row)
+DEVINL void stokes_gather_point(const StokesArgs& a, int la, int mu, int d, int k, RowOut row)
 {
     const int Ns = a.Ns;
     const double inv2root2 = 1.0 / (2.0 * sqrt(2.0));
@@ -157,7 +175,7 @@ template <typename W> DEVINL void stokes_gather_point(const StokesArgs& a, int l
 }
 
 // Iupw of the ray's first point (:365-410 / FormalScalar.cpp:551-597): Stokes I only
-template <typename R> DEVINL double upwind_intensity(const StokesArgs& a, R chi0, int la, int mu, int d, double zmu)
+DEVINL double upwind_intensity(const StokesArgs& a, RowIn chi0, int la, int mu, int d, double zmu)
 {
     const int Ns = a.Ns;
     const int dk = d ? -1 : 1;
@@ -195,7 +213,7 @@ template <typename R> DEVINL double upwind_intensity(const StokesArgs& a, R chi0
 
 // K of stokes_K (:119-142) as its six independent entries u = (K01, K02, K03, K12, K13, K23); K is symmetric in its first
 // row and column and antisymmetric in the 3 x 3 block below them (K10 = u0, K21 = -u3, K31 = -u4, K32 = -u5)
-template <typename R> DEVINL void stokes_k6(R row, int Ns, int k, double (&u)[6])
+DEVINL void stokes_k6(RowIn row, int Ns, int k, double (&u)[6])
 {
     const double chiI = row[k];
     u[0] = row[1 * Ns + k] / chiI;
@@ -229,8 +247,7 @@ DEVINL void prod44(const double (&A)[4][4], double (&C)[4][4])
 }
 
 // piecewise_bezier3_1d_impl (FormalScalar.cpp:209-325) without the operator; I0 at every depth into `out` if given
-template <typename R, typename O>
-DEVINL double scalar_bezier3(const StokesArgs& a, R chi, R S, double zmu, int d, double Iupw, O out)
+DEVINL double scalar_bezier3(const StokesArgs& a, RowIn chi, RowIn S, double zmu, int d, double Iupw, RowOut out)
 {
     const int Ns = a.Ns;
     const double* h = a.height;
@@ -307,13 +324,13 @@ DEVINL double scalar_bezier3(const StokesArgs& a, R chi, R S, double zmu, int d,
 
 // piecewise_stokes_bezier3_1d_impl (:166-340); I(0..3) of the last point (k_end) returned, I and Q at every depth into
 // out0 / out1 if given
-template <typename R, typename O>
-DEVINL void stokes_bezier3(const StokesArgs& a, R row, double zmu, int d, double Iupw, O out0, O out1, double (&Iend)[4])
+DEVINL void stokes_bezier3(const StokesArgs& a, RowIn row, double zmu, int d, double Iupw, RowOut out0, RowOut out1,
+                           double (&Iend)[4])
 {
     const int Ns = a.Ns;
     const double* h = a.height;
-    const R chi = row;
-    const R Srow = row + 7 * Ns;
+    const RowIn chi = row;
+    const RowIn Srow = row + 7 * Ns;
     int dk = -1, k_start = Ns - 1, k_end = 0;
     if (!d)
     {
@@ -464,8 +481,7 @@ DEVINL void stokes_bezier3(const StokesArgs& a, R row, double zmu, int d, double
 
 // One ray (la, mu, d) of a context whose rows are `row`: its march, I and Q at every depth into out0 / out1 (updateJ), and
 // the emergent Stokes vector into a.I / a.Quv
-template <typename R, typename O>
-DEVINL void stokes_march_ray(const StokesArgs& a, R row, O out0, O out1, int la, int mu, int d, int nDir)
+DEVINL void stokes_march_ray(const StokesArgs& a, RowIn row, RowOut out0, RowOut out1, int la, int mu, int d, int nDir)
 {
     const int Ns = a.Ns;
     const double zmu = 1.0 / a.muz[mu];
@@ -536,5 +552,296 @@ template <typename F> DEVINL void stokes_j_lambda(const StokesArgs& a, int la, i
     }
     a.dJ[la] = dJMax;
 }
+
+// one chunk: columns [col0, col0 + ncol) x wavelengths [la0, la0 + nla)
+struct StokesChunk
+{
+    const StokesArgs* cols; // [n] the columns' argument blocks
+    int32_t col0, ncol, la0, nla;
+    int32_t nDir, dir0, blocksPerCol, Ns;
+    int32_t Nr, updateJ;
+    double* scratch; // [ncol * blocksPerCol][ST_ROWS][Ns][64]
+    double* Isc;     // [ncol * blocksPerCol][2][Ns][64]: I and Q at every depth (updateJ)
+};
+
+// (la, mu, d) of ray r of a column in the chunk
+DEVINL void chunk_ray(const StokesChunk& b, int r, int& la, int& mu, int& d)
+{
+    d = b.dir0 + r % b.nDir;
+    mu = (r / b.nDir) % b.Nr;
+    la = b.la0 + r / (b.nDir * b.Nr);
+}
+
+// one workgroup of 256 threads per block of 64 rays: 64 lanes x 4 depth points at a time
+__global__ void __launch_bounds__(256) stokes_gather_kernel(const StokesChunk b)
+{
+    const int blk = blockIdx.x;
+    const int lane = threadIdx.x % SB_LANES;
+    const StokesArgs a = b.cols[b.col0 + blk / b.blocksPerCol];
+    const int r = (blk % b.blocksPerCol) * SB_LANES + lane;
+    if (r >= b.nla * b.Nr * b.nDir)
+        return;
+    int la, mu, d;
+    chunk_ray(b, r, la, mu, d);
+    const int Ns = b.Ns;
+    double* base = b.scratch + (size_t)blk * ST_ROWS * Ns * SB_LANES + lane;
+    for (int k = threadIdx.x / SB_LANES; k < Ns; k += blockDim.x / SB_LANES)
+        stokes_gather_point(a, la, mu, d, k, RowOut{ base + (size_t)k * SB_LANES });
+}
+
+// one wavefront per block of 64 rays, a lane per ray.  One wavefront per SIMD: held to two (256 registers) the march spills
+// 37 VGPRs to scratch memory ("Full Stokes")
+__global__ void __launch_bounds__(64) stokes_march_kernel(const StokesChunk b)
+{
+    const int blk = blockIdx.x;
+    const int lane = threadIdx.x;
+    const StokesArgs a = b.cols[b.col0 + blk / b.blocksPerCol];
+    const int r = (blk % b.blocksPerCol) * SB_LANES + lane;
+    if (r >= b.nla * b.Nr * b.nDir)
+        return;
+    int la, mu, d;
+    chunk_ray(b, r, la, mu, d);
+    const int Ns = b.Ns;
+    const RowIn row{ b.scratch + (size_t)blk * ST_ROWS * Ns * SB_LANES + lane };
+    const RowOut out0{ b.updateJ ? b.Isc + (size_t)blk * 2 * Ns * SB_LANES + lane : nullptr };
+    const RowOut out1{ b.updateJ ? out0.p + (size_t)Ns * SB_LANES : nullptr };
+    stokes_march_ray(a, row, out0, out1, la, mu, d, b.nDir);
+}
+
+// J, J20 and dJ: one thread per wavelength of the chunk, blockIdx.y = the column in the chunk
+__global__ void stokes_j_kernel(const StokesChunk b)
+{
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    const int col = blockIdx.y;
+    if (l >= b.nla)
+        return;
+    const StokesArgs a = b.cols[b.col0 + col];
+    const int Ns = b.Ns;
+    stokes_j_lambda(a, b.la0 + l, b.nDir, [&](int mu, int dd, int q, int k) {
+        const int r = (l * b.Nr + mu) * b.nDir + dd;
+        const size_t blk = (size_t)col * b.blocksPerCol + r / SB_LANES;
+        return b.Isc[((blk * 2 + q) * Ns + k) * SB_LANES + r % SB_LANES];
+    });
+}
+} // namespace
+
+// what a context, or a batch, keeps for its full-Stokes formal solutions
+struct StokesBatch
+{
+    DevBuf<StokesArgs> args; // the columns' argument blocks, as argsHost
+    std::vector<StokesArgs> argsHost;
+    DevBuf<double> scratch, Isc; // one chunk's rows and I / Q profiles
+    DevBuf<double> tail;         // [n][Nla] dJ of every column, then n int32 singular flags
+    PinnedBlock tailPinned;
+};
+
+void stokes_batch_release(StokesBatch* s)
+{
+    if (s)
+        s->tailPinned.release();
+    delete s;
+}
+
+namespace
+{
+StokesArgs stokes_args(lwhip_context* c, int updateJ, double* dJ, int32_t* singular)
+{
+    const StokesState& s = c->stokes;
+    StokesArgs a{};
+    a.Ns = c->Ns;
+    a.Nr = c->Nrays;
+    a.Nla = c->Nla;
+    a.updateJ = updateJ ? 1 : 0;
+    a.hasJ20 = s.desc.J20 ? 1 : 0;
+    a.lowerType = c->prob.zLowerBc.type;
+    a.upperType = c->prob.zUpperBc.type;
+    a.lowerNmu = c->prob.zLowerBc.Nmu;
+    a.upperNmu = c->prob.zUpperBc.Nmu;
+    a.height = c->height.p;
+    a.temperature = c->temperature.p;
+    a.muz = c->muz.p;
+    a.wmu = c->wmu.p;
+    a.wavelength = c->wavelength.p;
+    a.bgChi = c->bgChi.p;
+    a.bgEta = c->bgEta.p;
+    a.bgSca = c->bgSca.p;
+    a.J = c->J.p;
+    a.J20 = s.J20.p;
+    a.n = c->n.p;
+    a.ratio = c->ratio.p;
+    a.par = c->par.p;
+    a.phi = c->phi.p;
+    a.rho = c->rho.p;
+    a.pol = s.pol.p;
+    a.lowerBc = c->lowerBcData.p;
+    a.upperBc = c->upperBcData.p;
+    a.lowerIdx = c->lowerIdx.p;
+    a.upperIdx = c->upperIdx.p;
+    a.laOff = s.laOff.p;
+    a.laTr = s.laTr.p;
+    a.laPol = s.laPol.p;
+    a.tr = s.tr.p;
+    a.I = c->I.p;
+    a.Quv = s.Quv.p;
+    a.dJ = dJ;
+    a.singular = singular;
+    return a;
+}
+
+// formal_sol_full_stokes_impl's serial loop: dJMax = max_idx(dJ, dJMax, maxIdx, la) (FormalStokes.cpp:708-714)
+void stokes_max_idx(const double* dJ, int Nla, lwhip_iter_result& r)
+{
+    double dJMax = 0.0;
+    int maxIdx = 0;
+    for (int la = 0; la < Nla; ++la)
+    {
+        if (dJ[la] < dJMax)
+            maxIdx = la;
+        else
+            dJMax = dJ[la];
+    }
+    r.dJMax = dJMax;
+    r.dJMaxIdx = maxIdx;
+}
+
+// The call: the n columns `cols` (of batch `b`, or one context on its own: b null), everything on cols[0]'s stream, the
+// scratch in `slot` and at most capBytes of it.  The columns have passed check_stokes_ctx / check_stokes_batch.
+int stokes_fs_run(lwhip_context* const* cols, int n, lwhip_batch* b, int updateJ, int upOnly, lwhip_iter_result* results,
+                  StokesBatch*& slot, size_t capBytes, const char* whatC)
+{
+    const std::string what(whatC);
+    auto column = [&](const char* pre, int i) { return n > 1 ? pre + std::to_string(i) : std::string(); };
+    for (int i = 0; i < n; ++i)
+        if (updateJ && cols[i]->JhostReg)
+            return fail(LWHIP_ERR_UNSUPPORTED, what + ": updateJ with a mapped host J" + column(" in column ", i)
+                                                   + " (lwhip_map_host_J(ctx, 0) first)");
+    lwhip_context* c0 = cols[0];
+    if (c0->Ns < 3)
+        return fail(LWHIP_ERR_INVALID, what + ": needs at least 3 depth points");
+    HIP_TRY(hipSetDevice(c0->device));
+    {
+        const int stp = b ? batch_ensure_profiles(b) : ensure_profiles(c0);
+        if (stp != LWHIP_OK)
+            return stp;
+    }
+    if (!slot)
+        slot = new StokesBatch();
+    StokesBatch& sb = *slot;
+    const int Ns = c0->Ns, Nr = c0->Nrays, Nla = c0->Nla;
+    const int nDir = upOnly ? 1 : 2;
+    const size_t tailN = (size_t)n * Nla + (n + 1) / 2; // the dJ rows, then the flags
+    if (sb.tail.n < tailN)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        HIP_TRY(sb.tail.alloc(c0->mem, tailN));
+        HIP_TRY(sb.tailPinned.reserve(c0->device, tailN * sizeof(double), c0->stream));
+    }
+    int32_t* flags = (int32_t*)(sb.tail.p + (size_t)n * Nla);
+    // the columns' argument blocks (uploaded again only when one of them changed)
+    std::vector<StokesArgs> args(n);
+    for (int i = 0; i < n; ++i)
+        args[i] = stokes_args(cols[i], updateJ, sb.tail.p + (size_t)i * Nla, flags + i);
+    if (sb.argsHost.size() != args.size() || std::memcmp(sb.argsHost.data(), args.data(), args.size() * sizeof(StokesArgs)) != 0)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream)); // (nothing queued may still read the blocks about to be replaced)
+        sb.argsHost = args;
+        if (sb.args.n < (size_t)n)
+            HIP_TRY(sb.args.alloc(c0->mem, (size_t)n, false));
+        HIP_TRY(hipMemcpyAsync(sb.args.p, sb.argsHost.data(), (size_t)n * sizeof(StokesArgs), hipMemcpyHostToDevice, c0->stream));
+    }
+    // chunks of (columns x wavelength range) whose rows stay within the cap.  Two debug knobs (LWHIP_DEBUG) make small chunks
+    // for the tests: LWHIP_STOKES_BATCH_RAYS caps the rays of a chunk instead, LWHIP_STOKES_CHUNK_LA caps its wavelengths
+    const size_t rowsPerRay = (size_t)ST_ROWS + (updateJ ? 2 : 0);
+    size_t maxBlocks = std::max<size_t>(1, capBytes / (rowsPerRay * Ns * sizeof(double) * SB_LANES));
+    const int dbgRays = dbg_env_int("LWHIP_STOKES_BATCH_RAYS", 0);
+    if (dbgRays > 0)
+        maxBlocks = std::max<size_t>(1, (size_t)dbgRays / SB_LANES);
+    const size_t raysPerLa = (size_t)Nr * nDir;
+    int nlaChunk = (int)std::min<size_t>((size_t)Nla, std::max<size_t>(1, maxBlocks * SB_LANES / raysPerLa));
+    const int dbgLa = dbg_env_int("LWHIP_STOKES_CHUNK_LA", 0);
+    if (dbgLa > 0)
+        nlaChunk = std::min(nlaChunk, dbgLa);
+    const size_t blocksPerColMax = (nlaChunk * raysPerLa + SB_LANES - 1) / SB_LANES;
+    // (65 535: the columns of a chunk are the second grid dimension of stokes_j_kernel)
+    const int colsChunk = (int)std::max<size_t>(1, std::min<size_t>({ (size_t)n, maxBlocks / blocksPerColMax, 65535 }));
+    const size_t blocksMax = (size_t)colsChunk * blocksPerColMax;
+    if (sb.scratch.n < blocksMax * ST_ROWS * Ns * SB_LANES || (updateJ && sb.Isc.n < blocksMax * 2 * Ns * SB_LANES))
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        if (sb.scratch.n < blocksMax * ST_ROWS * Ns * SB_LANES)
+            HIP_TRY(sb.scratch.alloc(c0->mem, blocksMax * ST_ROWS * Ns * SB_LANES, false));
+        if (updateJ && sb.Isc.n < blocksMax * 2 * Ns * SB_LANES)
+            HIP_TRY(sb.Isc.alloc(c0->mem, blocksMax * 2 * Ns * SB_LANES, false));
+    }
+    HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n * sizeof(int32_t), c0->stream));
+    StokesChunk ch{};
+    ch.cols = sb.args.p;
+    ch.nDir = nDir;
+    ch.dir0 = upOnly ? 1 : 0;
+    ch.Ns = Ns;
+    ch.Nr = Nr;
+    ch.updateJ = updateJ ? 1 : 0;
+    ch.scratch = sb.scratch.p;
+    ch.Isc = sb.Isc.p;
+    for (int col0 = 0; col0 < n; col0 += colsChunk)
+        for (int la0 = 0; la0 < Nla; la0 += nlaChunk)
+        {
+            ch.col0 = col0;
+            ch.ncol = std::min(colsChunk, n - col0);
+            ch.la0 = la0;
+            ch.nla = std::min(nlaChunk, Nla - la0);
+            ch.blocksPerCol = (int)((ch.nla * raysPerLa + SB_LANES - 1) / SB_LANES);
+            const unsigned nBlk = (unsigned)ch.ncol * ch.blocksPerCol;
+            LWHIP_LAUNCH(stokes_gather_kernel, dim3(nBlk), dim3(256), 0, c0->stream, ch);
+            LWHIP_LAUNCH(stokes_march_kernel, dim3(nBlk), dim3(SB_LANES), 0, c0->stream, ch);
+            if (updateJ)
+                LWHIP_LAUNCH(stokes_j_kernel, dim3((ch.nla + 63) / 64, ch.ncol), dim3(64), 0, c0->stream, ch);
+            HIP_TRY(hipGetLastError());
+        }
+    if (updateJ)
+        for (int i = 0; i < n; ++i)
+            cols[i]->fpJValid = false;
+    // one copy back: the dJ rows (updateJ) and the flags, then one wait
+    const size_t off = updateJ ? 0 : (size_t)n * Nla;
+    HIP_TRY(hipMemcpyAsync(sb.tailPinned.as<double>() + off, sb.tail.p + off, (tailN - off) * sizeof(double), hipMemcpyDeviceToHost,
+                           c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    const double* dJ = sb.tailPinned.as<double>();
+    const int32_t* sing = (const int32_t*)(dJ + (size_t)n * Nla);
+    for (int i = 0; i < n && results; ++i)
+    {
+        results[i].updatedJ = updateJ ? 1 : 0;
+        results[i].dJMax = 0.0;
+        results[i].dJMaxIdx = 0;
+        if (updateJ)
+            stokes_max_idx(dJ + (size_t)i * Nla, Nla, results[i]);
+    }
+    for (int i = 0; i < n; ++i)
+        if (sing[i])
+            return fail(LWHIP_ERR_SINGULAR, what + ": Singular Matrix in the 4 x 4 DELO-Bezier3 step" + column(" of column ", i));
+    return LWHIP_OK;
+}
 } // namespace
 } // namespace lwhip
+
+extern "C"
+{
+int lwhip_full_stokes_fs(lwhip_context* c, int updateJ, int upOnly, lwhip_iter_result* res)
+{
+    const char* what = "lwhip_full_stokes_fs";
+    const int chk = check_stokes_ctx(c, what, true);
+    if (chk != LWHIP_OK)
+        return chk;
+    lwhip_context* cols[1] = { c };
+    return stokes_fs_run(cols, 1, nullptr, updateJ, upOnly, res, c->stokesFs, (size_t)256 << 20, what);
+}
+
+int lwhip_batch_full_stokes_fs(lwhip_batch* b, int updateJ, int upOnly, lwhip_iter_result* results)
+{
+    const char* what = "lwhip_batch_full_stokes_fs";
+    const int chk = check_stokes_batch(b, what);
+    if (chk != LWHIP_OK)
+        return chk;
+    return stokes_fs_run(b->ctxs.data(), (int)b->ctxs.size(), b, updateJ, upOnly, results, b->stokes, (size_t)1 << 30, what);
+}
+}

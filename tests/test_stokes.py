@@ -356,8 +356,10 @@ def test_timed_size_against_numpy_march(gpu):
         assert np.max(np.abs(prob.I[las] / I - 1.0)) <= 1e-9
         assert np.max(np.abs(prob.Quv[:, las] - Quv) / I[None]) <= 1e-9
         # both directions with J updated: several 256 MB wavelength chunks, each with its own rows of I and Q at every
-        # depth for stokes_j_kernel
-        chunk = (256 << 20) // (prob.Nrays * 2 * 13 * Ns * 8)
+        # depth for stokes_j_kernel.  A context's chunk is the whole blocks of 64 rays whose 11 + 2 rows of Ns doubles fit
+        # into 256 MB, and the whole wavelengths (Nrays x 2 rays each) that these blocks hold
+        blocks = (256 << 20) // (13 * Ns * 8 * 64)
+        chunk = blocks * 64 // (prob.Nrays * 2)
         assert prob.Nlambda > 2 * chunk
         res = ctx.single_stokes_fs(updateJ=True, upOnly=False)
     las = np.unique(np.concatenate([las, [0, prob.Nlambda - 1]]))
@@ -446,24 +448,27 @@ CHUNK_VARIANTS = [(False, True), (False, False), (True, False), (True, True)]
 
 @pytest.mark.gpu
 def test_wavelength_chunks_are_invisible(gpu, matrix, monkeypatch):
-    """LWHIP_STOKES_CHUNK_LA (a debug knob) sets the wavelengths of a chunk of lwhip_full_stokes_fs: every output is the
-    same bits for 1, 7 (no divisor of 208) and 64 wavelengths per chunk as for the whole grid in one."""
+    """LWHIP_STOKES_CHUNK_LA (a debug knob) caps the wavelengths of a chunk of lwhip_full_stokes_fs: every output is the
+    same bits for 1, 7 (no divisor of 208) and 64 wavelengths per chunk as for the whole grid in one.  So it is with
+    LWHIP_STOKES_BATCH_RAYS, the column batch's knob, which caps the rays of a chunk: one block of 64 rays, and five."""
     from lightweaver_amd.context import Context
     prob = sc.fixture_problem(matrix, 'moving82')
     rng = np.random.default_rng(11)
     J0 = prob.J.copy()
     J20dag = 0.05 * J0 * (rng.random(J0.shape) - 0.5)
     assert prob.Nlambda == 208
-    monkeypatch.delenv('LWHIP_STOKES_CHUNK_LA', raising=False)
+    knobs = ('LWHIP_STOKES_CHUNK_LA', 'LWHIP_STOKES_BATCH_RAYS')
+    for k in knobs:
+        monkeypatch.delenv(k, raising=False)
     with Context(prob) as ctx:
         ctx.compute_polarised_profiles()
         for updateJ, upOnly in CHUNK_VARIANTS:
             base = None
-            for chunk in (None, 1, 7, 64):
-                if chunk is None:
-                    monkeypatch.delenv('LWHIP_STOKES_CHUNK_LA', raising=False)
-                else:
-                    monkeypatch.setenv('LWHIP_STOKES_CHUNK_LA', str(chunk))
+            for chunk in (None, (0, 1), (0, 7), (0, 64), (1, 64), (1, 5 * 64)):
+                for k in knobs:
+                    monkeypatch.delenv(k, raising=False)
+                if chunk is not None:
+                    monkeypatch.setenv(knobs[chunk[0]], str(chunk[1]))
                 prob.J[...] = J0
                 res = ctx.single_stokes_fs(updateJ=updateJ, upOnly=upOnly, J20=J20dag.copy())
                 got = dict(I=prob.I.copy(), Quv=prob.Quv.copy(), J=prob.J.copy(), J20=prob.stokes.J20.copy(),
@@ -474,7 +479,8 @@ def test_wavelength_chunks_are_invisible(gpu, matrix, monkeypatch):
                     continue
                 for k in base:
                     assert np.array_equal(got[k], base[k]), (updateJ, upOnly, chunk, k)
-    monkeypatch.delenv('LWHIP_STOKES_CHUNK_LA', raising=False)
+    for k in knobs:
+        monkeypatch.delenv(k, raising=False)
 
 
 def test_stokes_needs_three_depth_points(hip_lib):

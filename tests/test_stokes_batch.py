@@ -249,6 +249,31 @@ def test_batch_chunks_order_and_single_column(gpu):
 
 
 @pytest.mark.gpu
+def test_member_context_alone_between_batched_calls(gpu):
+    """A column of a batch called alone through its own Context between two batched calls: the context's own scratch next
+    to the batch's.  All three results of that column are the same bits."""
+    from lightweaver_amd.batch import ColumnBatch
+    probs = zeeman.stokes_columns(3, **SMALL)
+    J0 = [p.J.copy() for p in probs]
+    with ColumnBatch(probs) as b:
+        assert b._batch is not None
+        b.compute_polarised_profiles(deviceResident=False)
+        for updateJ, upOnly in VARIANTS:
+            got = []
+            for alone in (False, True, False):
+                for p, j in zip(probs, J0):   # (every call uploads and reads the same J)
+                    p.J[...] = j
+                if alone:
+                    r = b.contexts[1].single_stokes_fs(updateJ=updateJ, upOnly=upOnly)
+                else:
+                    r = b.single_stokes_fs(updateJ=updateJ, upOnly=upOnly)[1]
+                got.append(_snap(probs[1], r))
+            _assert_same(got[1], got[0], ('alone', updateJ, upOnly))
+            _assert_same(got[2], got[0], ('batched again', updateJ, upOnly))
+            assert np.abs(got[0]['Quv']).max() > 0.0 and (not updateJ or got[0]['dJMax'] > 0.0)
+
+
+@pytest.mark.gpu
 def test_batch_refusals_launch_nothing(gpu):
     from lightweaver_amd.batch import ColumnBatch
     from lightweaver_amd.context import LwHipError
