@@ -690,6 +690,40 @@ int lwhip_compute_rays(lwhip_context* ctx, const lwhip_rays* rays);
  * lowerBc may differ.  Each column's results are the bits of lwhip_compute_rays on it. */
 int lwhip_batch_compute_rays(lwhip_batch* batch, const lwhip_rays* perColumn);
 
+/* ---- full Stokes along observer rays (1D) --------------------------------------------------------------------------------
+ * LwContext.compute_rays(mus, stokes=True) (Source/LwMiddleLayer.pyx:3898-4002) from the state resident on the device: for
+ * every wavelength of [laStart, laEnd) and every direction the emergent Stokes vector (I, Q, U, V at k = 0) of the up-going
+ * ray -- what lwhip_full_stokes_fs(updateJ = 0, upOnly = 1) gives on the context the reference would construct: the same state
+ * (n, J, rhoPrd, background), rays muz, vlosMu = mu (x) v_z, wmu = 0, the field projected onto the new directions, the polarised
+ * profiles of those directions (Transition::compute_polarised_profiles, Source/FormalStokes.cpp:9-117) and the plain Voigt phi
+ * for the other lines.  Needs Stokes data (lwhip_set_stokes): B and the Zeeman components are the resident ones; the profiles
+ * are formed inside the gather kernel where it needs them and never stored.  As the reference does, and therefore:
+ *   - no scattering term: without updateJ the Stokes source function uses J dagger = 0 (Source/FormalStokes.cpp:429-438, :591;
+ *     see lwhip_full_stokes_fs), so at wavelengths with background scattering I here is NOT the I of lwhip_compute_rays;
+ *   - a wavelength without a polarised line (and without J20) takes the scalar piecewise_bezier3_1d march and its Q, U, V are
+ *     exact zeros, as in lwhip_full_stokes_fs; hasJ20 follows the attached lwhip_stokes descriptor as there;
+ *   - any 1D formal solver is accepted: the Stokes path ignores the one the context was built with, so piecewise_linear_1d
+ *     and piecewise_besser_1d contexts are served here, unlike lwhip_compute_rays.
+ * Nothing of the context changes (I, Quv, J, any line's phi / wphi / phiQ..psiV, its profile bookkeeping, the argument blocks
+ * lwhip_full_stokes_fs keeps); only the request crosses to the device and only I and Quv come back (one copy each way, one
+ * wait).  All pointers are host pointers. */
+typedef struct lwhip_stokes_rays {
+    lwhip_rays rays;         /* Nmu, range, muz, vz, lowerBc, I as for lwhip_compute_rays; the three depth arrays must be NULL */
+    const double* cosGamma;  /* [Nmu, Nspace] projections of the field on the new directions, computed by the caller */
+    const double* cos2chi;   /* (as in lwhip_stokes: Atmosphere::update_projections)                                  */
+    const double* sin2chi;
+    double* Quv;             /* [3, Nla, Nmu] out */
+} lwhip_stokes_rays;
+/* Refusals, before anything is queued and with the outputs untouched: no device LWHIP_ERR_DEVICE; what lwhip_full_stokes_fs
+ * refuses (2D, a wavelength shard, hybrid PRD tables: LWHIP_ERR_UNSUPPORTED; no Stokes data: LWHIP_ERR_INVALID); what
+ * lwhip_compute_rays refuses, except the formal solver; a missing projection array or Quv, a depth array present:
+ * LWHIP_ERR_INVALID.  A singular 4 x 4 system: LWHIP_ERR_SINGULAR, the outputs written all the same. */
+int lwhip_compute_stokes_rays(lwhip_context* ctx, const lwhip_stokes_rays* rays);
+/* The same for every column of a batch in one set of launches: perColumn [n]; the conditions of lwhip_batch_full_stokes_fs (every
+ * column with column 0's polarised lines) and of lwhip_batch_compute_rays (Nmu and the wavelength range of column 0), the
+ * offending column named.  Each column's results are the bits of lwhip_compute_stokes_rays on it. */
+int lwhip_batch_compute_stokes_rays(lwhip_batch* batch, const lwhip_stokes_rays* perColumn);
+
 /* Block until all work queued on the context's stream has finished. */
 int lwhip_synchronize(lwhip_context* ctx);
 

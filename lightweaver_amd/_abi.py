@@ -168,6 +168,12 @@ class lwhip_rays(C.Structure):
                 ('depthChi', f64p), ('depthEta', f64p), ('depthI', f64p)]
 
 
+class lwhip_stokes_rays(C.Structure):
+    """Observer rays of lwhip_compute_stokes_rays: the lwhip_rays block (no depth arrays), the projections of the field on
+    the new directions [Nmu, Nspace] and the Quv output [3, Nla, Nmu] (host pointers)."""
+    _fields_ = [('rays', lwhip_rays), ('cosGamma', f64p), ('cos2chi', f64p), ('sin2chi', f64p), ('Quv', f64p)]
+
+
 _RAW = {}
 
 
@@ -265,6 +271,8 @@ SYMBOLS = [
     ('lwhip_batch_full_stokes_fs', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(lwhip_iter_result)]),
     ('lwhip_compute_rays', C.c_int, [ctx_p, C.POINTER(lwhip_rays)]),
     ('lwhip_batch_compute_rays', C.c_int, [C.c_void_p, C.POINTER(lwhip_rays)]),
+    ('lwhip_compute_stokes_rays', C.c_int, [ctx_p, C.POINTER(lwhip_stokes_rays)]),
+    ('lwhip_batch_compute_stokes_rays', C.c_int, [C.c_void_p, C.POINTER(lwhip_stokes_rays)]),
 ]
 
 

@@ -205,16 +205,31 @@ class ColumnBatch:
                                 dJMaxIdx=r.dJMaxIdx if updateJ else 0, crsw=c.crsw) for r, c in zip(res, self.contexts)]
 
     # -- emergent spectra along observer rays ------------------------------------------------------------------------------
-    def compute_rays(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False):
+    def compute_rays(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False, stokes=False, mux=None,
+                     muy=None):
         """Context.compute_rays of every column from its device-resident state, all columns in one set of launches and
         one copy back (lwhip_batch_compute_rays; an unfused batch runs the columns one after the other).  The same
         directions and wavelength range for every column; `vz` / `lowerBc`: None, or one array per column.  Returns I
-        [Ncolumns, Nla, Nmu], or with depthData a RaysResult whose I, chi, eta, Idepth carry the column axis first."""
+        [Ncolumns, Nla, Nmu], or with depthData a RaysResult whose I, chi, eta, Idepth carry the column axis first.
+        stokes: Context.compute_rays(stokes=True) of every column (lwhip_batch_compute_stokes_rays): [Ncolumns, 4, Nla, Nmu]."""
         import ctypes as C
         import numpy as np
         from .context import RaysResult
         n = len(self.contexts)
         per = lambda a, i: None if a is None else a[i]  # noqa: E731
+        if stokes:
+            if depthData:
+                raise ValueError('compute_rays: no depthData with stokes=True')
+            reqs = [c._stokes_rays_request(mus, laStart, laEnd, per(vz, i), per(lowerBc, i), mux, muy)
+                    for i, c in enumerate(self.contexts)]
+            if self._batch is not None:
+                lib = self.contexts[0].lib
+                arr = (abi.lwhip_stokes_rays * n)(*[q for q, _, _ in reqs])
+                _check(lib, lib.lwhip_batch_compute_stokes_rays(self._batch, arr), 'lwhip_batch_compute_stokes_rays')
+            else:
+                for c, (q, _, _) in zip(self.contexts, reqs):
+                    _check(c.lib, c.lib.lwhip_compute_stokes_rays(c._h, C.byref(q)), 'lwhip_compute_stokes_rays')
+            return np.stack([o for _, o, _ in reqs]) if reqs else np.zeros((0, 4, 0, 0))
         reqs = [c._rays_request(mus, laStart, laEnd, per(vz, i), per(lowerBc, i), depthData)
                 for i, c in enumerate(self.contexts)]
         if self._batch is not None:

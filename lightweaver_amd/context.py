@@ -482,7 +482,25 @@ class Context:
             r.depthChi, r.depthEta, r.depthI = (a.ctypes.data_as(abi.f64p) for a in (out.chi, out.eta, out.Idepth))
         return r, out, keep
 
-    def compute_rays(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False, squeeze=True):
+    def _stokes_rays_request(self, mus, laStart, laEnd, vz, lowerBc, mux, muy):
+        """The lwhip_stokes_rays block of one compute_rays(stokes=True) call: (struct, out [4, Nla, Nmu], keepalive).  Attaches
+        the Stokes data if needed and projects the field onto the new directions on the host (update_projections)."""
+        from .model import observer_azimuth, update_projections
+        self._stokes_attach(None)
+        r, res, keep = self._rays_request(mus, laStart, laEnd, vz, lowerBc, False)
+        st = self.prob.stokes
+        mux, muy = observer_azimuth(res.mus, mux, muy)
+        proj = [np.ascontiguousarray(a) for a in update_projections(res.mus, mux, muy, st.gammaB, st.chiB)]
+        out = np.zeros((4,) + res.I.shape)   # I, Q, U, V: the reference's layout
+        q = abi.lwhip_stokes_rays()
+        q.rays = r
+        q.rays.I = out[0].ctypes.data_as(abi.f64p)
+        q.cosGamma, q.cos2chi, q.sin2chi = (a.ctypes.data_as(abi.f64p) for a in proj)
+        q.Quv = out[1:].ctypes.data_as(abi.f64p)
+        return q, out, keep + proj
+
+    def compute_rays(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False, squeeze=True, stokes=False,
+                     mux=None, muy=None):
         """LwContext.compute_rays(mus, upOnly=True) (Source/LwMiddleLayer.pyx:3898-4002) from the state that is resident on
         the device: the emergent intensity I [Nla, Nmu] of the up-going rays with direction cosines `mus` (any values in
         (0, 1], no weights), over the wavelengths [laStart, laEnd) of the global grid (default: all this context holds).
@@ -490,7 +508,21 @@ class Context:
         defaults to vlosMu[0] / muz[0] of the resident atmosphere.  Nothing of the context changes, and nothing but the
         request crosses to the device: upload what the host changed first.  A CALLABLE lower boundary needs `lowerBc`
         [Nla, Nmu].  depthData: returns a RaysResult whose chi, eta and Idepth [Nla, Nmu, Nspace] are the run of each ray
-        with depth (DepthData of the to-observer direction).  squeeze: a scalar `mus` drops the Nmu axis."""
+        with depth (DepthData of the to-observer direction).  squeeze: a scalar `mus` drops the Nmu axis.
+        stokes: LwContext.compute_rays(mus, stokes=True): the emergent Stokes vector [4, Nla, Nmu] (I, Q, U, V) of the same
+        rays, i.e. single_stokes_fs(upOnly=True) of observer_problem(prob, mus, stokes=True) with the polarised profiles of
+        the new directions, which the gather kernel forms in place (lwhip_compute_stokes_rays).  Needs prob.set_stokes; `mux`
+        / `muy` [Nmu] place the directions in azimuth (default mux = sqrt(1 - mu^2), muy = 0, the reference's 1D convention).
+        As in the reference this I carries no scattering term (J dagger = 0 without updateJ), so it is not the I of
+        stokes=False where the background scatters; Q, U, V are exact zeros where no polarised line is active; any 1D
+        formal solver is accepted.  No depthData."""
+        if stokes:
+            if depthData:
+                raise ValueError('compute_rays: no depthData with stokes=True')
+            q, out, keep = self._stokes_rays_request(mus, laStart, laEnd, vz, lowerBc, mux, muy)
+            _check(self.lib, self.lib.lwhip_compute_stokes_rays(self._h, C.byref(q)), 'lwhip_compute_stokes_rays')
+            del keep
+            return out[:, :, 0] if squeeze and np.ndim(mus) == 0 else out
         r, out, keep = self._rays_request(mus, laStart, laEnd, vz, lowerBc, depthData)
         _check(self.lib, self.lib.lwhip_compute_rays(self._h, C.byref(r)), 'lwhip_compute_rays')
         del keep

@@ -302,6 +302,30 @@ inline void active_trans_lists(const std::vector<HostTrans>& trans, int Nla, boo
     if (laTr.empty())
         laTr.push_back(0); // (never an empty upload)
 }
+// What forming a line's profile at a point needs beside the point, per transition (the order of `trans`, which is what the lists
+// above index): where the pools keep vBroad of the line's atom, its aDamp row and its own wavelength grid, and lambda0.  For the
+// kernels that evaluate phi where they gather instead of reading a stored one: the observer rays (lwhip_rays.hip) and the
+// full-Stokes observer gather (lwhip_stokes_fs.hip).
+struct LineEval
+{
+    int32_t atom, row, ltStart, _pad; // row: aDamp row (lines) / ratio row (continua); ltStart: own-grid index of the shard's first row
+    int64_t waveOff;                   // the line's full own grid in the lineWave pool (0 for a continuum)
+    double lambda0;
+};
+inline std::vector<LineEval> line_eval_records(const std::vector<HostTrans>& trans)
+{
+    std::vector<LineEval> ev(std::max<size_t>(trans.size(), 1), LineEval{});
+    for (size_t tr = 0; tr < trans.size(); ++tr)
+    {
+        const HostTrans& h = trans[tr];
+        ev[tr].atom = h.atom;
+        ev[tr].row = h.row;
+        ev[tr].ltStart = h.ltStart;
+        ev[tr].waveOff = h.waveOff >= 0 ? h.waveOff : 0;
+        ev[tr].lambda0 = h.t.lambda0;
+    }
+    return ev;
+}
 }
 using namespace lwhip;
 
@@ -329,6 +353,11 @@ struct StokesState
     DevBuf<double> B, proj, pol, Quv, J20, comp;
     DevBuf<int32_t> alpha, laOff, laTr, laPol;
     DevBuf<StokesTrans> tr;
+    // for the observer gather, which forms the profiles of a new direction where it needs them: what evaluating each transition's
+    // profile takes (indexed as `tr`), and per polarised line the offset of its components in alpha / comp and their number
+    DevBuf<LineEval> ev;
+    DevBuf<int32_t> polComp;
+    int64_t nComp = 0; // all lines' components: `comp` holds the shifts, then the strengths
     DevBuf<PolLineArgs> args;
     std::vector<PolLineArgs> argsHost;
 };
@@ -702,4 +731,7 @@ int batch_ensure_profiles(lwhip_batch* b);                                  // t
 int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols); // tile-blocked copies of their phi, one launch list
 // lwhip_stokes_batch.hip: the refusals the batch's Stokes entry points share
 int check_stokes_batch(lwhip_batch* b, const char* what);
+// Every refusal of an observer-ray request, before anything is queued (lwhip_rays.hip); la0 / la1: the rows of the global grid it
+// asks for.  anySolver: the full-Stokes observer rays, which like lwhip_full_stokes_fs ignore the context's formal solver.
+int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, bool anySolver, int& la0, int& la1);
 }

@@ -342,6 +342,51 @@ void rays_release(RaysState* s)
     delete s;
 }
 
+// Every refusal of a request, before anything is queued.  la0 / la1: the rows of the global grid.  (Shared with the full-Stokes
+// observer rays, lwhip_stokes_fs.hip: anySolver.)
+int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, bool anySolver, int& la0, int& la1)
+{
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, what + ": null context");
+    if (!r)
+        return fail(LWHIP_ERR_INVALID, what + ": null request");
+    if (c->is2d)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": observer rays are 1D plane-parallel only");
+    if (c->hprd)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": not with hybrid PRD tables (rho there is tied to the quadrature rays)");
+    if (!anySolver && c->prob.formalSolver != LWHIP_FS_BEZIER3_1D)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": piecewise_bezier3_1d contexts only");
+    if (c->Ns < 3)
+        return fail(LWHIP_ERR_INVALID, what + ": needs at least 3 depth points");
+    if (c->Ns > RAYS_MAX_NS) // (lwhip_create admits no deeper 1D column: a guard for the LDS rows, should that change)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": more than " + std::to_string((int)RAYS_MAX_NS) + " depth points");
+    if (r->Nmu < 1 || !r->muz || !r->I)
+        return fail(LWHIP_ERR_INVALID, what + ": Nmu >= 1, muz and I are required");
+    if (r->Nmu > LWHIP_RAYS_MAX_MU)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": Nmu above LWHIP_RAYS_MAX_MU (" + std::to_string(LWHIP_RAYS_MAX_MU)
+                                               + " directions per call)");
+    for (int m = 0; m < r->Nmu; ++m)
+        if (!(r->muz[m] > 0.0 && r->muz[m] <= 1.0))
+            return fail(LWHIP_ERR_INVALID, what + ": direction cosine " + std::to_string(m) + " is outside (0, 1]");
+    la0 = (r->laStart == 0 && r->laEnd == 0) ? c->laStart : r->laStart;
+    la1 = (r->laEnd == 0) ? c->laEnd : r->laEnd;
+    if (la0 < c->laStart || la1 > c->laEnd || la1 <= la0)
+        return fail(LWHIP_ERR_INVALID, what + ": wavelength range [" + std::to_string(la0) + ", " + std::to_string(la1)
+                                           + ") is not inside the context's rows [" + std::to_string(c->laStart) + ", "
+                                           + std::to_string(c->laEnd) + ")");
+    if (c->prob.zLowerBc.type == LWHIP_BC_CALLABLE && !r->lowerBc)
+        return fail(LWHIP_ERR_INVALID, what + ": a CALLABLE lower boundary has no data for new directions (pass lowerBc [Nla, Nmu])");
+    const int nDepth = (r->depthChi ? 1 : 0) + (r->depthEta ? 1 : 0) + (r->depthI ? 1 : 0);
+    if (nDepth != 0 && nDepth != 3)
+        return fail(LWHIP_ERR_INVALID, what + ": depthChi, depthEta and depthI go together");
+    if (!r->vz && !c->prob.vlosMu)
+        return fail(LWHIP_ERR_INVALID, what + ": needs vz, or vlosMu in the descriptor");
+    for (const HostTrans& h : c->trans)
+        if (h.t.type == LWHIP_LINE && !h.t.aDamp)
+            return fail(LWHIP_ERR_INVALID, what + ": needs aDamp for every line (the profiles are evaluated in the kernel)");
+    return LWHIP_OK;
+}
+
 namespace
 {
 std::mutex g_raysCreate;
@@ -375,6 +420,7 @@ int rays_tables(lwhip_context* o, RaysState*& out)
         return LWHIP_OK;
     const int Ns = o->Ns;
     std::vector<RayTrans> trs(std::max<size_t>(o->trans.size(), 1));
+    const std::vector<LineEval> ev = line_eval_records(o->trans);
     for (size_t i = 0; i < o->trans.size(); ++i)
     {
         const HostTrans& h = o->trans[i];
@@ -385,13 +431,13 @@ int rays_tables(lwhip_context* o, RaysState*& out)
         t.gj = o->levelOff[h.atom] + h.t.j;
         t.Nblue = h.NblueLoc;
         t.prd = (h.t.type == LWHIP_LINE && h.t.prd && h.rhoOff >= 0) ? 1 : 0;
-        t.row = h.row;
-        t.atom = h.atom;
-        t.ltStart = h.ltStart;
+        t.row = ev[i].row;
+        t.atom = ev[i].atom;
+        t.ltStart = ev[i].ltStart;
         t.parOff = h.parOff;
         t.rhoOff = h.rhoOff >= 0 ? h.rhoOff + (int64_t)(h.ltStart - h.rhoLt0) * Ns : 0;
-        t.waveOff = h.waveOff >= 0 ? h.waveOff : 0;
-        t.lambda0 = h.t.lambda0;
+        t.waveOff = ev[i].waveOff;
+        t.lambda0 = ev[i].lambda0;
     }
     std::vector<int32_t> laOff, laTr;
     active_trans_lists(o->trans, o->Nla, true, laOff, laTr);
@@ -407,50 +453,6 @@ int rays_tables(lwhip_context* o, RaysState*& out)
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// Every refusal of a request, before anything is queued.  la0 / la1: the rows of the global grid.
-int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, int& la0, int& la1)
-{
-    if (!c)
-        return fail(LWHIP_ERR_INVALID, what + ": null context");
-    if (!r)
-        return fail(LWHIP_ERR_INVALID, what + ": null request");
-    if (c->is2d)
-        return fail(LWHIP_ERR_UNSUPPORTED, what + ": observer rays are 1D plane-parallel only");
-    if (c->hprd)
-        return fail(LWHIP_ERR_UNSUPPORTED, what + ": not with hybrid PRD tables (rho there is tied to the quadrature rays)");
-    if (c->prob.formalSolver != LWHIP_FS_BEZIER3_1D)
-        return fail(LWHIP_ERR_UNSUPPORTED, what + ": piecewise_bezier3_1d contexts only");
-    if (c->Ns < 3)
-        return fail(LWHIP_ERR_INVALID, what + ": needs at least 3 depth points");
-    if (c->Ns > RAYS_MAX_NS) // (lwhip_create admits no deeper 1D column: a guard for the LDS rows, should that change)
-        return fail(LWHIP_ERR_UNSUPPORTED, what + ": more than " + std::to_string((int)RAYS_MAX_NS) + " depth points");
-    if (r->Nmu < 1 || !r->muz || !r->I)
-        return fail(LWHIP_ERR_INVALID, what + ": Nmu >= 1, muz and I are required");
-    if (r->Nmu > LWHIP_RAYS_MAX_MU)
-        return fail(LWHIP_ERR_UNSUPPORTED, what + ": Nmu above LWHIP_RAYS_MAX_MU (" + std::to_string(LWHIP_RAYS_MAX_MU)
-                                               + " directions per call)");
-    for (int m = 0; m < r->Nmu; ++m)
-        if (!(r->muz[m] > 0.0 && r->muz[m] <= 1.0))
-            return fail(LWHIP_ERR_INVALID, what + ": direction cosine " + std::to_string(m) + " is outside (0, 1]");
-    la0 = (r->laStart == 0 && r->laEnd == 0) ? c->laStart : r->laStart;
-    la1 = (r->laEnd == 0) ? c->laEnd : r->laEnd;
-    if (la0 < c->laStart || la1 > c->laEnd || la1 <= la0)
-        return fail(LWHIP_ERR_INVALID, what + ": wavelength range [" + std::to_string(la0) + ", " + std::to_string(la1)
-                                           + ") is not inside the context's rows [" + std::to_string(c->laStart) + ", "
-                                           + std::to_string(c->laEnd) + ")");
-    if (c->prob.zLowerBc.type == LWHIP_BC_CALLABLE && !r->lowerBc)
-        return fail(LWHIP_ERR_INVALID, what + ": a CALLABLE lower boundary has no data for new directions (pass lowerBc [Nla, Nmu])");
-    const int nDepth = (r->depthChi ? 1 : 0) + (r->depthEta ? 1 : 0) + (r->depthI ? 1 : 0);
-    if (nDepth != 0 && nDepth != 3)
-        return fail(LWHIP_ERR_INVALID, what + ": depthChi, depthEta and depthI go together");
-    if (!r->vz && !c->prob.vlosMu)
-        return fail(LWHIP_ERR_INVALID, what + ": needs vz, or vlosMu in the descriptor");
-    for (const HostTrans& h : c->trans)
-        if (h.t.type == LWHIP_LINE && !h.t.aDamp)
-            return fail(LWHIP_ERR_INVALID, what + ": needs aDamp for every line (the profiles are evaluated in the kernel)");
-    return LWHIP_OK;
-}
-
 // The call: cols[i] with request reqs[i], everything on cols[0]'s stream, staged through `st`.
 int rays_run(lwhip_context* const* cols, int n, const lwhip_rays* reqs, RaysState*& slot, const char* whatC)
 {
@@ -463,7 +465,7 @@ int rays_run(lwhip_context* const* cols, int n, const lwhip_rays* reqs, RaysStat
     for (int i = 0; i < n; ++i)
     {
         int a0 = 0, a1 = 0;
-        const int chk = rays_check(cols[i], reqs + i, what, a0, a1);
+        const int chk = rays_check(cols[i], reqs + i, what, false, a0, a1);
         if (chk != LWHIP_OK)
             return n > 1 ? fail(chk, std::string(lwhip_last_error()) + " (column " + std::to_string(i) + ")") : chk;
         if (i == 0)

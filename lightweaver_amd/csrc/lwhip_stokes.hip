@@ -158,6 +158,17 @@ int lwhip_set_stokes(lwhip_context* c, const lwhip_stokes* st)
     HIP_TRY(s.laOff.upload(c->mem, laOff));
     HIP_TRY(s.laTr.upload(c->mem, laTr));
     HIP_TRY(s.laPol.upload(c->mem, laPol));
+    {
+        std::vector<int32_t> polComp(2 * std::max<size_t>(s.lines.size(), 1), 0);
+        for (size_t i = 0; i < s.lines.size(); ++i)
+        {
+            polComp[2 * i] = compOff[i];
+            polComp[2 * i + 1] = s.lines[i].Ncomp;
+        }
+        HIP_TRY(s.ev.upload(c->mem, line_eval_records(c->trans)));
+        HIP_TRY(s.polComp.upload(c->mem, polComp));
+        s.nComp = (int64_t)nComp;
+    }
     if (alpha.empty())
         alpha.push_back(0);
     HIP_TRY(s.alpha.upload(c->mem, alpha));

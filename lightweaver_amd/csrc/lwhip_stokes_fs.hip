@@ -1,11 +1,15 @@
 // lwhip_stokes_fs.hip -- the full-Stokes formal solution for Zeeman-polarised lines (1D plane-parallel): formal_sol_full_stokes
 // (Source/FormalStokes.cpp:166-723) of one context (lwhip_full_stokes_fs) or of every column of a 1.5D batch
-// (lwhip_batch_full_stokes_fs).  One driver, stokes_fs_run, serves both: a context on its own is a batch of one column.
+// (lwhip_batch_full_stokes_fs), and the emergent Stokes vector along observer rays (lwhip_compute_stokes_rays,
+// lwhip_batch_compute_stokes_rays).  One driver, stokes_fs_run, serves them all: a context on its own is a batch of one column,
+// and an observer call is a column whose argument block carries the request's directions and outputs.
 //
 // A chunk of (columns x wavelength range) runs as up to three launches on the first column's stream, each over ALL columns
 // of the chunk, the column outermost in the work index:
 //   stokes_gather_kernel  one workgroup per block of 64 rays: chi[7] and eta[4] of every depth point summed over the
 //                         transitions active at lambda (stokes_fs_core :496-602), stored as the rays' rows chi[0..6], S[0..3];
+//                         stokes_observer_gather_kernel is the same sum for the directions of an observer request, whose
+//                         profiles it forms in place (see "Observer rays" below);
 //   stokes_march_kernel   one lane per ray, one wavefront per block of 64 rays: the DELO-Bezier3 march of
 //                         piecewise_stokes_bezier3_1d_impl (:166-340) down the ray with a 4 x 4 Crout LU per depth point
 //                         (lwhip_lu.h), or the scalar piecewise_bezier3_1d (FormalScalar.cpp:209-325) where the wavelength
@@ -20,8 +24,22 @@
 // Scratch.  The rows of a chunk belong to the caller's slot (the context's, or the batch's) and are capped by the caller:
 // they do not grow with the number of columns.  A chunk takes as many whole columns as fit, or one column's wavelength
 // range when a single column does not fit.  The results are the same bits for any chunking (tested).
+//
+// Observer rays.  What LwContext.compute_rays(mus, stokes=True) (Source/LwMiddleLayer.pyx:3898-4002) computes: the result of
+// formal_sol_full_stokes(updateJ = 0, upOnly = 1) on a second context with the same state, rays muz = mus, vlosMu = mu (x) v_z,
+// wmu = 0, the field projected onto the new directions and the profiles of those directions.  Here no context is made and no
+// profile stored: the observer gather evaluates, per (ray, depth point, active line), phi = H(a, v) / (sqrt(pi) vBroad) of a
+// line that is not polarised (as rays_kernel does) or the Zeeman sum and projections of compute_polarised_profiles
+// (FormalStokes.cpp:43-110; d_polarised_profile) of a polarised one, and writes the row blocks the march reads.  The march is
+// stokes_march_kernel as it stands: it reaches everything through StokesArgs, and an observer column's StokesArgs has the
+// request's directions as muz, the identity as lowerIdx, the staged request data as lowerBc and the request's device output as
+// I / Quv.  As in the reference: no scattering term (J dagger = 0 without updateJ), exact zeros for Q, U, V where no polarised
+// line is active, and whatever 1D solver the context was built with.
 #include "lwhip_host.h"
 #include "lwhip_device.h"
+// H(a, v), H + iF and the Zeeman sum under the contraction setting of the stored profiles' unit (d_voigt_H: the compiler's
+// default; the other two carry their own `fp contract(off)`): the same arguments give the same bits
+#include "lwhip_voigt_dev.h"
 
 // As in lwhip_pops.hip: no fused multiply-adds, so that the operations match the reference's one for one.
 #pragma clang fp contract(off)
@@ -29,6 +47,7 @@
 #include "lwhip_lu.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -89,9 +108,89 @@ using RowOut = LaneRow<double>;
 
 DEVINL bool polarised_la(const StokesArgs& a, int la) { return a.laPol[la] != 0 || a.hasJ20; }
 
+// one column of an observer call: what forming the profiles of its directions takes (the rest is in its StokesArgs)
+struct ObsCol
+{
+    const LineEval* ev;      // per transition, indexed as StokesArgs::tr
+    const int32_t* polComp;  // per polarised line: offset of its Zeeman components in the three arrays below, their number
+    const int32_t* alpha;
+    const double* shift;
+    const double* strength;
+    const double* vBroad;
+    const double* aDamp;
+    const double* lineWave;
+    const double* B;
+    const double* vz;        // [Ns] staged, or null: vlosMu[0] / muz[0] of the resident atmosphere
+    const double* vlosMu;
+    const double* muzCtx;
+    const double* cosGamma;  // [Nmu, Ns] staged: the field projected onto the request's directions
+    const double* cos2chi;
+    const double* sin2chi;
+};
+
+// Where the gather takes the profiles of a line at a point from.  at(...) gives the point's phi(a, t) and, of a polarised
+// line, pol(a, t)[q]: phiQ, phiU, phiV, psiQ, psiU, psiV.
+// The context's own rays: the stored phi and phiQ..psiV.
+struct StoredProfiles
+{
+    struct Point
+    {
+        size_t pk = 0;
+        DEVINL double phi(const StokesArgs& a, const StokesTrans& t) const { return a.phi[t.phiOff + pk]; }
+        struct Pol
+        {
+            const double* P;
+            size_t s;
+            DEVINL double operator[](int q) const { return P[q * s]; }
+        };
+        DEVINL Pol pol(const StokesArgs& a, const StokesTrans& t) const { return Pol{ a.pol + t.polOff + pk, (size_t)t.polStride }; }
+    };
+    DEVINL Point at(const StokesArgs& a, const StokesTrans&, int, int lt, int mu, int d, int k) const
+    {
+        return Point{ (((size_t)lt * a.Nr + mu) * 2 + d) * a.Ns + k };
+    }
+};
+// The directions of an observer request (up-going: s = +1): formed here, never stored.  phi of a line that is not polarised
+// as voigt_phi_kernel / rays_kernel form it, the seven profiles of a polarised one as polarised_profile_kernel does.
+struct ObserverProfiles
+{
+    const ObsCol o;
+    struct Point
+    {
+        double ph = 0.0, p[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+        DEVINL double phi(const StokesArgs&, const StokesTrans&) const { return ph; }
+        DEVINL const double* pol(const StokesArgs&, const StokesTrans&) const { return p; }
+    };
+    DEVINL Point at(const StokesArgs& a, const StokesTrans& t, int tr, int lt, int mu, int, int k) const
+    {
+        const double sqrtPi = 1.772453850905516027298167483341145182798;
+        const int Ns = a.Ns;
+        const LineEval e = o.ev[tr];
+        const double vb = o.vBroad[(size_t)e.atom * Ns + k];
+        const double ad = o.aDamp[(size_t)e.row * Ns + k];
+        const double vBase = (o.lineWave[e.waveOff + lt] - e.lambda0) * CLight / e.lambda0;
+        const double vz = o.vz ? o.vz[k] : o.vlosMu[k] / o.muzCtx[0];
+        const double vk = (vBase + a.muz[mu] * vz) / vb;
+        Point pt;
+        if (t.pol < 0)
+        {
+            pt.ph = d_voigt_H(ad, vk) / (sqrtPi * vb);
+            return pt;
+        }
+        const double larmor = 1.60217733E-19 / (4.0 * Pi * 9.1093897E-31) * (e.lambda0 * NM_TO_M); // QElectron, MElectron
+        const double vB = larmor * o.B[k] / vb;
+        const double sv = 1.0 / (sqrtPi * vb);
+        const int c0 = o.polComp[2 * t.pol], nComp = o.polComp[2 * t.pol + 1];
+        const size_t mk = (size_t)mu * Ns + k;
+        d_polarised_profile(ad, vk, vB, nComp, o.alpha + c0, o.shift + c0, o.strength + c0, o.cosGamma, o.cos2chi, o.sin2chi, mk, sv,
+                            1.0, &pt.ph, pt.p, 1, 0);
+        return pt;
+    }
+};
+
 // chi[7] and eta[4] of (la, mu, d) at depth k summed over the transitions active at la (stokes_fs_core :496-602), stored as
-// the ray's rows chi[0..6], S[0..3]: row[m * Ns] is row m at this depth
-DEVINL void stokes_gather_point(const StokesArgs& a, int la, int mu, int d, int k, RowOut row)
+// the ray's rows chi[0..6], S[0..3]: row[m * Ns] is row m at this depth.  prof: where the lines' profiles come from.
+template <typename Prof> DEVINL void stokes_gather_point(const StokesArgs& a, const Prof& prof, int la, int mu, int d, int k, RowOut row)
 {
     const int Ns = a.Ns;
     const double inv2root2 = 1.0 / (2.0 * sqrt(2.0));
@@ -100,16 +199,17 @@ DEVINL void stokes_gather_point(const StokesArgs& a, int la, int mu, int d, int 
     double eta[4] = { 0.0, 0.0, 0.0, 0.0 };
     for (int q = a.laOff[la]; q < a.laOff[la + 1]; ++q)
     {
-        const StokesTrans t = a.tr[a.laTr[q]];
+        const int tr = a.laTr[q];
+        const StokesTrans t = a.tr[tr];
         const int lt = la - t.Nblue;
         const double* p = a.par + t.parOff + 4 * (size_t)lt;
         double Vij, Vji, Uji;
-        size_t pk = 0;
+        typename Prof::Point pt;
         if (t.type == LWHIP_LINE)
         {
             // Transition::uv (LwTransition.hpp:98-127) with gij of Atom::setup_wavelength (LwAtom.hpp:99-123)
-            pk = (((size_t)lt * a.Nr + mu) * 2 + d) * Ns + k;
-            Vij = p[0] * a.phi[t.phiOff + pk];
+            pt = prof.at(a, t, tr, lt, mu, d, k);
+            Vij = p[0] * pt.phi(a, t);
             double g = p[2];
             if (t.prd)
                 g *= a.rho[t.rhoOff + (size_t)lt * Ns + k];
@@ -132,20 +232,19 @@ DEVINL void stokes_gather_point(const StokesArgs& a, int la, int mu, int d, int 
         if (t.pol >= 0)
         {
             // :515-531.  chiNoProfile = chi / phi is kept as a division, as the reference writes it.
-            const double* P = a.pol + t.polOff + pk;
-            const size_t s = (size_t)t.polStride;
-            const double ph = a.phi[t.phiOff + pk];
+            const auto P = pt.pol(a, t);
+            const double ph = pt.phi(a, t);
             const double cnp = c / ph;
             chi[1] += cnp * P[0];
-            chi[2] += cnp * P[s];
-            chi[3] += cnp * P[2 * s];
-            chi[4] += cnp * P[3 * s];
-            chi[5] += cnp * P[4 * s];
-            chi[6] += cnp * P[5 * s];
+            chi[2] += cnp * P[1];
+            chi[3] += cnp * P[2];
+            chi[4] += cnp * P[3];
+            chi[5] += cnp * P[4];
+            chi[6] += cnp * P[5];
             const double enp = e / ph;
             eta[1] += enp * P[0];
-            eta[2] += enp * P[s];
-            eta[3] += enp * P[2 * s];
+            eta[2] += enp * P[1];
+            eta[3] += enp * P[2];
         }
     }
     const size_t lk = (size_t)la * Ns + k;
@@ -586,7 +685,27 @@ __global__ void __launch_bounds__(256) stokes_gather_kernel(const StokesChunk b)
     const int Ns = b.Ns;
     double* base = b.scratch + (size_t)blk * ST_ROWS * Ns * SB_LANES + lane;
     for (int k = threadIdx.x / SB_LANES; k < Ns; k += blockDim.x / SB_LANES)
-        stokes_gather_point(a, la, mu, d, k, RowOut{ base + (size_t)k * SB_LANES });
+        stokes_gather_point(a, StoredProfiles{}, la, mu, d, k, RowOut{ base + (size_t)k * SB_LANES });
+}
+// The observer gather: the same rows, in the same layout, for the rays (lambda, m) of an observer request, the profiles formed
+// in place; obs: [n] the columns' observer blocks, indexed as b.cols.  Lanes are rays as above, so neighbouring lanes sit at
+// different wavelengths and diverge inside the Faddeeva algorithm ("Full-Stokes observer rays").
+__global__ void __launch_bounds__(256) stokes_observer_gather_kernel(const StokesChunk b, const ObsCol* __restrict__ obs)
+{
+    const int blk = blockIdx.x;
+    const int lane = threadIdx.x % SB_LANES;
+    const int col = b.col0 + blk / b.blocksPerCol;
+    const StokesArgs a = b.cols[col];
+    const int r = (blk % b.blocksPerCol) * SB_LANES + lane;
+    if (r >= b.nla * b.Nr * b.nDir)
+        return;
+    int la, mu, d;
+    chunk_ray(b, r, la, mu, d);
+    const int Ns = b.Ns;
+    const ObserverProfiles prof{ obs[col] };
+    double* base = b.scratch + (size_t)blk * ST_ROWS * Ns * SB_LANES + lane;
+    for (int k = threadIdx.x / SB_LANES; k < Ns; k += blockDim.x / SB_LANES)
+        stokes_gather_point(a, prof, la, mu, d, k, RowOut{ base + (size_t)k * SB_LANES });
 }
 
 // one wavefront per block of 64 rays, a lane per ray.  One wavefront per SIMD: held to two (256 registers) the march spills
@@ -633,12 +752,20 @@ struct StokesBatch
     DevBuf<double> scratch, Isc; // one chunk's rows and I / Q profiles
     DevBuf<double> tail;         // [n][Nla] dJ of every column, then n int32 singular flags
     PinnedBlock tailPinned;
+    // observer rays: the staged request [args | observer blocks | per column: muz, projections, v_z, lowerBc, lowerIdx] and
+    // its results [per column: I, Quv | flags]
+    DevBuf<unsigned char> obsIn, obsOut;
+    PinnedBlock obsInPinned, obsOutPinned;
 };
 
 void stokes_batch_release(StokesBatch* s)
 {
     if (s)
+    {
         s->tailPinned.release();
+        s->obsInPinned.release();
+        s->obsOutPinned.release();
+    }
     delete s;
 }
 
@@ -704,51 +831,23 @@ void stokes_max_idx(const double* dJ, int Nla, lwhip_iter_result& r)
     r.dJMaxIdx = maxIdx;
 }
 
-// The call: the n columns `cols` (of batch `b`, or one context on its own: b null), everything on cols[0]'s stream, the
-// scratch in `slot` and at most capBytes of it.  The columns have passed check_stokes_ctx / check_stokes_batch.
-int stokes_fs_run(lwhip_context* const* cols, int n, lwhip_batch* b, int updateJ, int upOnly, lwhip_iter_result* results,
-                  StokesBatch*& slot, size_t capBytes, const char* whatC)
+// One call of the driver: n columns whose argument blocks are on the device, the wavelengths [la0, la1) of their grid, Nr rays
+// per wavelength.  obs: the columns' observer blocks (the observer gather forms the profiles), or null (the stored profiles).
+struct StokesCall
 {
-    const std::string what(whatC);
-    auto column = [&](const char* pre, int i) { return n > 1 ? pre + std::to_string(i) : std::string(); };
-    for (int i = 0; i < n; ++i)
-        if (updateJ && cols[i]->JhostReg)
-            return fail(LWHIP_ERR_UNSUPPORTED, what + ": updateJ with a mapped host J" + column(" in column ", i)
-                                                   + " (lwhip_map_host_J(ctx, 0) first)");
-    lwhip_context* c0 = cols[0];
-    if (c0->Ns < 3)
-        return fail(LWHIP_ERR_INVALID, what + ": needs at least 3 depth points");
-    HIP_TRY(hipSetDevice(c0->device));
-    {
-        const int stp = b ? batch_ensure_profiles(b) : ensure_profiles(c0);
-        if (stp != LWHIP_OK)
-            return stp;
-    }
-    if (!slot)
-        slot = new StokesBatch();
-    StokesBatch& sb = *slot;
-    const int Ns = c0->Ns, Nr = c0->Nrays, Nla = c0->Nla;
-    const int nDir = upOnly ? 1 : 2;
-    const size_t tailN = (size_t)n * Nla + (n + 1) / 2; // the dJ rows, then the flags
-    if (sb.tail.n < tailN)
-    {
-        HIP_TRY(hipStreamSynchronize(c0->stream));
-        HIP_TRY(sb.tail.alloc(c0->mem, tailN));
-        HIP_TRY(sb.tailPinned.reserve(c0->device, tailN * sizeof(double), c0->stream));
-    }
-    int32_t* flags = (int32_t*)(sb.tail.p + (size_t)n * Nla);
-    // the columns' argument blocks (uploaded again only when one of them changed)
-    std::vector<StokesArgs> args(n);
-    for (int i = 0; i < n; ++i)
-        args[i] = stokes_args(cols[i], updateJ, sb.tail.p + (size_t)i * Nla, flags + i);
-    if (sb.argsHost.size() != args.size() || std::memcmp(sb.argsHost.data(), args.data(), args.size() * sizeof(StokesArgs)) != 0)
-    {
-        HIP_TRY(hipStreamSynchronize(c0->stream)); // (nothing queued may still read the blocks about to be replaced)
-        sb.argsHost = args;
-        if (sb.args.n < (size_t)n)
-            HIP_TRY(sb.args.alloc(c0->mem, (size_t)n, false));
-        HIP_TRY(hipMemcpyAsync(sb.args.p, sb.argsHost.data(), (size_t)n * sizeof(StokesArgs), hipMemcpyHostToDevice, c0->stream));
-    }
+    const StokesArgs* args; // device [n]
+    const ObsCol* obs;      // device [n], or null
+    int32_t* flags;         // device [n]: set where a 4 x 4 system is singular; cleared here
+    int n, Ns, Nr, la0, la1, updateJ, upOnly;
+};
+
+// The driver of every full-Stokes formal solution: everything queued on c0's stream, the rows in `sb` and at most capBytes of
+// them.  Nothing is waited for unless the scratch has to grow; the caller copies its results back.
+int stokes_fs_run(lwhip_context* c0, StokesBatch& sb, const StokesCall& call, size_t capBytes)
+{
+    const int n = call.n, Ns = call.Ns, Nr = call.Nr, updateJ = call.updateJ;
+    const int Nla = call.la1 - call.la0;
+    const int nDir = call.upOnly ? 1 : 2;
     // chunks of (columns x wavelength range) whose rows stay within the cap.  Two debug knobs (LWHIP_DEBUG) make small chunks
     // for the tests: LWHIP_STOKES_BATCH_RAYS caps the rays of a chunk instead, LWHIP_STOKES_CHUNK_LA caps its wavelengths
     const size_t rowsPerRay = (size_t)ST_ROWS + (updateJ ? 2 : 0);
@@ -773,31 +872,106 @@ int stokes_fs_run(lwhip_context* const* cols, int n, lwhip_batch* b, int updateJ
         if (updateJ && sb.Isc.n < blocksMax * 2 * Ns * SB_LANES)
             HIP_TRY(sb.Isc.alloc(c0->mem, blocksMax * 2 * Ns * SB_LANES, false));
     }
-    HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n * sizeof(int32_t), c0->stream));
+    HIP_TRY(hipMemsetAsync(call.flags, 0, (size_t)n * sizeof(int32_t), c0->stream));
     StokesChunk ch{};
-    ch.cols = sb.args.p;
+    ch.cols = call.args;
     ch.nDir = nDir;
-    ch.dir0 = upOnly ? 1 : 0;
+    ch.dir0 = call.upOnly ? 1 : 0;
     ch.Ns = Ns;
     ch.Nr = Nr;
     ch.updateJ = updateJ ? 1 : 0;
     ch.scratch = sb.scratch.p;
     ch.Isc = sb.Isc.p;
     for (int col0 = 0; col0 < n; col0 += colsChunk)
-        for (int la0 = 0; la0 < Nla; la0 += nlaChunk)
+        for (int la0 = call.la0; la0 < call.la1; la0 += nlaChunk)
         {
             ch.col0 = col0;
             ch.ncol = std::min(colsChunk, n - col0);
             ch.la0 = la0;
-            ch.nla = std::min(nlaChunk, Nla - la0);
+            ch.nla = std::min(nlaChunk, call.la1 - la0);
             ch.blocksPerCol = (int)((ch.nla * raysPerLa + SB_LANES - 1) / SB_LANES);
             const unsigned nBlk = (unsigned)ch.ncol * ch.blocksPerCol;
-            LWHIP_LAUNCH(stokes_gather_kernel, dim3(nBlk), dim3(256), 0, c0->stream, ch);
+            if (call.obs)
+                LWHIP_LAUNCH(stokes_observer_gather_kernel, dim3(nBlk), dim3(256), 0, c0->stream, ch, call.obs);
+            else
+                LWHIP_LAUNCH(stokes_gather_kernel, dim3(nBlk), dim3(256), 0, c0->stream, ch);
             LWHIP_LAUNCH(stokes_march_kernel, dim3(nBlk), dim3(SB_LANES), 0, c0->stream, ch);
             if (updateJ)
                 LWHIP_LAUNCH(stokes_j_kernel, dim3((ch.nla + 63) / 64, ch.ncol), dim3(64), 0, c0->stream, ch);
             HIP_TRY(hipGetLastError());
         }
+    return LWHIP_OK;
+}
+
+// solve_lin_eq throws on a singular system (LuSolve.cpp:22-23): the first column whose flag is set
+int stokes_singular(const int32_t* sing, int n, const std::string& what)
+{
+    for (int i = 0; i < n; ++i)
+        if (sing[i])
+            return fail(LWHIP_ERR_SINGULAR, what + ": Singular Matrix in the 4 x 4 DELO-Bezier3 step"
+                                                + (n > 1 ? " of column " + std::to_string(i) : std::string()));
+    return LWHIP_OK;
+}
+
+// formal_sol_full_stokes of the n columns `cols` (of batch `b`, or one context on its own: b null) on their own rays.  The
+// columns have passed check_stokes_ctx / check_stokes_batch.
+int stokes_fs_solve(lwhip_context* const* cols, int n, lwhip_batch* b, int updateJ, int upOnly, lwhip_iter_result* results,
+                    StokesBatch*& slot, size_t capBytes, const char* whatC)
+{
+    const std::string what(whatC);
+    auto column = [&](const char* pre, int i) { return n > 1 ? pre + std::to_string(i) : std::string(); };
+    for (int i = 0; i < n; ++i)
+        if (updateJ && cols[i]->JhostReg)
+            return fail(LWHIP_ERR_UNSUPPORTED, what + ": updateJ with a mapped host J" + column(" in column ", i)
+                                                   + " (lwhip_map_host_J(ctx, 0) first)");
+    lwhip_context* c0 = cols[0];
+    if (c0->Ns < 3)
+        return fail(LWHIP_ERR_INVALID, what + ": needs at least 3 depth points");
+    HIP_TRY(hipSetDevice(c0->device));
+    {
+        const int stp = b ? batch_ensure_profiles(b) : ensure_profiles(c0);
+        if (stp != LWHIP_OK)
+            return stp;
+    }
+    if (!slot)
+        slot = new StokesBatch();
+    StokesBatch& sb = *slot;
+    const int Nla = c0->Nla;
+    const size_t tailN = (size_t)n * Nla + (n + 1) / 2; // the dJ rows, then the flags
+    if (sb.tail.n < tailN)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        HIP_TRY(sb.tail.alloc(c0->mem, tailN));
+        HIP_TRY(sb.tailPinned.reserve(c0->device, tailN * sizeof(double), c0->stream));
+    }
+    int32_t* flags = (int32_t*)(sb.tail.p + (size_t)n * Nla);
+    // the columns' argument blocks (uploaded again only when one of them changed)
+    std::vector<StokesArgs> args(n);
+    for (int i = 0; i < n; ++i)
+        args[i] = stokes_args(cols[i], updateJ, sb.tail.p + (size_t)i * Nla, flags + i);
+    if (sb.argsHost.size() != args.size() || std::memcmp(sb.argsHost.data(), args.data(), args.size() * sizeof(StokesArgs)) != 0)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream)); // (nothing queued may still read the blocks about to be replaced)
+        sb.argsHost = args;
+        if (sb.args.n < (size_t)n)
+            HIP_TRY(sb.args.alloc(c0->mem, (size_t)n, false));
+        HIP_TRY(hipMemcpyAsync(sb.args.p, sb.argsHost.data(), (size_t)n * sizeof(StokesArgs), hipMemcpyHostToDevice, c0->stream));
+    }
+    StokesCall call{};
+    call.args = sb.args.p;
+    call.flags = flags;
+    call.n = n;
+    call.Ns = c0->Ns;
+    call.Nr = c0->Nrays;
+    call.la0 = 0;
+    call.la1 = Nla;
+    call.updateJ = updateJ ? 1 : 0;
+    call.upOnly = upOnly ? 1 : 0;
+    {
+        const int stp = stokes_fs_run(c0, sb, call, capBytes);
+        if (stp != LWHIP_OK)
+            return stp;
+    }
     if (updateJ)
         for (int i = 0; i < n; ++i)
             cols[i]->fpJValid = false;
@@ -807,7 +981,6 @@ int stokes_fs_run(lwhip_context* const* cols, int n, lwhip_batch* b, int updateJ
                            c0->stream));
     HIP_TRY(hipStreamSynchronize(c0->stream));
     const double* dJ = sb.tailPinned.as<double>();
-    const int32_t* sing = (const int32_t*)(dJ + (size_t)n * Nla);
     for (int i = 0; i < n && results; ++i)
     {
         results[i].updatedJ = updateJ ? 1 : 0;
@@ -816,10 +989,188 @@ int stokes_fs_run(lwhip_context* const* cols, int n, lwhip_batch* b, int updateJ
         if (updateJ)
             stokes_max_idx(dJ + (size_t)i * Nla, Nla, results[i]);
     }
+    return stokes_singular((const int32_t*)(dJ + (size_t)n * Nla), n, what);
+}
+
+hipError_t stokes_init_voigt_table(int device)
+{
+    // (this unit's copy of the table of lwhip_voigt_dev.h, as rays_init_table)
+    static std::atomic<bool> done[64];
+    if (device >= 0 && device < 64 && done[device].load())
+        return hipSuccess;
+    const hipError_t e = voigt_fill_table();
+    if (e == hipSuccess && device >= 0 && device < 64)
+        done[device].store(true);
+    return e;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Observer rays: cols[i] (which have passed check_stokes_ctx / check_stokes_batch) with request reqs[i].  Every other refusal
+// comes first; then the request is staged as rays_run stages its own -- one pinned block [args | observer blocks | per column:
+// muz, projections, v_z, lowerBc, lowerIdx], one copy up -- the driver runs with the observer gather, and I, Quv and the
+// singular flags come back in one copy, after one wait.  The argument blocks that stokes_fs_solve keeps are not touched.
+int stokes_rays_solve(lwhip_context* const* cols, int n, const lwhip_stokes_rays* reqs, StokesBatch*& slot, size_t capBytes,
+                      const char* whatC)
+{
+    const std::string what(whatC);
+    if (!reqs)
+        return fail(LWHIP_ERR_INVALID, what + ": null request");
+    int la0 = 0, la1 = 0;
     for (int i = 0; i < n; ++i)
-        if (sing[i])
-            return fail(LWHIP_ERR_SINGULAR, what + ": Singular Matrix in the 4 x 4 DELO-Bezier3 step" + column(" of column ", i));
-    return LWHIP_OK;
+    {
+        const std::string col = n > 1 ? " (column " + std::to_string(i) + ")" : std::string();
+        int a0 = 0, a1 = 0;
+        const int chk = rays_check(cols[i], &reqs[i].rays, what, true, a0, a1);
+        if (chk != LWHIP_OK)
+            return n > 1 ? fail(chk, std::string(lwhip_last_error()) + col) : chk;
+        const lwhip_stokes_rays& q = reqs[i];
+        if (!q.cosGamma || !q.cos2chi || !q.sin2chi)
+            return fail(LWHIP_ERR_INVALID, what + ": cosGamma, cos2chi and sin2chi [Nmu, Nspace] of the new directions are required" + col);
+        if (!q.Quv)
+            return fail(LWHIP_ERR_INVALID, what + ": Quv [3, Nla, Nmu] is required" + col);
+        if (q.rays.depthChi || q.rays.depthEta || q.rays.depthI)
+            return fail(LWHIP_ERR_INVALID, what + ": no depth output of the Stokes vector (depthChi, depthEta and depthI must be NULL)" + col);
+        if (!cols[i]->lineWave.p)
+            return fail(LWHIP_ERR_INVALID, what + ": the context has no line grids on the device" + col);
+        if (i == 0)
+        {
+            la0 = a0;
+            la1 = a1;
+        }
+        if (cols[i]->Ns != cols[0]->Ns || cols[i]->device != cols[0]->device || q.rays.Nmu != reqs[0].rays.Nmu || a0 != la0 || a1 != la1)
+            return fail(LWHIP_ERR_INVALID, what + ": column " + std::to_string(i)
+                                               + " differs from column 0 (depth points, Nmu and wavelength range are the same for "
+                                                 "every column)");
+    }
+    lwhip_context* c0 = cols[0];
+    const int Ns = c0->Ns, Nmu = reqs[0].rays.Nmu, nla = la1 - la0;
+    HIP_TRY(hipSetDevice(c0->device));
+    HIP_TRY(stokes_init_voigt_table(c0->device));
+    if (!slot)
+        slot = new StokesBatch();
+    StokesBatch& sb = *slot;
+    // ---- the staged request ------------------------------------------------------------------------------------------------
+    const size_t nRayCol = (size_t)nla * Nmu;
+    const size_t argsBytes = align256((size_t)n * sizeof(StokesArgs)), obsBytes = align256((size_t)n * sizeof(ObsCol));
+    const size_t muBytes = align256((size_t)Nmu * sizeof(double)), projBytes = align256((size_t)3 * Nmu * Ns * sizeof(double));
+    const size_t vzBytes = align256((size_t)Ns * sizeof(double)), bcBytes = align256(nRayCol * sizeof(double));
+    const size_t idxBytes = align256((size_t)2 * Nmu * sizeof(int32_t));
+    std::vector<size_t> colOff(n);
+    size_t inBytes = argsBytes + obsBytes;
+    for (int i = 0; i < n; ++i)
+    {
+        colOff[i] = inBytes;
+        inBytes += muBytes + projBytes + (reqs[i].rays.vz ? vzBytes : 0);
+        if (cols[i]->prob.zLowerBc.type == LWHIP_BC_CALLABLE)
+            inBytes += bcBytes + idxBytes;
+    }
+    // out: per column I [nla, Nmu] and Quv [3, nla, Nmu], then the n flags
+    const size_t perColOut = 4 * nRayCol * sizeof(double);
+    const size_t outBytes = (size_t)n * perColOut + (size_t)n * sizeof(int32_t);
+    if (sb.obsIn.n < inBytes || sb.obsOut.n < outBytes)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        if (sb.obsIn.n < inBytes)
+            HIP_TRY(sb.obsIn.alloc(c0->mem, inBytes, false));
+        if (sb.obsOut.n < outBytes)
+            HIP_TRY(sb.obsOut.alloc(c0->mem, outBytes, false));
+    }
+    HIP_TRY(sb.obsInPinned.reserve(c0->device, inBytes, c0->stream));
+    HIP_TRY(sb.obsOutPinned.reserve(c0->device, outBytes, c0->stream));
+    unsigned char* hin = sb.obsInPinned.as<unsigned char>();
+    unsigned char* din = sb.obsIn.p;
+    StokesArgs* ha = (StokesArgs*)hin;
+    ObsCol* ho = (ObsCol*)(hin + argsBytes);
+    int32_t* flags = (int32_t*)(sb.obsOut.p + (size_t)n * perColOut);
+    for (int i = 0; i < n; ++i)
+    {
+        lwhip_context* c = cols[i];
+        const lwhip_stokes_rays& q = reqs[i];
+        const StokesState& st = c->stokes;
+        size_t off = colOff[i];
+        auto stage = [&](const void* src, size_t bytes, size_t padded) {
+            std::memcpy(hin + off, src, bytes);
+            const unsigned char* dev = din + off;
+            off += padded;
+            return dev;
+        };
+        // the column as the march sees it: the context's state, the request's directions, boundary data and outputs.  Rows
+        // are addressed by the context's la, so the request's arrays are taken as if they began at row 0
+        StokesArgs a = stokes_args(c, 0, nullptr, flags + i);
+        const ptrdiff_t rowShift = (ptrdiff_t)la0 * Nmu;
+        a.Nr = Nmu;
+        a.Nla = nla;
+        a.muz = (const double*)stage(q.rays.muz, (size_t)Nmu * sizeof(double), muBytes);
+        a.wmu = nullptr;
+        ObsCol o{};
+        o.cosGamma = (const double*)(din + off);
+        o.cos2chi = o.cosGamma + (size_t)Nmu * Ns;
+        o.sin2chi = o.cos2chi + (size_t)Nmu * Ns;
+        std::memcpy(hin + off, q.cosGamma, (size_t)Nmu * Ns * sizeof(double));
+        std::memcpy(hin + off + (size_t)Nmu * Ns * sizeof(double), q.cos2chi, (size_t)Nmu * Ns * sizeof(double));
+        std::memcpy(hin + off + (size_t)2 * Nmu * Ns * sizeof(double), q.sin2chi, (size_t)Nmu * Ns * sizeof(double));
+        off += projBytes;
+        if (q.rays.vz)
+            o.vz = (const double*)stage(q.rays.vz, (size_t)Ns * sizeof(double), vzBytes);
+        if (a.lowerType == LWHIP_BC_CALLABLE)
+        {
+            a.lowerBc = (const double*)stage(q.rays.lowerBc, nRayCol * sizeof(double), bcBytes) - rowShift;
+            int32_t* idx = (int32_t*)(hin + off);
+            for (int m = 0; m < Nmu; ++m)
+            {
+                idx[2 * m] = -1;
+                idx[2 * m + 1] = m;
+            }
+            a.lowerIdx = (const int32_t*)(din + off);
+            off += idxBytes;
+            a.lowerNmu = Nmu;
+        }
+        double* out = (double*)(sb.obsOut.p + (size_t)i * perColOut);
+        a.I = out - rowShift;
+        a.Quv = out + nRayCol - rowShift;
+        ha[i] = a;
+        o.ev = st.ev.p;
+        o.polComp = st.polComp.p;
+        o.alpha = st.alpha.p;
+        o.shift = st.comp.p;
+        o.strength = st.comp.p + st.nComp;
+        o.vBroad = c->vBroad.p;
+        o.aDamp = c->aDamp.p;
+        o.lineWave = c->lineWave.p;
+        o.B = st.B.p;
+        o.vlosMu = c->vlosMu.p;
+        o.muzCtx = c->muz.p;
+        ho[i] = o;
+    }
+    HIP_TRY(c0->mem.h2d(din, hin, inBytes));
+    StokesCall call{};
+    call.args = (const StokesArgs*)din;
+    call.obs = (const ObsCol*)(din + argsBytes);
+    call.flags = flags;
+    call.n = n;
+    call.Ns = Ns;
+    call.Nr = Nmu;
+    call.la0 = la0;
+    call.la1 = la1;
+    call.updateJ = 0;
+    call.upOnly = 1;
+    {
+        const int stp = stokes_fs_run(c0, sb, call, capBytes);
+        if (stp != LWHIP_OK)
+            return stp;
+    }
+    // ---- one copy back, one wait ---------------------------------------------------------------------------------------------
+    unsigned char* hout = sb.obsOutPinned.as<unsigned char>();
+    HIP_TRY(hipMemcpyAsync(hout, sb.obsOut.p, outBytes, hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    for (int i = 0; i < n; ++i)
+    {
+        const double* o = (const double*)(hout + (size_t)i * perColOut);
+        std::memcpy(reqs[i].rays.I, o, nRayCol * sizeof(double));
+        std::memcpy(reqs[i].Quv, o + nRayCol, 3 * nRayCol * sizeof(double));
+    }
+    return stokes_singular((const int32_t*)(hout + (size_t)n * perColOut), n, what);
 }
 } // namespace
 } // namespace lwhip
@@ -833,7 +1184,7 @@ int lwhip_full_stokes_fs(lwhip_context* c, int updateJ, int upOnly, lwhip_iter_r
     if (chk != LWHIP_OK)
         return chk;
     lwhip_context* cols[1] = { c };
-    return stokes_fs_run(cols, 1, nullptr, updateJ, upOnly, res, c->stokesFs, (size_t)256 << 20, what);
+    return stokes_fs_solve(cols, 1, nullptr, updateJ, upOnly, res, c->stokesFs, (size_t)256 << 20, what);
 }
 
 int lwhip_batch_full_stokes_fs(lwhip_batch* b, int updateJ, int upOnly, lwhip_iter_result* results)
@@ -842,6 +1193,25 @@ int lwhip_batch_full_stokes_fs(lwhip_batch* b, int updateJ, int upOnly, lwhip_it
     const int chk = check_stokes_batch(b, what);
     if (chk != LWHIP_OK)
         return chk;
-    return stokes_fs_run(b->ctxs.data(), (int)b->ctxs.size(), b, updateJ, upOnly, results, b->stokes, (size_t)1 << 30, what);
+    return stokes_fs_solve(b->ctxs.data(), (int)b->ctxs.size(), b, updateJ, upOnly, results, b->stokes, (size_t)1 << 30, what);
+}
+
+int lwhip_compute_stokes_rays(lwhip_context* c, const lwhip_stokes_rays* rays)
+{
+    const char* what = "lwhip_compute_stokes_rays";
+    const int chk = check_stokes_ctx(c, what, true);
+    if (chk != LWHIP_OK)
+        return chk;
+    lwhip_context* cols[1] = { c };
+    return stokes_rays_solve(cols, 1, rays, c->stokesFs, (size_t)256 << 20, what);
+}
+
+int lwhip_batch_compute_stokes_rays(lwhip_batch* b, const lwhip_stokes_rays* perColumn)
+{
+    const char* what = "lwhip_batch_compute_stokes_rays";
+    const int chk = check_stokes_batch(b, what);
+    if (chk != LWHIP_OK)
+        return chk;
+    return stokes_rays_solve(b->ctxs.data(), (int)b->ctxs.size(), perColumn, b->stokes, (size_t)1 << 30, what);
 }
 }

@@ -39,181 +39,12 @@
 
 #include <cmath>
 
-// d_voigt_H and its table (shared with the observer rays, lwhip_rays.hip); this unit owns them
+// d_voigt_H, d_voigt_HF and their table (shared with the observer rays: lwhip_rays.hip, lwhip_stokes_fs.hip); this unit owns them
 #define LWHIP_VOIGT_LINKAGE
 #include "lwhip_voigt_dev.h"
 
 namespace lwhip
 {
-// The complex w(v + i av) = H + i F of voigt_HF (Source/LwMisc.hpp:21-27), the same restatement of Faddeeva.cc's w(z) as
-// d_voigt_H above, branch for branch, keeping the imaginary part as well (d_voigt_H is left as it is: the unpolarised
-// profiles keep their bits).  The damping parameter is never negative here, so the y < 0 continuations of Faddeeva.cc are
-// not restated.  At av == 0 the reference takes Im w from its Dawson-function table (w_im); here the general branches
-// below give it (Algorithm 916 and the continued fraction hold on the real axis too), and Re w is exp(-v^2) as there.
-__device__ __forceinline__ void d_voigt_HF(double av, double v, double& H, double& F)
-{
-    // (no fused multiply-adds: the dispersion profile F falls off as 1 / v against H's a / v^2, so in the far wings its
-    // rounding shows relative to phi; unfused, the operations are the reference's one for one)
-#pragma clang fp contract(off)
-    const double a = 0.518321480430085929872;
-    const double c = 0.329973702884629072537;
-    const double a2 = 0.268657157075235951582;
-    const double relerr = 2.2204460492503131e-16;
-    const double x = fabs(v);
-    const double y = av, ya = fabs(av);
-    if (v == 0.0)
-    {
-        H = erfcx(y);
-        F = v;
-        return;
-    }
-    double retR = 0.0, retI = 0.0;
-    double sum1 = 0, sum2 = 0, sum3 = 0, sum4 = 0, sum5 = 0;
-    if (ya > 7 || (x > 6 && (ya > 0.1 || (x > 8 && ya > 1e-10) || x > 28)))
-    {
-        // continued fraction / asymptotic expansions: w(z) returned as it stands
-        const double ispi = 0.56418958354775628694807945156;
-        const double xs = v;
-        if (x + ya > 4000)
-        {
-            if (x + ya > 1e7)
-            {
-                if (x > ya)
-                {
-                    const double yax = ya / xs;
-                    const double denom = ispi / (xs + yax * ya);
-                    H = denom * yax;
-                    F = denom;
-                    return;
-                }
-                const double xya = xs / ya;
-                const double denom = ispi / (xya * xs + ya);
-                H = denom;
-                F = denom * xya;
-                return;
-            }
-            const double dr = xs * xs - ya * ya - 0.5, di = 2 * xs * ya;
-            const double denom = ispi / (dr * dr + di * di);
-            H = denom * (xs * di - ya * dr);
-            F = denom * (xs * dr + ya * di);
-            return;
-        }
-        const double c0 = 3.9, c1 = 11.398, c2 = 0.08254, c3 = 0.1421, c4 = 0.2023;
-        double nu = floor(c0 + c1 / (c2 * x + c3 * ya + c4));
-        double wr = xs, wi = ya;
-        for (nu = 0.5 * (nu - 1); nu > 0.4; nu -= 0.5)
-        {
-            const double denom = nu / (wr * wr + wi * wi);
-            wr = xs - wr * denom;
-            wi = ya + wi * denom;
-        }
-        const double denom = ispi / (wr * wr + wi * wi);
-        H = denom * wi;
-        F = denom * wr;
-        return;
-    }
-    else if (x < 10)
-    {
-        double prod2ax = 1, prodm2ax = 1;
-        double expx2;
-        if (x < 5e-4)
-        {
-            // sum4 and sum5 together as sum5 - sum4
-            const double x2 = x * x;
-            expx2 = 1 - x2 * (1 - 0.5 * x2);
-            const double ax2 = 1.036642960860171859744 * x;
-            const double exp2ax = 1 + ax2 * (1 + ax2 * (0.5 + 0.166666666666666666667 * ax2));
-            const double expm2ax = 1 - ax2 * (1 - ax2 * (0.5 - 0.166666666666666666667 * ax2));
-            for (int n = 1; n < 60; ++n)
-            {
-                const double coef = c_expa2n2[n - 1] * expx2 / (a2 * (n * n) + y * y);
-                prod2ax *= exp2ax;
-                prodm2ax *= expm2ax;
-                sum1 += coef;
-                sum2 += coef * prodm2ax;
-                sum3 += coef * prod2ax;
-                sum5 += coef * (2 * a) * n * v_sinh_taylor((2 * a) * n * x);
-                if (coef * prod2ax < relerr * sum3)
-                    break;
-            }
-        }
-        else
-        {
-            expx2 = exp(-x * x);
-            const double exp2ax = exp((2 * a) * x), expm2ax = 1 / exp2ax;
-            for (int n = 1; n < 60; ++n)
-            {
-                const double coef = c_expa2n2[n - 1] * expx2 / (a2 * (n * n) + y * y);
-                prod2ax *= exp2ax;
-                prodm2ax *= expm2ax;
-                sum1 += coef;
-                sum2 += coef * prodm2ax;
-                sum4 += (coef * prodm2ax) * (a * n);
-                sum3 += coef * prod2ax;
-                sum5 += (coef * prod2ax) * (a * n);
-                if ((coef * prod2ax) * (a * n) < relerr * sum5)
-                    break;
-            }
-        }
-        const double expx2erfcxy = expx2 * erfcx(y);
-        if (y > 5)
-        {
-            // the imaginary terms cancel
-            const double sinxy = sin(x * y);
-            retR = (expx2erfcxy - c * y * sum1) * cos(2 * x * y) + (c * x * expx2) * sinxy * v_sinc(x * y, sinxy);
-        }
-        else
-        {
-            const double xs = v;
-            const double sinxy = sin(xs * y);
-            const double sin2xy = sin(2 * xs * y), cos2xy = cos(2 * xs * y);
-            const double coef1 = expx2erfcxy - c * y * sum1;
-            const double coef2 = c * xs * expx2;
-            retR = coef1 * cos2xy + coef2 * sinxy * v_sinc(xs * y, sinxy);
-            retI = coef2 * v_sinc(2 * xs * y, sin2xy) - coef1 * sin2xy;
-        }
-    }
-    else
-    {
-        // x >= 10: only sum3 and sum5 contribute
-        retR = exp(-x * x);
-        const double n0 = floor(x / a + 0.5);
-        const double dx = a * n0 - x;
-        sum3 = exp(-dx * dx) / (a2 * (n0 * n0) + y * y);
-        sum5 = a * n0 * sum3;
-        const double exp1 = exp(4 * a * dx);
-        double exp1dn = 1;
-        int dn;
-        bool done = false;
-        for (dn = 1; n0 - dn > 0; ++dn)
-        {
-            const double np = n0 + dn, nm = n0 - dn;
-            double tp = exp(-(a * dn + dx) * (a * dn + dx));
-            double tm = tp * (exp1dn *= exp1);
-            tp /= (a2 * (np * np) + y * y);
-            tm /= (a2 * (nm * nm) + y * y);
-            sum3 += tp + tm;
-            sum5 += a * (np * tp + nm * tm);
-            if (a * (np * tp + nm * tm) < relerr * sum5)
-            {
-                done = true;
-                break;
-            }
-        }
-        while (!done)
-        {
-            const double np = n0 + dn++;
-            const double tp = exp(-(a * dn + dx) * (a * dn + dx)) / (a2 * (np * np) + y * y);
-            sum3 += tp;
-            sum5 += a * np * tp;
-            if (a * np * tp < relerr * sum5)
-                break;
-        }
-    }
-    H = retR + (0.5 * c) * y * (sum2 + sum3);
-    F = retI + (0.5 * c) * copysign(sum5 - sum4, v);
-}
-
 // phi, phiQ..psiV [l, mu, dir, k] of every polarised line: one thread per point, the Zeeman components summed in their
 // order by alpha, then the projections (Source/FormalStokes.cpp:43-110; phi and the six arrays are written, not
 // accumulated: the reference zero-fills them and visits every point once).
@@ -240,45 +71,8 @@ __global__ void __launch_bounds__(256) polarised_profile_kernel(const PolLineArg
         const size_t mk = (size_t)mu * a.Ns + k;
         const double vk = (vBase + s * a.vlosMu[mk]) / vb;
         const double ad = a.aDamp[k];
-        double phi_sb = 0.0, phi_pi = 0.0, phi_sr = 0.0;
-        double psi_sb = 0.0, psi_pi = 0.0, psi_sr = 0.0;
-        for (int nz = 0; nz < a.nComp; ++nz)
-        {
-            double H, F;
-            d_voigt_HF(ad, vk - a.shift[nz] * vB, H, F);
-            const double st = a.strength[nz];
-            const int al = a.alpha[nz];
-            if (al == -1)
-            {
-                phi_sb += st * H;
-                psi_sb += st * F;
-            }
-            else if (al == 0)
-            {
-                phi_pi += st * H;
-                psi_pi += st * F;
-            }
-            else if (al == 1)
-            {
-                phi_sr += st * H;
-                psi_sr += st * F;
-            }
-        }
-        const double cg = a.cosGamma[mk];
-        const double sin2_gamma = 1.0 - cg * cg;
-        const double cos_2chi = a.cos2chi[mk];
-        const double sin_2chi = a.sin2chi[mk];
-        const double phi_sigma = phi_sr + phi_sb;
-        const double phi_delta = 0.5 * phi_pi - 0.25 * phi_sigma;
-        a.phi[idx] = (phi_delta * sin2_gamma + 0.5 * phi_sigma) * sv;
-        a.pol[0 * n + idx] = s * phi_delta * sin2_gamma * cos_2chi * sv;
-        a.pol[1 * n + idx] = phi_delta * sin2_gamma * sin_2chi * sv;
-        a.pol[2 * n + idx] = s * 0.5 * (phi_sr - phi_sb) * cg * sv;
-        const double psi_sigma = psi_sr + psi_sb;
-        const double psi_delta = 0.5 * psi_pi - 0.25 * psi_sigma;
-        a.pol[3 * n + idx] = s * psi_delta * sin2_gamma * cos_2chi * sv;
-        a.pol[4 * n + idx] = psi_delta * sin2_gamma * sin_2chi * sv;
-        a.pol[5 * n + idx] = s * 0.5 * (psi_sr - psi_sb) * cg * sv;
+        d_polarised_profile(ad, vk, vB, a.nComp, a.alpha, a.shift, a.strength, a.cosGamma, a.cos2chi, a.sin2chi, mk, sv, s,
+                            a.phi, a.pol, n, idx);
     }
 }
 

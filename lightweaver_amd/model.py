@@ -420,15 +420,22 @@ def check_mus(mus):
     return mus
 
 
-def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None) -> Problem:
+def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None, stokes=False, mux=None, muy=None) -> Problem:
     """The problem LwContext.compute_rays (Source/LwMiddleLayer.pyx:3898-4002) hands to its second context: a deep copy
     of `prob` (populations, J, background, rhoPrd: equal, not shared) whose rays are `mus`, with wmu = 0 as
     Atmosphere.rays leaves it unless `wmu` is given, and vlosMu = mu (x) v_z.  `vz` [Nspace] defaults to
     vlosMu[0] / muz[0] of `prob` (the 1D convention vlosMu = muz (x) v_z).  Every line's phi is dropped for a zero array of
-    the new ray count (make it with compute_profiles); full-Stokes data is not carried over.  A CALLABLE lower boundary
+    the new ray count (make it with compute_profiles); full-Stokes data is not carried over unless `stokes` (below).  A
+    CALLABLE lower boundary
     has no data for a new direction: pass `lowerBc` [Nlambda, Nmu] (it feeds the up-going rays); a CALLABLE upper
     boundary becomes ZERO, which an up-going ray never reads.  What Context.compute_rays computes on the device without any
-    of this is formal_sol(upOnly=True) of this problem."""
+    of this is formal_sol(upOnly=True) of this problem.
+    stokes: the copy carries StokesData for the new rays, as compute_rays(mus, stokes=True) of the reference leaves its
+    second context: B, gammaB, chiB and every line's Zeeman components equal to the originals (not shared), zero polarised
+    profiles of the new ray count (make them with compute_polarised_profiles) and the field projected onto the new
+    directions (update_projections).  `mux` / `muy` [Nmu] default to the reference's 1D convention mux = sqrt(1 - mu^2),
+    muy = 0 (lightweaver/atmosphere.py:1509-1510).  Context.compute_rays(stokes=True) computes single_stokes_fs(upOnly=True)
+    of this problem on the device."""
     if prob.grid2d is not None:
         raise ValueError('observer_problem: 1D plane-parallel problems only')
     mus = check_mus(mus)
@@ -458,4 +465,21 @@ def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None) -> Pro
         new.zUpperBc = Boundary(abi.BC_ZERO)
     new.stokes = None
     new.Quv = None
+    if stokes:
+        st = prob.stokes
+        if st is None:
+            raise ValueError('observer_problem: stokes=True needs Problem.set_stokes(StokesData(...)) first')
+        mux, muy = observer_azimuth(mus, mux, muy)
+        new.set_stokes(StokesData(B=st.B.copy(), gammaB=st.gammaB.copy(), chiB=st.chiB.copy(), mux=mux, muy=muy,
+                                  lines=[StokesLine(L.atom, L.trans, L.alpha.copy(), L.shift.copy(), L.strength.copy())
+                                         for L in st.lines], vz=vz.copy()))
     return new
+
+
+def observer_azimuth(mus, mux=None, muy=None):
+    """mux, muy [Nmu] of observer directions `mus`: the reference's 1D convention mux = sqrt(1 - mu^2), muy = 0
+    (lightweaver/atmosphere.py:1509-1510) where not given."""
+    mus = check_mus(mus)
+    mux = np.sqrt(1.0 - mus ** 2) if mux is None else _f64(np.atleast_1d(mux), mus.shape).copy()
+    muy = np.zeros(mus.shape[0]) if muy is None else _f64(np.atleast_1d(muy), mus.shape).copy()
+    return mux, muy
