@@ -724,6 +724,32 @@ int lwhip_compute_stokes_rays(lwhip_context* ctx, const lwhip_stokes_rays* rays)
  * offending column named.  Each column's results are the bits of lwhip_compute_stokes_rays on it. */
 int lwhip_batch_compute_stokes_rays(lwhip_batch* batch, const lwhip_stokes_rays* perColumn);
 
+/* ---- emergent spectra along observer rays (2D) --------------------------------------------------------------------------
+ * LwContext.compute_rays(mus, upOnly=True) (Source/LwMiddleLayer.pyx:3898-4002) on a 2D context, from the state resident on the
+ * device: for every wavelength of [laStart, laEnd) and every direction (mux[m], muz[m]) the up-going rays through the x-periodic
+ * grid, I at the top plane.  The intersection table of the directions is built on the host (lwhip_build_intersections), uploaded
+ * and kept until a call asks for other directions; chi and S are gathered as lwhip_formal_sol gathers them, except that each
+ * line's profile is evaluated in the kernel: phi = H(aDamp, v) / (sqrt(pi) vBroad), v = ((lambda - lambda0) c / lambda0 +
+ * mux vx + muz vz) / vBroad; the solve is the 2D formal solver of lwhip_formal_sol(upOnly).  Nothing of the context changes, and
+ * only this request crosses to the device.  All pointers are host pointers.  Nspace = Nz Nx, Nla = laEnd - laStart. */
+typedef struct lwhip_rays2d {
+    int32_t Nmu;            /* 1 .. LWHIP_RAYS_MAX_MU directions */
+    int32_t laStart, laEnd; /* as in lwhip_rays: rows of the GLOBAL grid inside the context's own rows; 0, 0 = all */
+    int32_t _pad;
+    const double* muz;      /* [Nmu] 0 < muz <= 1 */
+    const double* mux;      /* [Nmu] signed; muz^2 + mux^2 <= 1 (the remainder is muy, which a 2D atmosphere never reads) */
+    const double* vz;       /* [Nspace] vertical and */
+    const double* vx;       /* [Nspace] horizontal velocity: vlos = mux vx + muz vz (Source/Atmosphere.cpp:20-29) */
+    const double* lowerBc;  /* [Nla, Nmu, Nx]: required with a CALLABLE z lower boundary, ignored otherwise */
+    double* I;              /* [Nla, Nmu, Nx] out: emergent intensity of the up-going rays at the top plane */
+} lwhip_rays2d;
+/* Refusals, before anything is queued and with I untouched: a null context or request, a missing muz / mux / vz / vx / I, muz
+ * outside (0, 1] or muz^2 + mux^2 > 1 + 1e-12, a range outside the context's rows, a CALLABLE lower boundary without lowerBc, a
+ * line without aDamp: LWHIP_ERR_INVALID; no device: LWHIP_ERR_DEVICE; a 1D context, a grid with fixed (CALLABLE) x boundaries
+ * (they have no data for new directions), Nmu above LWHIP_RAYS_MAX_MU, directions whose table has a long characteristic that
+ * does not end on a z plane: LWHIP_ERR_UNSUPPORTED.  The call returns when I is in place (one copy back, one wait). */
+int lwhip_compute_rays_2d(lwhip_context* ctx, const lwhip_rays2d* rays);
+
 /* Block until all work queued on the context's stream has finished. */
 int lwhip_synchronize(lwhip_context* ctx);
 

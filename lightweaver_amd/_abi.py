@@ -174,6 +174,13 @@ class lwhip_stokes_rays(C.Structure):
     _fields_ = [('rays', lwhip_rays), ('cosGamma', f64p), ('cos2chi', f64p), ('sin2chi', f64p), ('Quv', f64p)]
 
 
+class lwhip_rays2d(C.Structure):
+    """Observer rays of lwhip_compute_rays_2d: Nmu directions (muz, mux), a range of the global wavelength grid, both velocity
+    components [Nspace], optional lower-boundary data [Nla, Nmu, Nx], the output I [Nla, Nmu, Nx] (host pointers)."""
+    _fields_ = [('Nmu', C.c_int32), ('laStart', C.c_int32), ('laEnd', C.c_int32), ('_pad', C.c_int32),
+                ('muz', f64p), ('mux', f64p), ('vz', f64p), ('vx', f64p), ('lowerBc', f64p), ('I', f64p)]
+
+
 _RAW = {}
 
 
@@ -273,6 +280,7 @@ SYMBOLS = [
     ('lwhip_batch_compute_rays', C.c_int, [C.c_void_p, C.POINTER(lwhip_rays)]),
     ('lwhip_compute_stokes_rays', C.c_int, [ctx_p, C.POINTER(lwhip_stokes_rays)]),
     ('lwhip_batch_compute_stokes_rays', C.c_int, [C.c_void_p, C.POINTER(lwhip_stokes_rays)]),
+    ('lwhip_compute_rays_2d', C.c_int, [ctx_p, C.POINTER(lwhip_rays2d)]),
 ]
 
 

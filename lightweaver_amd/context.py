@@ -532,6 +532,58 @@ class Context:
                 out.chi, out.eta, out.Idepth = out.chi[:, 0], out.eta[:, 0], out.Idepth[:, 0]
         return out if depthData else out.I
 
+    # -- emergent spectra along observer rays (2D) ------------------------------------------------------------------------
+    def _rays2d_request(self, muz, mux, vz, vx, laStart, laEnd, lowerBc):
+        """The lwhip_rays2d block of one compute_rays_2d call and the arrays it points to: (struct, I, keepalive)."""
+        from .model import check_mus
+        muz = check_mus(muz)
+        Nmu, Ns = muz.shape[0], self.prob.Nspace
+        Nx = self.prob.grid2d.Nx if self.prob.grid2d is not None else 1
+        if mux is None:
+            mux = np.sqrt(1.0 - muz ** 2)    # (the convention of the reference's Atmosphere.rays)
+        mux = np.ascontiguousarray(np.atleast_1d(np.asarray(mux, dtype=np.float64)).reshape(-1))
+        if mux.shape != muz.shape:
+            raise ValueError('mux must have one entry per muz')
+        if vz is None:
+            raise ValueError('compute_rays_2d: vz [Nspace] is required (a 2D context holds only the projections vlosMu)')
+        vz = np.ascontiguousarray(vz, dtype=np.float64).reshape(-1)
+        vx = np.zeros(Ns) if vx is None else np.ascontiguousarray(vx, dtype=np.float64).reshape(-1)
+        if vz.shape != (Ns,) or vx.shape != (Ns,):
+            raise ValueError('vz and vx must be [Nspace]')
+        la0 = int(laStart) if (laStart or laEnd) else self.laStart
+        la1 = int(laEnd) if laEnd else self.laEnd
+        nla = max(la1 - la0, 0)
+        r = abi.lwhip_rays2d()
+        r.Nmu, r.laStart, r.laEnd = Nmu, la0, la1
+        keep = [muz, mux, vz, vx]
+        r.muz, r.mux = muz.ctypes.data_as(abi.f64p), mux.ctypes.data_as(abi.f64p)
+        r.vz, r.vx = vz.ctypes.data_as(abi.f64p), vx.ctypes.data_as(abi.f64p)
+        if lowerBc is not None:
+            lowerBc = np.ascontiguousarray(lowerBc, dtype=np.float64)
+            if lowerBc.shape != (nla, Nmu, Nx):
+                raise ValueError('lowerBc must be [Nla, Nmu, Nx] of the requested wavelength range')
+            keep.append(lowerBc)
+            r.lowerBc = lowerBc.ctypes.data_as(abi.f64p)
+        I = np.zeros((nla, Nmu, Nx))
+        r.I = I.ctypes.data_as(abi.f64p)
+        return r, I, keep
+
+    def compute_rays_2d(self, muz=1.0, mux=None, vz=None, vx=None, laStart=0, laEnd=0, lowerBc=None, squeeze=True):
+        """LwContext.compute_rays(mus, upOnly=True) (Source/LwMiddleLayer.pyx:3898-4002) of a 2D context from the state that
+        is resident on the device: the emergent intensity I [Nla, Nmu, Nx] at the top plane of the up-going rays with
+        direction cosines (muz, mux), over the wavelengths [laStart, laEnd) of the global grid (default: all this context
+        holds).  `mux` defaults to sqrt(1 - muz^2), the convention of the reference's Atmosphere.rays; it is signed.  `vz`
+        [Nspace] is required (a 2D context holds only the projections vlosMu), `vx` [Nspace] defaults to no horizontal flow:
+        the profiles of the new directions are evaluated in the gather kernel with vlos = mux vx + muz vz.  The intersection
+        table of the directions is built on the host and kept on the device until another set of directions is asked for.
+        Nothing of the context changes, and nothing but the request crosses to the device: upload what the host changed
+        first.  A CALLABLE lower boundary needs `lowerBc` [Nla, Nmu, Nx].  squeeze: a scalar `muz` drops the Nmu axis.
+        formal_sol(upOnly=True) of model.observer_problem_2d is the same computation through a second context."""
+        r, I, keep = self._rays2d_request(muz, mux, vz, vx, laStart, laEnd, lowerBc)
+        _check(self.lib, self.lib.lwhip_compute_rays_2d(self._h, C.byref(r)), 'lwhip_compute_rays_2d')
+        del keep
+        return I[:, 0] if squeeze and np.ndim(muz) == 0 else I
+
     # -- multi-GPU split ----------------------------------------------------------------------------------
     def fs_partial(self, lambdaIterate=False):
         _check(self.lib, self.lib.lwhip_fs_partial(self._h, int(lambdaIterate)), 'lwhip_fs_partial')

@@ -66,7 +66,7 @@ int run_2d(lwhip_context* c, int lambdaIterate, int mode)
     f.zLowerBc = g.zLowerBc;
     f.zUpperBc = g.zUpperBc;
     f.nRayCycle = nRaysActive;
-    f.mux = c->g2mux.p;
+    f.mux = c->g2.mux.p;
     f.periodic = g.periodic ? 1 : 0;
     f.zNmuLow = c->prob.zLowerBc.Nmu;
     f.zNmuUp = c->prob.zUpperBc.Nmu;
@@ -84,18 +84,18 @@ int run_2d(lwhip_context* c, int lambdaIterate, int mode)
         f.xIdxUp = c->xIdxUp.p;
     }
     f.temperature = c->temperature.p;
-    f.uw = c->g2uw.p;
-    f.dw = c->g2dw.p;
-    f.uwS = c->g2uwS.p;
-    f.dwS = c->g2dwS.p;
-    f.uwA = c->g2uwA.p;
-    f.dwA = c->g2dwA.p;
+    f.uw = c->g2.uw.p;
+    f.dw = c->g2.dw.p;
+    f.uwS = c->g2.uwS.p;
+    f.dwS = c->g2.dwS.p;
+    f.uwA = c->g2.uwA.p;
+    f.dwA = c->g2.dwA.p;
     f.nRec = (size_t)2 * g.Nrays * Ns;
-    f.longCharIdx = c->g2long.p;
-    f.substepOff = c->g2subOff.p;
-    f.substeps = c->g2sub.p;
+    f.longCharIdx = c->g2.longIdx.p;
+    f.substepOff = c->g2.subOff.p;
+    f.substeps = c->g2.sub.p;
     f.NlongChar = g.NlongChar;
-    f.lcOwner = c->g2lcOwner.p;
+    f.lcOwner = c->g2.lcOwner.p;
     f.lcBuf = g.NlongChar > 0 ? c->b2lc.p : nullptr;
     f.lcUpOnly = (mode == 2) ? 1 : 0;
     f.rays = rayList;

@@ -9,6 +9,7 @@
 //     lwhip_batch.hip    1.5D column batches
 //     lwhip_api_prd.hip  PRD sub-iterations
 //     lwhip_rays.hip     emergent spectra along observer rays
+//     lwhip_rays2d.hip   ... of a 2D context
 //
 // There is no CPU fallback: without a HIP device every compute entry point fails with LWHIP_ERR_DEVICE.
 #pragma once
@@ -366,8 +367,45 @@ int stokes_transfer(lwhip_context* c, bool up); // lwhip_upload / lwhip_download
 int check_stokes_ctx(lwhip_context* c, const char* what, bool needStokes);
 struct StokesBatch; // what a context, or a column batch, keeps for its full-Stokes formal solutions (lwhip_stokes_fs.hip)
 void stokes_batch_release(StokesBatch* s);
-struct RaysState; // observer rays (lwhip_rays.hip): the gather tables of a context, the staging of its -- or a batch's -- calls
+// observer rays (lwhip_rays.hip, lwhip_rays2d.hip)
+// one transition as the gather reads it
+struct RayTrans
+{
+    int32_t type, gi, gj, Nblue; // (gi, gj: global level rows of the n pool; Nblue: first row of the context's grid)
+    int32_t prd, row, atom, ltStart; // row: aDamp row (lines) / ratio row (continua); ltStart: own-grid index of Nblue
+    int64_t parOff, rhoOff, waveOff; // (rhoOff: of the row of Nblue)
+    double lambda0;
+};
+
+// The structure tables of the gather and the staging of a call.  The tables depend on the structure alone: a context made with
+// lwhip_create_like uses its table owner's.
+struct RaysState
+{
+    std::mutex lock;
+    bool built = false;
+    DevBuf<RayTrans> tr;
+    DevBuf<int32_t> laOff, laTr;
+    DevBuf<unsigned char> in, out; // [RayCol per column | staged vz | staged lowerBc], [per column: I | chi | eta | I(k)]
+    PinnedBlock inPinned, outPinned;
+};
+
 void rays_release(RaysState* s);
+// the gather tables of `o` (a table owner: a context made with lwhip_create_like uses its owner's), made on first use
+int rays_tables(lwhip_context* o, RaysState*& out);
+struct Rays2dState; // observer rays of a 2D context (lwhip_rays2d.hip): the geometry of the last view, the staging of its calls
+void rays2d_release(Rays2dState* s);
+
+// The geometry tables of a 2D grid on the device, as the 2D formal solver reads them (Fs2dArgs): the context's own grid, and the
+// grid of an observer's directions (lwhip_rays2d.hip).  Filled by geom2d_upload (lwhip_state.hip).
+struct Geom2dDev
+{
+    DevBuf<double> mux;
+    DevBuf<lwhip_intersection> uw, dw, sub;
+    DevBuf<double> uwS, dwS; // the records field by field (fs2d_records_packed), or empty
+    DevBuf<int32_t> uwA, dwA, longIdx, subOff, lcOwner;
+};
+// `g`'s tables into `d`, queued on m's stream: g's arrays must stay until that stream has been waited for
+int geom2d_upload(DevMem& m, const lwhip_grid2d& g, Geom2dDev& d);
 }
 
 struct lwhip_context;
@@ -474,7 +512,7 @@ struct lwhip_context
     DevBuf<double> prdChange, rowsBuf, popScratch, prdJt, prdJ;
     DevBuf<PrdLineArgs> prdArgsDev;   // argument blocks of the PRD lines of a sub-iteration (one launch for all lines)
     std::vector<PrdLineArgs> prdArgsHost; // what the device copy holds
-    DevBuf<double> g2mux, b2cs, b2I, b2Psi, b2coef, red2d;
+    DevBuf<double> b2cs, b2I, b2Psi, b2coef, red2d;
     DevBuf<int32_t> b2idx;
     int groups2d = 1, maxRowsLa = 1;
     int kLo = 0, kHi = -1; // depth range of the population updates (lwhip_set_depth_range); kHi < 0: to the end
@@ -492,14 +530,13 @@ struct lwhip_context
     bool partsOnly = false;       // fs_partial ran stage 1 of the slab reduce only (one-call iteration)
     int batchHint = 0;            // lwhip_options.flags & 0xffff: contexts expected to share the device (column batch)
     bool prdDetailed = false;     // LWHIP_OPT_PRD_DETAILED: the PRD calls include the detailed atoms' PRD lines
-    DevBuf<lwhip_intersection> g2uw, g2dw, g2sub;
+    Geom2dDev g2;                      // 2D: the geometry tables of the context's own grid (geom2d_upload)
     DevBuf<double> xbcLow, xbcUp;      // 2D, fixed x boundaries: [Nla, Nmu, Nz] of the shard
     DevBuf<double> zDown, zUp;         // ZPlaneDecomposition outputs [Nla, Nrays, Nx] (lwhip_set_zplane_outputs)
     double* zDownHost = nullptr;       // their host arrays [Nlambda, Nrays, Nx]
     double* zUpHost = nullptr;
     DevBuf<int32_t> xIdxLow, xIdxUp;   // [Nrays, 2]
-    DevBuf<int32_t> g2long, g2subOff, slotTrD, g2lcOwner, g2uwA, g2dwA;
-    DevBuf<double> g2uwS, g2dwS; // the records field by field
+    DevBuf<int32_t> slotTrD;
     DevBuf<double> b2lc; // [batch2d][NlongChar][3]
     // lwhip_create_like: the structure tables (lwhip_tables.hip) are borrowed from a context of the same structure, which
     // counts its borrowers and cannot be destroyed before them
@@ -563,6 +600,7 @@ struct lwhip_context
     StokesState stokes;           // lwhip_set_stokes (lwhip_stokes.hip)
     StokesBatch* stokesFs = nullptr; // made by the first lwhip_full_stokes_fs (lwhip_stokes_fs.hip)
     RaysState* rays = nullptr;    // made by the first lwhip_compute_rays (lwhip_rays.hip)
+    Rays2dState* rays2d = nullptr; // made by the first lwhip_compute_rays_2d (lwhip_rays2d.hip)
 
     bool profiling = false;
     int profEvery = 1, profCount = 0; // time every profEvery-th sweep launch (lwhip_profile_enable(ctx, n))
@@ -621,6 +659,7 @@ struct lwhip_context
             b->release(); // (before the stream they were used on goes back to its pool)
         stokes_batch_release(stokesFs);
         rays_release(rays);
+        rays2d_release(rays2d);
         for (auto& pr : pending)
         {
             (void)hipEventDestroy(pr.first);

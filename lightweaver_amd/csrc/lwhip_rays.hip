@@ -41,15 +41,6 @@ namespace
 {
 enum { RAYS_THREADS = 256, RAYS_ARRAYS = 8, RAYS_MAX_NS = 1024, RAYS_LDS_TARGET = 40 << 10 };
 
-// one transition as the gather reads it
-struct RayTrans
-{
-    int32_t type, gi, gj, Nblue; // (gi, gj: global level rows of the n pool; Nblue: first row of the context's grid)
-    int32_t prd, row, atom, ltStart; // row: aDamp row (lines) / ratio row (continua); ltStart: own-grid index of Nblue
-    int64_t parOff, rhoOff, waveOff; // (rhoOff: of the row of Nblue)
-    double lambda0;
-};
-
 // one column: the context's resident state, the request's staged inputs and its outputs
 struct RayCol
 {
@@ -320,18 +311,6 @@ int rays_per_group(int Ns)
 }
 } // namespace
 
-// The structure tables of the gather and the staging of a call.  The tables depend on the structure alone: a context made with
-// lwhip_create_like uses its table owner's.
-struct RaysState
-{
-    std::mutex lock;
-    bool built = false;
-    DevBuf<RayTrans> tr;
-    DevBuf<int32_t> laOff, laTr;
-    DevBuf<unsigned char> in, out; // [RayCol per column | staged vz | staged lowerBc], [per column: I | chi | eta | I(k)]
-    PinnedBlock inPinned, outPinned;
-};
-
 void rays_release(RaysState* s)
 {
     if (s)
@@ -410,6 +389,8 @@ hipError_t rays_init_table(int device)
     return e;
 }
 
+} // namespace
+
 // the gather tables of `o` (a table owner), made on first use
 int rays_tables(lwhip_context* o, RaysState*& out)
 {
@@ -451,6 +432,8 @@ int rays_tables(lwhip_context* o, RaysState*& out)
     return LWHIP_OK;
 }
 
+namespace
+{
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The call: cols[i] with request reqs[i], everything on cols[0]'s stream, staged through `st`.

@@ -133,6 +133,61 @@ void released_fill(void* p, size_t bytes)
     (void)hipMemsetAsync(p, 0xFE, bytes, hipStreamPerThread);
 }
 
+// The geometry tables of a 2D grid as the 2D formal solver reads them: the intersection records whole and packed, the long
+// characteristics with their sub-steps and their owners.  For the context's own grid (alloc_state) and for the grid of an
+// observer's directions (lwhip_rays2d.hip).
+int geom2d_upload(DevMem& m, const lwhip_grid2d& g, Geom2dDev& d)
+{
+    const size_t Ns = (size_t)g.Nx * g.Nz;
+    const size_t nSt = (size_t)g.Nrays * 2 * Ns;
+    auto upv = [&m](auto& buf, const auto* host, size_t count) -> hipError_t {
+        hipError_t e = buf.alloc(m, std::max<size_t>(count, 1));
+        return e != hipSuccess ? e : m.h2d(buf.p, host, count * sizeof(*host));
+    };
+    HIP_TRY(upv(d.mux, g.mux, (size_t)g.Nrays));
+    HIP_TRY(upv(d.uw, g.uw, nSt));
+    HIP_TRY(upv(d.dw, g.dw, nSt));
+    d.uwS.release();
+    d.uwA.release();
+    d.dwS.release();
+    d.dwA.release();
+    {
+        std::vector<double> su, sd;
+        std::vector<int32_t> wu, wd;
+        if (fs2d_records_packed(g.uw, nSt, g.Nx, g.Nz, su, wu) && fs2d_records_packed(g.dw, nSt, g.Nx, g.Nz, sd, wd))
+        {
+            HIP_TRY(d.uwS.upload(m, su));
+            HIP_TRY(d.uwA.upload(m, wu));
+            HIP_TRY(d.dwS.upload(m, sd));
+            HIP_TRY(d.dwA.upload(m, wd));
+        }
+    }
+    HIP_TRY(upv(d.longIdx, g.longCharIdx, nSt));
+    HIP_TRY(upv(d.subOff, g.substepOff, (size_t)g.NlongChar + 1));
+    HIP_TRY(upv(d.sub, g.substeps, (size_t)g.substepOff[g.NlongChar]));
+    d.lcOwner.release();
+    if (g.NlongChar > 0)
+    {
+        // who owns each long characteristic: (ray, point)
+        std::vector<int32_t> owner((size_t)2 * g.NlongChar, -1);
+        for (size_t i = 0; i < nSt; ++i)
+        {
+            const int lc = g.longCharIdx[i];
+            if (lc < 0)
+                continue;
+            if (lc >= g.NlongChar)
+                return fail(LWHIP_ERR_INVALID, "grid2d: longCharIdx out of range");
+            owner[2 * (size_t)lc] = (int32_t)(i / Ns);
+            owner[2 * (size_t)lc + 1] = (int32_t)(i % Ns);
+        }
+        for (int lc = 0; lc < g.NlongChar; ++lc)
+            if (owner[2 * (size_t)lc] < 0)
+                return fail(LWHIP_ERR_INVALID, "grid2d: a long characteristic belongs to no point");
+        HIP_TRY(d.lcOwner.upload(m, owner));
+    }
+    return LWHIP_OK;
+}
+
 int alloc_state(lwhip_context* c)
 {
     const size_t Ns = c->Ns, Nla = c->Nla, Nr = c->Nrays;
@@ -234,48 +289,10 @@ int alloc_state(lwhip_context* c)
     if (c->is2d)
     {
         const lwhip_grid2d& g = *c->prob.grid2d;
-        const size_t nSt = (size_t)g.Nrays * 2 * Ns;
         // (the caller's arrays: they outlive lwhip_create, which waits for its stream)
-        auto upv = [c](auto& buf, const auto* host, size_t count) -> hipError_t {
-            hipError_t e = buf.alloc(c->mem, std::max<size_t>(count, 1));
-            return e != hipSuccess ? e : c->mem.h2d(buf.p, host, count * sizeof(*host));
-        };
-        HIP_TRY(upv(c->g2mux, g.mux, (size_t)g.Nrays));
-        HIP_TRY(upv(c->g2uw, g.uw, nSt));
-        HIP_TRY(upv(c->g2dw, g.dw, nSt));
-        {
-            std::vector<double> su, sd;
-            std::vector<int32_t> wu, wd;
-            if (fs2d_records_packed(g.uw, nSt, g.Nx, g.Nz, su, wu) && fs2d_records_packed(g.dw, nSt, g.Nx, g.Nz, sd, wd))
-            {
-                HIP_TRY(c->g2uwS.upload(c->mem, su));
-                HIP_TRY(c->g2uwA.upload(c->mem, wu));
-                HIP_TRY(c->g2dwS.upload(c->mem, sd));
-                HIP_TRY(c->g2dwA.upload(c->mem, wd));
-            }
-        }
-        HIP_TRY(upv(c->g2long, g.longCharIdx, nSt));
-        HIP_TRY(upv(c->g2subOff, g.substepOff, (size_t)g.NlongChar + 1));
-        HIP_TRY(upv(c->g2sub, g.substeps, (size_t)g.substepOff[g.NlongChar]));
-        if (g.NlongChar > 0)
-        {
-            // who owns each long characteristic: (ray, point)
-            std::vector<int32_t> owner((size_t)2 * g.NlongChar, -1);
-            for (size_t i = 0; i < nSt; ++i)
-            {
-                const int lc = g.longCharIdx[i];
-                if (lc < 0)
-                    continue;
-                if (lc >= g.NlongChar)
-                    return fail(LWHIP_ERR_INVALID, "grid2d: longCharIdx out of range");
-                owner[2 * (size_t)lc] = (int32_t)(i / Ns);
-                owner[2 * (size_t)lc + 1] = (int32_t)(i % Ns);
-            }
-            for (int lc = 0; lc < g.NlongChar; ++lc)
-                if (owner[2 * (size_t)lc] < 0)
-                    return fail(LWHIP_ERR_INVALID, "grid2d: a long characteristic belongs to no point");
-            HIP_TRY(c->g2lcOwner.upload(c->mem, owner));
-        }
+        const int stg = geom2d_upload(c->mem, g, c->g2);
+        if (stg != LWHIP_OK)
+            return stg;
         // wavelengths per batch: per-ray chi, S, I, Psi* of a batch within ~8 GB of the 288.  Every kernel of a batch is
         // latency-bound per workgroup (82 sequential planes in fs2d), so the batch should fill the chip, and fewer,
         // larger batches mean fewer kernel tails (256 x 82 x 268 wavelengths: one batch of 3 GB, 0.1 ms less than two).

@@ -476,6 +476,62 @@ def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None, stokes
     return new
 
 
+def observer_problem_2d(prob: Problem, muz, mux=None, vz=None, vx=None, lowerBc=None, grid2d_factory=None) -> Problem:
+    """observer_problem for a 2D problem: what LwContext.compute_rays (Source/LwMiddleLayer.pyx:3898-4002) hands to its second
+    context.  A deep copy of `prob` whose rays are the directions (muz, mux) with wmu = 0, the intersection table of those
+    directions (grid2d.build_grid2d, or grid2d_factory(x, z, mux, muz, temperature) -> Grid2d), vlosMu = mux (x) vx +
+    muz (x) vz, a zero phi [Nlambda, Nmu, 2, Nspace] per line (make it with compute_profiles) and I [Nlambda, Nmu, Nx].
+    `mux` defaults to sqrt(1 - muz^2); `vz` [Nspace] is required, `vx` defaults to zeros.  A CALLABLE upper boundary becomes
+    ZERO (an up-going ray never reads it), a CALLABLE lower one takes `lowerBc` [Nlambda, Nmu, Nx].  What
+    Context.compute_rays_2d computes on the device without any of this is formal_sol(upOnly=True) of this problem."""
+    from .grid2d import build_grid2d
+    g = prob.grid2d
+    if g is None:
+        raise ValueError('observer_problem_2d: 2D problems only (observer_problem serves 1D ones)')
+    if not g.periodic:
+        raise ValueError('observer_problem_2d: fixed x boundaries have no data for new directions')
+    muz = check_mus(muz)
+    Nr, Ns = muz.shape[0], prob.Nspace
+    mux = np.sqrt(1.0 - muz ** 2) if mux is None else _f64(np.atleast_1d(mux), muz.shape).copy()
+    if np.any(muz ** 2 + mux ** 2 > 1.0 + 1e-12):
+        raise ValueError('observer_problem_2d: muz^2 + mux^2 > 1')
+    if vz is None:
+        raise ValueError('observer_problem_2d: vz [Nspace] is required')
+    vz = _f64(np.asarray(vz).reshape(-1), (Ns,))
+    vx = np.zeros(Ns) if vx is None else _f64(np.asarray(vx).reshape(-1), (Ns,))
+    new = prob.copy()
+    new.muz = muz.copy()
+    new.Nrays = Nr
+    new.wmu = np.zeros(Nr)
+    new.vlosMu = np.ascontiguousarray(mux[:, None] * vx[None, :] + muz[:, None] * vz[None, :])
+    new.I = np.zeros((prob.Nlambda, Nr, g.Nx))
+    if new.storeDepthData:
+        dshape = (prob.Nlambda, Nr, 2, Ns)
+        new.depthChi, new.depthEta, new.depthI = np.zeros(dshape), np.zeros(dshape), np.zeros(dshape)
+    for a in new.atoms:
+        for t in a.trans:
+            if t.type == abi.LINE:
+                t.phi = np.zeros((t.Nlambda, Nr, 2, Ns))   # (the stored one carries the old ray count)
+    zLow, zUp = g.zLowerBc, g.zUpperBc
+    if new.zLowerBc.type == abi.BC_CALLABLE:
+        if lowerBc is None:
+            raise ValueError('observer_problem_2d: a CALLABLE lower boundary has no data for new directions: pass lowerBc '
+                             '[Nlambda, Nmu, Nx]')
+        idxs = np.full((Nr, 2), -1, dtype=np.int32)
+        idxs[:, 1] = np.arange(Nr)
+        new.zLowerBc = Boundary(abi.BC_CALLABLE, idxs=idxs, bcData=_f64(lowerBc, (prob.Nlambda, Nr, g.Nx)).copy())
+    if new.zUpperBc.type == abi.BC_CALLABLE:
+        new.zUpperBc = Boundary(abi.BC_ZERO)
+        zUp = abi.BC_ZERO
+    make = grid2d_factory if grid2d_factory is not None else build_grid2d
+    ng = make(g.x.copy(), g.z.copy(), mux.copy(), muz.copy(), g.temperature.copy())
+    ng.zLowerBc, ng.zUpperBc = zLow, zUp
+    new.grid2d = ng
+    new.stokes = None
+    new.Quv = None
+    return new
+
+
 def observer_azimuth(mus, mux=None, muy=None):
     """mux, muy [Nmu] of observer directions `mus`: the reference's 1D convention mux = sqrt(1 - mu^2), muy = 0
     (lightweaver/atmosphere.py:1509-1510) where not given."""
