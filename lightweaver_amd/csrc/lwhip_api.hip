@@ -802,6 +802,7 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
     if (host_block_init(c) != LWHIP_OK)
         return bail(LWHIP_ERR_DEVICE);
     c->pairRays = dbg_env_int("LWHIP_PAIR_RAYS", 1) != 0;
+    c->isoRays = dbg_env_int("LWHIP_ISO_RAYS", 1) != 0;
     c->prdPipeline = dbg_env_int("LWHIP_PRD_PIPELINE", 1) != 0;
     c->prdGeneral = dbg_env_int("LWHIP_PRD_GENERAL", 0) != 0;
     const bool timing = std::getenv("LWHIP_CREATE_TIMING") != nullptr;
@@ -1734,6 +1735,7 @@ static int compute_profiles_impl(lwhip_context* c)
     c->deviceProfiles = true;
     c->profilesStale = false;
     c->phiSym = c->vlosZero; // (the Voigt arguments of the two directions differ by the sign of the line-of-sight velocity alone)
+    c->phiIso = c->vlosZero; // (... and those of two angles by the velocity's projection alone)
     return retile_profiles(c);
 }
 

@@ -43,6 +43,7 @@ static int batch_compute_profiles(lwhip_batch* b, bool all)
         c->deviceProfiles = true;
         c->profilesStale = false;
         c->phiSym = c->vlosZero;
+        c->phiIso = c->vlosZero;
     }
     return batch_retile(b, todo);
 }
@@ -244,6 +245,8 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
     TileDyn dyn = make_dyn(c0, false, lambdaIterate);
     for (int q = 0; q < n && dyn.phiSym; ++q) // (one launch for all columns: pairs only if every column's profiles are symmetric)
         dyn.phiSym = b->ctxs[q]->phiSym ? 1 : 0;
+    for (int q = 0; q < n && dyn.phiIso; ++q) // (... and one stencil set per wavefront only if every column's are angle-independent)
+        dyn.phiIso = (b->ctxs[q]->phiIso && dyn.phiSym) ? 1 : 0;
     const bool fuse = c0->tileFuse;
     if (!c0->laneSweep) // (the lane sweep's tasks do their own pre-pass)
         HIP_TRY(launch_tile_pre(c0->dtargs.p, c0->htargs, c0->nTiles, b->apList.p, n, c0->stream));

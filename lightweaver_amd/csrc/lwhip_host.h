@@ -574,9 +574,14 @@ struct lwhip_context
     // every line's profile is the same for the two directions of an angle (static atmosphere): found when the profiles are
     // uploaded (the host's arrays are compared) or generated (all line-of-sight velocities zero); TileDyn::phiSym
     bool phiSym = false, vlosZero = false;
+    // ... and, beyond that, the same for every angle (no line-of-sight velocity at all: the Voigt argument does not know the
+    // ray), found in the same places: bit-identical blocks [lt][0][down] = [lt][mu][dir]; TileDyn::phiIso
+    bool phiIso = false;
     // LWHIP_PAIR_RAYS=0 / LWHIP_PRD_PIPELINE=0 (experiment knobs, read ONCE per context in lwhip_create and only under
     // LWHIP_DEBUG like the other layout knobs: the first changes the order of the arithmetic)
-    bool pairRays = true, prdPipeline = true, prdGeneral = false;
+    // LWHIP_ISO_RAYS=0: angle-independent profiles are not made use of (the stencils are formed once per angle as for
+    // profiles that are only direction-symmetric; the same arithmetic, so the same bits)
+    bool pairRays = true, isoRays = true, prdPipeline = true, prdGeneral = false;
     PinnedBlock prdPinnedPipe;
     int prdPipeIter = 0;     // > 0: the sub-iteration the calls of lwhip_prd_partial / _finalise belong to
     double prdPipeTol = 0.0;

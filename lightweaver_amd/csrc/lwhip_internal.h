@@ -345,7 +345,8 @@ struct TileDyn
     const int32_t* stopCtl;
     // 1: every line's profile is the same for the two directions of an angle (a static atmosphere): the lane sweep forms
     // chi, S and the stencils once per angle for its one-line tiles (lwhip_lanesweep.hip, "pairs")
-    int32_t phiSym, _padS;
+    // phiIso = 1: ... and the same for every angle (no line-of-sight velocity): once per wavefront, whichever rays it holds
+    int32_t phiSym, phiIso;
 };
 // retile one line's profiles: standard [nlt][Nmu][2][Ns] -> the tiles' [2][Ns][64] blocks
 struct RetileArgs

@@ -586,6 +586,9 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
     // ANGLE (cont_unit with the line's opacity of that angle), the down and the up ray scale / mirror them.  The host sets
     // TileDyn::phiSym when every line's profile is direction-symmetric (checked when the profiles are uploaded or generated);
     // wavefronts that hold only one direction of an angle (split rays) take the general path.
+    // Without any line-of-sight velocity the profile does not depend on the angle either (TileDyn::phiIso, found in the same
+    // places): cont_unit reads the angle nowhere but in its profile load, so the unit-mu stencils of the wavefront's FIRST
+    // angle are those of all its rays -- once per wavefront, and for any share of a split tile's rays.
 #ifdef LS_NO_PAIR_HOIST
     constexpr bool PAIRABLE = false;
 #else
@@ -1601,8 +1604,11 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
     const int nRun = NRUN;
     for (run = 0; run < nRun; ++run)
     {
-    // (pairs: only a wavefront that holds both rays of every angle -- no split -- and only if the host found the profiles symmetric)
-    const bool pairMode = PAIRABLE && dyn.phiSym != 0 && dyn.nPass == 2 && q0 == 0 && q1 == 2 * Nmu;
+    // (pairs: only a wavefront that holds both rays of every angle -- no split -- and only if the host found the profiles
+    // symmetric; if it found them the same for every angle as well -- phiIso: no line-of-sight velocity --, any share of the
+    // rays, and chi, S and the stencils of the wavefront's first angle serve all its rays)
+    const bool isoMode = PAIRABLE && dyn.phiIso != 0 && dyn.nPass == 2;
+    const bool pairMode = isoMode || (PAIRABLE && dyn.phiSym != 0 && dyn.nPass == 2 && q0 == 0 && q1 == 2 * Nmu);
     if (!pairMode)
         prefetch_first();
     if constexpr (CONT)
@@ -1617,11 +1623,15 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
         {
             if constexpr (PAIRABLE)
             {
-                for (int mu = 0; mu < Nmu; ++mu)
+                const int mu0 = q0 >> 1;
+                for (int mu = mu0; 2 * mu < q1; ++mu)
                 {
-                    cont_unit(mu);
-                    pass(std::false_type{}, std::true_type{}, mu, 0u);
-                    pass(std::true_type{}, std::true_type{}, mu, 0u);
+                    if (mu == mu0 || !isoMode)
+                        cont_unit(mu);
+                    if (2 * mu >= q0)
+                        pass(std::false_type{}, std::true_type{}, mu, 0u);
+                    if (2 * mu + 1 < q1)
+                        pass(std::true_type{}, std::true_type{}, mu, 0u);
                 }
             }
         }

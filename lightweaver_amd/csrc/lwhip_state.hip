@@ -566,6 +566,7 @@ TileDyn make_dyn(lwhip_context* c, bool upOnly, int lambdaIterate)
     d.stopIter = 0;
     d.stopCtl = nullptr;
     d.phiSym = (c && c->phiSym && c->pairRays) ? 1 : 0;
+    d.phiIso = (c && c->phiIso && c->phiSym && c->pairRays && c->isoRays) ? 1 : 0;
     return d;
 }
 
@@ -712,6 +713,7 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
     const size_t l0 = c->laStart;
     std::vector<double> rmuzHost; // (lives until the stream has drained, at the end)
     bool phiSymUp = true;         // (LWHIP_PROFILES: the uploaded profiles are the same for both directions of every angle)
+    bool phiIsoUp = true;         // (... and every angle's are the same as angle 0's)
     if (mask & LWHIP_GAMMA)
         c->prefillPending = false; // the host pre-fill being uploaded supersedes it
     if (mask & LWHIP_J)
@@ -922,6 +924,9 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
                     {
                         const double* ph = t.phi + ((size_t)h.ltStart * Nr + e) * 2 * Ns;
                         phiSymUp = std::memcmp(ph, ph + Ns, Ns * sizeof(double)) == 0;
+                        // (the down block against angle 0's of the same wavelength; with phiSymUp that covers the up blocks)
+                        if (phiIsoUp && e % Nr != 0)
+                            phiIsoUp = std::memcmp(ph, ph - (e % Nr) * 2 * Ns, Ns * sizeof(double)) == 0;
                     }
                     H2D(c->wphi.p + (size_t)h.row * Ns, t.wphi, Ns);
                 }
@@ -984,6 +989,7 @@ static int upload_impl(lwhip_context* c, uint32_t mask)
             return str;
         c->deviceProfiles = c->profilesStale = false; // the host's profiles are authoritative again
         c->phiSym = phiSymUp;
+        c->phiIso = phiSymUp && phiIsoUp;
     }
     else if ((mask & (LWHIP_ATMOS | LWHIP_NSTAR)) && c->deviceProfiles)
         c->profilesStale = true; // phi / wphi follow the new velocities and widths before the next sweep

@@ -238,6 +238,7 @@ int lwhip_compute_polarised_profiles(lwhip_context* c)
     s.polOnDevice = true;
     // phi of the polarised lines changed: the two directions of an angle stay alike only without line-of-sight velocities
     c->phiSym = c->phiSym && c->vlosZero;
+    c->phiIso = false; // (a Zeeman-split line's phi holds sin^2 gamma of the ray: it depends on the angle even at rest)
     return retile_profiles(c);
 }
 }

@@ -81,6 +81,7 @@ int lwhip_batch_compute_polarised_profiles(lwhip_batch* b)
     {
         c->stokes.polOnDevice = true;
         c->phiSym = c->phiSym && c->vlosZero;
+        c->phiIso = false; // (phi of a Zeeman-split line depends on the angle even at rest: lwhip_stokes.hip)
     }
     return batch_retile(b, b->ctxs);
 }
