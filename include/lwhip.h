@@ -775,6 +775,10 @@ int lwhip_algorithmic_bytes(lwhip_context* ctx, double* bytes);
 /* Which sweep kernel serves this context (chosen at lwhip_create from its size, LWHIP_SWEEP overrides):
  * 0 the ray-column march (raymarch_kernel), 1 the depth-across-lanes sweep (lanesweep_kernel), 2 the 2D pipeline. */
 int lwhip_sweep_kind(lwhip_context* ctx);
+/* The march on deep columns: the number of wavefronts S a direction's depth points are split over in the
+ * main sweep of this context -- 1, 2 or 4, chosen at lwhip_create so that the split launch fits a workgroup's LDS; 1 for
+ * the lane sweep and for 2D; -1 for a null context. */
+int lwhip_depth_split(lwhip_context* ctx);
 
 #ifdef __cplusplus
 }

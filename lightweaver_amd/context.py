@@ -676,6 +676,11 @@ class Context:
         """'march' (ray-column march), 'lanes' (depth-across-lanes sweep) or '2d': which sweep kernel the library chose."""
         return {0: 'march', 1: 'lanes', 2: '2d'}.get(self.lib.lwhip_sweep_kind(self._h), '?')
 
+    def depth_split(self):
+        """The number of wavefronts (1, 2 or 4) a direction's depth points are split over in this context's main sweep (the
+        march on deep columns); 1 for the lane sweep and for 2D."""
+        return self.lib.lwhip_depth_split(self._h)
+
     def algorithmic_bytes(self):
         b = C.c_double()
         _check(self.lib, self.lib.lwhip_algorithmic_bytes(self._h, C.byref(b)), 'lwhip_algorithmic_bytes')

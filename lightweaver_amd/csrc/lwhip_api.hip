@@ -881,10 +881,10 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
     if (std::getenv("LWHIP_VERBOSE"))
         std::fprintf(stderr,
                      "lwhip_create: Nla=%d Ns=%d Nmu=%d sweep=%s tiles=%d (L=%d, max slots %d, cap %d) chunks=%d x %d waves post=%d maxCT=%d/%d "
-                     "rows=%.1f MB phiT=%.1f MB\n",
+                     "depthSplit=%d rows=%.1f MB phiT=%.1f MB\n",
                      c->Nla, c->Ns, c->Nrays, c->is2d ? "2d" : c->laneSweep ? "depth-lanes" : "ray-column",
                      c->nTiles, c->tileL, c->maxSlotsTile, c->tileCap, c->nTileChunks, c->tileWaves, c->nPostChunks, c->maxCTTile, c->maxCTPost,
-                     c->rowsTileTot * 8e-6, c->phiTTot * 8e-6);
+                     c->depthSplit, c->rowsTileTot * 8e-6, c->phiTTot * 8e-6);
     if (std::getenv("LWHIP_VERBOSE") && c->laneSweep)
         std::fprintf(stderr, "lwhip_create: lane sweep LDS per workgroup: accumulators %zu B + depth arena %zu B + per-wave blocks = %zu B\n",
                      sizeof(double) * (size_t)c->maxCTTile * 4 * (c->laneLR * c->laneD), (size_t)c->depArena.n * sizeof(double),
@@ -1949,6 +1949,13 @@ int lwhip_sweep_kind(lwhip_context* c)
     if (!c)
         return -1;
     return c->is2d ? 2 : c->laneSweep ? 1 : 0;
+}
+
+int lwhip_depth_split(lwhip_context* c)
+{
+    if (!c)
+        return -1;
+    return (c->is2d || c->laneSweep) ? 1 : std::max(1, c->depthSplit);
 }
 
 int lwhip_algorithmic_bytes(lwhip_context* c, double* bytes)

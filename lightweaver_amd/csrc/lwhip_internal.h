@@ -358,7 +358,12 @@ struct RetileArgs
     const double* phi;
     double* phiT;
 };
+// LDS of the march's launches: the one place that sizes them, for the launches and for the checks of build_tables
+// (reads Ns, maxCT, Natom, NlevTot, depthSplit of the argument block).  A workgroup of gfx950 may have LWHIP_LDS_WORKGROUP
+// bytes; LWHIP_LDS_BUDGET is the project's margin below it: what lwhip_create accepts for the unsplit launches.
+enum : size_t { LWHIP_LDS_WORKGROUP = 160 * 1024, LWHIP_LDS_BUDGET = 150 * 1024 };
 size_t raymarch_lds_bytes(const TileArgs& a, int waves, bool fuse);
+size_t tile_post_lds_bytes(const TileArgs& a);
 hipError_t launch_tile_pre(const TileArgs* devArgs, const TileArgs& hostArgs, int nTilesLaunch, const TileArgs* const* apList,
                            int nBatch, hipStream_t stream);
 hipError_t launch_tile_sweep(const TileArgs* devArgs, const TileArgs& hostArgs, const TileDyn& dyn, int solver, int cap,

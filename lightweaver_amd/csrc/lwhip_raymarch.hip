@@ -1547,6 +1547,9 @@ size_t raymarch_lds_bytes(const TileArgs& a, int waves, bool fuse)
     return sizeof(double) * ((size_t)a.maxCT * 4 * a.Ns + std::max(win, post));
 }
 
+// the post-pass as a launch of its own (tile_post_kernel): the dJ row and the threads' level columns
+size_t tile_post_lds_bytes(const TileArgs& a) { return sizeof(double) * (16 + (size_t)(a.Natom + 2 * a.NlevTot) * RM_POST_T); }
+
 hipError_t launch_tile_pre(const TileArgs* devArgs, const TileArgs& a, int nTilesLaunch, const TileArgs* const* apList, int nBatch,
                            hipStream_t stream)
 {
@@ -1660,7 +1663,7 @@ hipError_t launch_tile_post(const TileArgs* devArgs, const TileArgs& a, const Ti
 {
     if (nPostChunks <= 0)
         return hipSuccess;
-    const size_t lds = sizeof(double) * (16 + (size_t)(a.Natom + 2 * a.NlevTot) * RM_POST_T);
+    const size_t lds = tile_post_lds_bytes(a);
     if (lds > 48 * 1024)
     {
         hipError_t e = hipFuncSetAttribute(apList ? (const void*)tile_post_kernel<true> : (const void*)tile_post_kernel<false>,

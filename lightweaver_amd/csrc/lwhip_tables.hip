@@ -1109,25 +1109,8 @@ int build_tables(lwhip_context* c)
             tgtSweep = c->nTiles;
         if (!c->tileFuse)
             tgtSweep = std::max(1, tgtSweep);
-        // Deep columns on the march (round 6): a wavefront's march is ~1.6 us per depth point whatever the number of wavelengths,
-        // so a launch of few tiles over many depth points -- the reference benchmark's 500-point FAL-C: 242 tiles -- leaves most of
-        // the chip idle for 0.8 ms.  While 2 S wavefronts per tile still fit the chip's two-per-SIMD, a direction's depth points
-        // are split over S wavefronts of the tile's workgroup (lwhip_raymarch.hip: raymarch_kernel, depthSplit).
-        // LWHIP_DEPTH_SPLIT=1|2|4 (LWHIP_DEBUG) forces it.
+        // (deep columns on the march: depthSplit is chosen below, once the chunking has fixed maxCTTile)
         c->depthSplit = 1;
-        if (c->tileFuse && c->tileCap == 0 && c->batchHint <= 1 && !c->deterministic)
-        {
-            const long slots = 2L * 4 * numCU; // wavefronts the chip holds at the march's two per SIMD
-            // (measured at 500 points x 2 908 wavelengths, 242 tiles: S = 1 0.804 ms, S = 2 1.088, S = 4 0.652 per sweep -- every
-            // later segment walks its points twice, so the split turns a latency-bound launch (a quarter of the SIMDs busy) into
-            // a throughput-bound one with twice the instructions: a gain only where the unsplit launch leaves most of the chip
-            // idle and four-way; S = 2 is kept for the tests)
-            // (the reference benchmark's grid is 281 tiles = 2 248 wavefronts four-way: 1.10 x the slots, 0.65 against 0.80 ms per sweep)
-            int S = (Ns >= 256 && 8L * c->nTiles <= slots * 3 / 2) ? 4 : 1;
-            S = dbg_env_int("LWHIP_DEPTH_SPLIT", S);
-            if ((S == 2 || S == 4) && Ns >= 64 * S)
-                c->depthSplit = S;
-        }
         c->laneSplit = 1;
         if (c->laneSweep)
         {
@@ -1265,6 +1248,50 @@ int build_tables(lwhip_context* c)
         // both chunkings share one accumulator-slot capacity per kind
         c->maxCTTile = std::max(sw.maxCT, swPrd.maxCT);
         c->maxCTPost = po.maxCT;
+        // LDS of the march's launches, sized where the launches size it (raymarch_lds_bytes, tile_post_lds_bytes)
+        auto march_args = [&](int S) {
+            TileArgs t{};
+            t.Ns = Ns;
+            t.maxCT = c->maxCTTile;
+            t.Natom = c->Natom;
+            t.NlevTot = c->NlevTot;
+            t.depthSplit = S;
+            return t;
+        };
+        // Deep columns on the march (round 6): a wavefront's march is ~1.6 us per depth point whatever the number of wavelengths,
+        // so a launch of few tiles over many depth points -- the reference benchmark's 500-point FAL-C: 242 tiles -- leaves most of
+        // the chip idle for 0.8 ms.  While 2 S wavefronts per tile still fit the chip's two-per-SIMD, a direction's depth points
+        // are split over S wavefronts of the tile's workgroup (lwhip_raymarch.hip: raymarch_split_kernel, depthSplit).
+        // LWHIP_DEPTH_SPLIT=1|2|4 (LWHIP_DEBUG) forces it.
+        // The split launch runs its post-pass on all 128 S threads, each with its level columns in LDS: S is kept only where
+        // that launch (2 S wavefronts, fused: what run_sweep launches) fits the LDS of a workgroup -- known only now that the
+        // chunking has fixed maxCTTile.  H(6) + Ca II(6) at 500 points, three slots: 154 624 of 163 840 bytes; a third active
+        // atom or a fourth slot there is over, and runs unsplit.
+        if (!c->laneSweep && c->tileFuse && c->tileCap == 0 && c->batchHint <= 1 && !c->deterministic)
+        {
+            const long slots = 2L * 4 * numCU; // wavefronts the chip holds at the march's two per SIMD
+            // (measured at 500 points x 2 908 wavelengths, 242 tiles: S = 1 0.804 ms, S = 2 1.088, S = 4 0.652 per sweep -- every
+            // later segment walks its points twice, so the split turns a latency-bound launch (a quarter of the SIMDs busy) into
+            // a throughput-bound one with twice the instructions: a gain only where the unsplit launch leaves most of the chip
+            // idle and four-way; S = 2 is kept for the tests)
+            // (the reference benchmark's grid is 281 tiles = 2 248 wavefronts four-way: 1.10 x the slots, 0.65 against 0.80 ms per sweep)
+            auto fits = [&](int S) { return Ns >= 64 * S && raymarch_lds_bytes(march_args(S), 2 * S, true) <= LWHIP_LDS_WORKGROUP; };
+            const int forced = dbg_env_int("LWHIP_DEPTH_SPLIT", -1);
+            if (forced == -1)
+            {
+                // (four-way or not at all: two-way is the measured loss above)
+                if (Ns >= 256 && 8L * c->nTiles <= slots * 3 / 2 && fits(4))
+                    c->depthSplit = 4;
+            }
+            else if (forced == 2 || forced == 4)
+            {
+                // a forced value is reduced to the largest one that fits: forcing never produces a launch that fails
+                int S = forced;
+                while (S > 1 && !fits(S))
+                    S /= 2;
+                c->depthSplit = S;
+            }
+        }
         auto widen = [&](TileChunking& ck, int maxCT) {
             if (ck.maxCT == maxCT)
                 return;
@@ -1339,11 +1366,18 @@ int build_tables(lwhip_context* c)
             c->nTileChunksPrd = (int)chunkTilePrd.size() - 1;
             c->nPostChunksPrd = (int)postChunkTilePrd.size() - 1;
         }
-        // LDS: the workgroup's accumulators + a 2 KB exchange row per wave (sweep); accumulators + continuum columns (post)
-        const size_t ldsSweep = sizeof(double) * ((size_t)c->maxCTTile * 4 * Ns + std::max((size_t)W * 5 * 16 * 9, (size_t)16 + (size_t)(c->Natom + 2 * c->NlevTot) * 128));
-        const size_t ldsPost = sizeof(double) * (16 + (size_t)(c->Natom + 2 * c->NlevTot) * 128);
-        if (!c->laneSweep && (ldsSweep > 150 * 1024 || ldsPost > 150 * 1024))
-            return fail(LWHIP_ERR_UNSUPPORTED, "problem does not fit the 160 KB LDS budget of one workgroup");
+        // LDS of the launches this context will make.  Unsplit (the iteration where the split is off, its PRD rates pass,
+        // formal_sol, a column batch; W wavefronts, the post-pass fused or a launch of its own): refused beyond the project's
+        // margin.  The split sweep was chosen above to fit the workgroup.  An accepted context never fails at launch for LDS.
+        if (!c->laneSweep)
+        {
+            const TileArgs t1 = march_args(1);
+            const size_t ldsUnsplit = std::max(raymarch_lds_bytes(t1, W, c->tileFuse), raymarch_lds_bytes(t1, W, false));
+            const size_t ldsPost = c->tileFuse ? 0 : tile_post_lds_bytes(t1);
+            const size_t ldsSplit = c->depthSplit > 1 ? raymarch_lds_bytes(march_args(c->depthSplit), 2 * c->depthSplit, true) : 0;
+            if (ldsUnsplit > LWHIP_LDS_BUDGET || ldsPost > LWHIP_LDS_BUDGET || ldsSplit > LWHIP_LDS_WORKGROUP)
+                return fail(LWHIP_ERR_UNSUPPORTED, "problem does not fit the 160 KB LDS budget of one workgroup");
+        }
         if (c->laneSweep && sizeof(double) * (size_t)c->maxCTTile * 4 * (c->laneLR * c->laneD) > 64 * 1024)
             return fail(LWHIP_ERR_UNSUPPORTED, "more transitions per workgroup than the lane sweep's LDS accumulators hold");
     }
