@@ -403,7 +403,8 @@ int lwhip_peer_detach(lwhip_context* ctx);
  * uncached / fine-grained device memory where the runtime offers it, so that a peer's stores are seen by a running kernel. */
 int lwhip_peer_selftest(lwhip_context* ctx, int timeoutMs, int32_t* result);
 
-/* formal_sol: chi/S/solve/I only, optionally up-going rays only (FsMode::FsOnly|UpOnly). */
+/* formal_sol: chi/S/solve/I only, optionally up-going rays only (FsMode::FsOnly|UpOnly).  J, Gamma, the rates and the depth
+ * data (storeDepthData) are left as they are, in 1D and in 2D: only the iteration stores depth data. */
 int lwhip_formal_sol(lwhip_context* ctx, int upOnly);
 
 /* Statistical equilibrium for atom `atom` (index into prob->atoms; -1 = every active atom):
@@ -779,6 +780,15 @@ int lwhip_sweep_kind(lwhip_context* ctx);
  * main sweep of this context -- 1, 2 or 4, chosen at lwhip_create so that the split launch fits a workgroup's LDS; 1 for
  * the lane sweep and for 2D; -1 for a null context. */
 int lwhip_depth_split(lwhip_context* ctx);
+/* What a 2D context launches, from the same host functions its launchers call:
+ *   out[0], out[1]  fs2d_scan_kernel<D, FULL>: columns per lane (1, 2, 4, 8, 16) and whether Nx = 64 D
+ *   out[2]          gather2d_kernel<MAXL>
+ *   out[3 .. 5]     rates2d_kernel<MAXL, MAXM, MAXP>
+ *   out[6], out[7]  wavelengths per batch, wavelength groups of the rates kernel
+ *   out[8]          1: pass 1 reads the packed intersection records, the long characteristics are walked by their own launch
+ *   out[9]          NlongChar of the context's grid
+ * LWHIP_ERR_UNSUPPORTED for a 1D context, LWHIP_ERR_INVALID for a null argument. */
+int lwhip_layout_2d(lwhip_context* ctx, int32_t out[10]);
 
 #ifdef __cplusplus
 }

@@ -681,6 +681,15 @@ class Context:
         march on deep columns); 1 for the lane sweep and for 2D."""
         return self.lib.lwhip_depth_split(self._h)
 
+    def layout_2d(self):
+        """What a 2D context launches (include/lwhip.h: lwhip_layout_2d): scan (D, FULL), gather MAXL, rates (MAXL, MAXM,
+        MAXP), batch2d, groups2d, whether the packed intersection records are in use, NlongChar.  A 1D context raises."""
+        out = (C.c_int32 * 10)()
+        _check(self.lib, self.lib.lwhip_layout_2d(self._h, out), 'lwhip_layout_2d')
+        v = list(out)
+        return {'scan': (v[0], bool(v[1])), 'gather': v[2], 'rates': (v[3], v[4], v[5]), 'batch2d': v[6], 'groups2d': v[7],
+                'packed': bool(v[8]), 'NlongChar': v[9]}
+
     def algorithmic_bytes(self):
         b = C.c_double()
         _check(self.lib, self.lib.lwhip_algorithmic_bytes(self._h, C.byref(b)), 'lwhip_algorithmic_bytes')

@@ -597,8 +597,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(R2D_WA
 }
 }
 
-// ---- formal_sol (intensity only, formal_sol_impl :722-784): the emergent intensity of the up-going rays and, when
-// asked for, I at depth; J, Gamma and the rates stay untouched ---------------------------------------------------
+// ---- formal_sol (intensity only, formal_sol_impl :722-784): the emergent intensity of the up-going rays; J, Gamma, the
+// rates and the depth data stay untouched (intensity_core_opt<.., StoreDepthData = false>, :735) ---------------------
 namespace
 {
 __global__ void __launch_bounds__(256) iout2d_kernel(const Batch2dArgs a)
@@ -606,7 +606,7 @@ __global__ void __launch_bounds__(256) iout2d_kernel(const Batch2dArgs a)
     dbg_poison_lds();
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     const bool planes = a.zUp || a.zDown;
-    if (k >= a.Ns || (!a.storeDepth && !planes && k >= a.Nx))
+    if (k >= a.Ns || (!planes && k >= a.Nx))
         return;
     const int r = blockIdx.y, b = blockIdx.z;
     const int la = a.la0 + b;
@@ -618,14 +618,12 @@ __global__ void __launch_bounds__(256) iout2d_kernel(const Batch2dArgs a)
         a.zDown[((size_t)la * a.Nrays + (ray >> 1)) * a.Nx + (k - (a.Ns - 2 * a.Nx))] = I;
     if ((ray & 1) && k < a.Nx) // Spectrum::I: the top row, written by the toObs ray (:365-370)
         a.Iout[((size_t)la * a.Nrays + (ray >> 1)) * a.Nx + k] = I;
-    if (a.storeDepth)
-        a.depthI[((size_t)la * a.Nrays * 2 + ray) * a.Ns + k] = I;
 }
 }
 
 hipError_t launch_iout2d(const Batch2dArgs& a, hipStream_t stream)
 {
-    const int n = (a.storeDepth || a.zUp || a.zDown) ? a.Ns : a.Nx;
+    const int n = (a.zUp || a.zDown) ? a.Ns : a.Nx;
     LWHIP_LAUNCH(iout2d_kernel, dim3((n + 255) / 256, a.nRaysActive, a.nLa), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
@@ -652,37 +650,83 @@ hipError_t launch_sum_groups(double* red, size_t n, size_t stride, int G, hipStr
     return hipGetLastError();
 }
 
+// The instances the two launchers below pick; lwhip_layout_2d reports the same values.  maxL <= 8 and (2D) maxM <= 4 are
+// checked at lwhip_create; maxP is unbounded: pure continua beyond the instance's MAXP go straight to memory.
+int gather2d_instance(int maxL)
+{
+    return maxL <= 2 ? 2 : maxL <= 4 ? 4 : maxL <= 8 ? 8 : 0;
+}
+
+Rates2dInstance rates2d_instance(int maxL, int maxM, int maxP)
+{
+    if (maxL > 8 || maxM > 4)
+        return { 0, 0, 0 };
+    if (maxL <= 2 && maxM <= 1 && maxP <= 5)
+        return { 2, 1, 5 };
+    if (maxL <= 2 && maxM <= 2 && maxP <= 5)
+        return { 2, 2, 5 };
+    if (maxL <= 2)
+        return { 2, 4, 8 };
+    if (maxL <= 4 && maxM <= 2 && maxP <= 5)
+        return { 4, 2, 5 };
+    if (maxL <= 4)
+        return { 4, 4, 8 };
+    return { 8, 4, 8 };
+}
+
 hipError_t launch_gather2d(const Batch2dArgs& a, int maxL, hipStream_t stream)
 {
     const dim3 grid((a.Ns + 255) / 256, a.nLa);
-    if (maxL <= 2)
+    switch (gather2d_instance(maxL))
+    {
+    case 2:
         LWHIP_LAUNCH(gather2d_kernel<2>, grid, dim3(256), 0, stream, a);
-    else if (maxL <= 4)
+        break;
+    case 4:
         LWHIP_LAUNCH(gather2d_kernel<4>, grid, dim3(256), 0, stream, a);
-    else
+        break;
+    case 8:
         LWHIP_LAUNCH(gather2d_kernel<8>, grid, dim3(256), 0, stream, a);
+        break;
+    default:
+        return hipErrorInvalidValue; // (refused at lwhip_create)
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_rates2d(const Batch2dArgs& a, int maxL, int maxM, int maxP, hipStream_t stream)
 {
-    if (maxM > 4)
+    const Rates2dInstance in = rates2d_instance(maxL, maxM, maxP);
+    // the ray table behind the row block holds 64 half weights and 64 ray indices (refused at lwhip_create: Nrays <= 32)
+    if (in.maxL == 0 || a.nRaysActive > 64)
         return hipErrorInvalidValue; // (refused at lwhip_create)
     const dim3 grid((a.Ns + 127) / 128, a.nGroups);
     const size_t lds = (size_t)std::max(a.maxRowsLa, 1) * 128 * sizeof(double) + 64 * (sizeof(double) + sizeof(int))
-                       + (size_t)((maxL <= 2 ? 2 : (maxL <= 4 ? 4 : 8)) + 4 + 8) * sizeof(DevSlot);
-    if (maxL <= 2 && maxM <= 1 && maxP <= 5)
+                       + (size_t)(in.maxL + 4 + 8) * sizeof(DevSlot);
+    const int key = in.maxL * 100 + in.maxM * 10 + in.maxP;
+    switch (key)
+    {
+    case 215:
         LWHIP_LAUNCH((rates2d_kernel<2, 1, 5>), grid, dim3(128), lds, stream, a);
-    else if (maxL <= 2 && maxM <= 2 && maxP <= 5)
+        break;
+    case 225:
         LWHIP_LAUNCH((rates2d_kernel<2, 2, 5>), grid, dim3(128), lds, stream, a);
-    else if (maxL <= 2)
+        break;
+    case 248:
         LWHIP_LAUNCH((rates2d_kernel<2, 4, 8>), grid, dim3(128), lds, stream, a);
-    else if (maxL <= 4 && maxM <= 2 && maxP <= 5)
+        break;
+    case 425:
         LWHIP_LAUNCH((rates2d_kernel<4, 2, 5>), grid, dim3(128), lds, stream, a);
-    else if (maxL <= 4)
+        break;
+    case 448:
         LWHIP_LAUNCH((rates2d_kernel<4, 4, 8>), grid, dim3(128), lds, stream, a);
-    else
+        break;
+    case 848:
         LWHIP_LAUNCH((rates2d_kernel<8, 4, 8>), grid, dim3(128), lds, stream, a);
+        break;
+    default:
+        return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 }

@@ -1958,6 +1958,28 @@ int lwhip_depth_split(lwhip_context* c)
     return (c->is2d || c->laneSweep) ? 1 : std::max(1, c->depthSplit);
 }
 
+int lwhip_layout_2d(lwhip_context* c, int32_t out[10])
+{
+    if (!c || !out)
+        return fail(LWHIP_ERR_INVALID, "layout_2d: null argument");
+    if (!c->is2d)
+        return fail(LWHIP_ERR_UNSUPPORTED, "layout_2d: not a 2D context");
+    // the same host functions the launchers call (lwhip_fs2d.hip, lwhip_2d.hip) on the same members run_2d passes them
+    const Fs2dScanInstance scan = fs2d_scan_instance(c->Nx);
+    const Rates2dInstance rates = rates2d_instance(c->maxL, c->maxM, c->maxP);
+    out[0] = scan.D;
+    out[1] = scan.full ? 1 : 0;
+    out[2] = gather2d_instance(c->maxL);
+    out[3] = rates.maxL;
+    out[4] = rates.maxM;
+    out[5] = rates.maxP;
+    out[6] = c->batch2d;
+    out[7] = c->groups2d;
+    out[8] = (c->g2.uwS.p && c->g2.dwS.p) ? 1 : 0;
+    out[9] = c->prob.grid2d->NlongChar;
+    return LWHIP_OK;
+}
+
 int lwhip_algorithmic_bytes(lwhip_context* c, double* bytes)
 {
     if (!c || !bytes)

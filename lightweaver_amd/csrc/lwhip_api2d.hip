@@ -27,7 +27,9 @@ int run_2d(lwhip_context* c, int lambdaIterate, int mode)
     a.Nrays = c->Nrays;
     a.nRaysActive = nRaysActive;
     a.lambdaIterate = lambdaIterate;
-    a.storeDepth = (c->prob.storeDepthData && mode != 3) ? 1 : 0;
+    // depth data: the iteration only -- the reference's formal_sol and its PRD rates pass instantiate intensity_core_opt without
+    // StoreDepthData (SimdFullIterationTemplates.hpp:735, PrdTemplates.hpp:67), as the 1D sweeps here do
+    a.storeDepth = (c->prob.storeDepthData && mode == 0) ? 1 : 0;
     a.NlevTot = c->NlevTot;
     a.Natom = c->Natom;
     a.rayList = rayList;
@@ -190,7 +192,8 @@ int lwhip_build_intersections(const lwhip_grid2d* grid, lwhip_intersection* uw, 
     if (st == LWHIP_ERR_INVALID)
         return fail(st, "build_intersections: substepOff / substeps buffers too small");
     if (st != LWHIP_OK)
-        return fail(st, "build_intersections: a long characteristic does not reach a z plane");
+        return fail(st, "build_intersections: a long characteristic does not reach a z plane (a column of no width, or more "
+                        "sub-steps than 32-bit offsets hold)");
     return LWHIP_OK;
 }
 

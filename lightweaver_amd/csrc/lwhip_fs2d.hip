@@ -435,7 +435,12 @@ fs2d_coef_kernel(const Fs2dArgs a)
 
 // Pass 0: the long characteristics, one thread per (wavelength, characteristic).  Inside pass 1 each of them sits alone
 // in a wavefront of short steps (one lane walking 2 ... 16 BESSER sub-steps while 63 wait: 12 % of the wavefronts of
-// the 256 x 82 grid took ~5 times as long as the rest); here they are packed 64 to a wavefront.
+// the 256 x 82 grid took ~5 times as long as the rest); here they are packed 64 to a wavefront.  That count is the 256 x 82
+// grid's, not a limit: the builder (lwhip_geom2d.hip) gives a characteristic one sub-step per x face its ray crosses between
+// two z planes plus the closing hit -- 2 for a steep ray, 155 for muz = 0.21 over 30 km columns with planes 1.2 Mm apart,
+// 5 708 for muz = 0.005 on three 60 km columns with planes 2.2 Mm apart, where the ray wraps round the periodic domain
+// many times (tests/test_fs2d_matrix.py).  f2_long_char walks [substepOff[lc], substepOff[lc + 1]) whatever its length, and
+// lcBuf holds three doubles per characteristic, not per sub-step.
 __global__ void __launch_bounds__(64) fs2d_longchar_kernel(const Fs2dArgs a)
 {
     dbg_poison_lds();
@@ -574,9 +579,20 @@ __global__ void __launch_bounds__(64) fs2d_scan_kernel(const Fs2dArgs a)
 }
 }
 
-template <int D> static void launch_scan(const Fs2dArgs& a, int nSolve, size_t lds, hipStream_t stream)
+// The instance of pass 2 for Nx columns: D = the smallest of 1, 2, 4, 8, 16 columns per lane that covers the row, FULL when
+// the row fills the 64 lanes exactly.
+Fs2dScanInstance fs2d_scan_instance(int Nx)
 {
-    if (a.Nx == 64 * D)
+    const int need = (Nx + 63) / 64;
+    for (int D : { 1, 2, 4, 8, 16 })
+        if (need <= D)
+            return { D, Nx == 64 * D };
+    return { 0, false };
+}
+
+template <int D> static void launch_scan(const Fs2dArgs& a, int nSolve, bool full, size_t lds, hipStream_t stream)
+{
+    if (full)
         LWHIP_LAUNCH((fs2d_scan_kernel<D, true>), dim3(nSolve), dim3(64), lds, stream, a);
     else
         LWHIP_LAUNCH((fs2d_scan_kernel<D, false>), dim3(nSolve), dim3(64), lds, stream, a);
@@ -637,19 +653,27 @@ hipError_t launch_fs2d(const Fs2dArgs& a, int nSolve, hipStream_t stream)
     else
         LWHIP_LAUNCH(fs2d_coef_kernel<true>, grid1, dim3(256), 0, stream, a);
     const size_t lds = ((size_t)a.Nx + 1) * sizeof(double);
-    const int D = (a.Nx + 63) / 64;
-    if (D <= 1)
-        launch_scan<1>(a, nSolve, lds, stream);
-    else if (D <= 2)
-        launch_scan<2>(a, nSolve, lds, stream);
-    else if (D <= 4)
-        launch_scan<4>(a, nSolve, lds, stream);
-    else if (D <= 8)
-        launch_scan<8>(a, nSolve, lds, stream);
-    else if (D <= 16)
-        launch_scan<16>(a, nSolve, lds, stream);
-    else
+    const Fs2dScanInstance inst = fs2d_scan_instance(a.Nx);
+    switch (inst.D)
+    {
+    case 1:
+        launch_scan<1>(a, nSolve, inst.full, lds, stream);
+        break;
+    case 2:
+        launch_scan<2>(a, nSolve, inst.full, lds, stream);
+        break;
+    case 4:
+        launch_scan<4>(a, nSolve, inst.full, lds, stream);
+        break;
+    case 8:
+        launch_scan<8>(a, nSolve, inst.full, lds, stream);
+        break;
+    case 16:
+        launch_scan<16>(a, nSolve, inst.full, lds, stream);
+        break;
+    default:
         return hipErrorInvalidValue; // Nx <= 1024 is checked at the boundary
+    }
     return hipGetLastError();
 }
 

@@ -156,12 +156,30 @@ extern "C" int lwhip_build_intersections_impl(const lwhip_grid2d* grid, lwhip_in
     const bool fill = uwOut != nullptr;
     std::vector<int32_t> off(1, 0);
     std::vector<lwhip_intersection> steps, one;
-    // a long characteristic crosses at most one x face per column and one z plane: more steps than that means the
-    // walk is not converging on a z plane (a ray along x)
-    const size_t maxSteps = (size_t)4 * ((size_t)Nx + Nz) + 16;
+    // The walk of a long characteristic ends: it runs from one z plane to the next (muz != 0, checked by the caller), and on
+    // the way every sub-step crosses one column, so it covers at least the narrowest column's width in x.  Between two planes
+    // the ray moves |dz| |mux / muz| in x; a periodic domain is crossed as often as that takes (a shallow ray wraps round a
+    // narrow grid many times -- the reference's loop, :1286, has no cap at all), and the wrap from the first column onto the
+    // last is no step of its own.  So a walk has at most  max|dz| |mux / muz| / min dx  sub-steps, plus the closing hit and
+    // some slack for hits snapped onto grid lines; more than that means the walk cannot end.  A grid whose bound is not
+    // finite (a column of no width) or beyond the 32-bit sub-step offsets is refused before any walk.
+    double maxDz = 0.0, minDx = std::numeric_limits<double>::infinity();
+    for (int k = 0; k + 1 < Nz; ++k)
+        maxDz = std::fmax(maxDz, std::fabs(grid->z[k + 1] - grid->z[k]));
+    for (int j = 0; j + 1 < Nx; ++j)
+        minDx = std::fmin(minDx, std::fabs(grid->x[j + 1] - grid->x[j]));
+    const double offLimit = (double)std::numeric_limits<int32_t>::max();
     for (int mu = 0; mu < Nrays; ++mu)
         for (int toObsI = 0; toObsI < 2; ++toObsI)
         {
+            size_t maxSteps = 8; // (a vertical ray, fixed x boundaries: no long characteristics)
+            if (grid->periodic && grid->mux[mu] != 0.0)
+            {
+                const double bound = std::ceil(maxDz * std::fabs(grid->mux[mu] / grid->muz[mu]) / minDx) + 8.0;
+                if (!(bound < offLimit))
+                    return LWHIP_ERR_UNSUPPORTED;
+                maxSteps = (size_t)bound;
+            }
             const bool toObs = toObsI != 0;
             Grid g;
             g.x = grid->x;
@@ -220,6 +238,8 @@ extern "C" int lwhip_build_intersections_impl(const lwhip_grid2d* grid, lwhip_in
                         }
                         steps.insert(steps.end(), one.rbegin(), one.rend());
                         steps.push_back(uw);
+                        if ((double)steps.size() > offLimit)
+                            return LWHIP_ERR_UNSUPPORTED;
                         off.push_back((int32_t)steps.size());
                     }
                     lwhip_intersection dw = hit(LWHIP_AXIS_NONE, k, j, 0.0);

@@ -681,6 +681,14 @@ struct Fs2dArgs
     const int32_t* zIdxUp;
 };
 hipError_t launch_fs2d(const Fs2dArgs& a, int nSolve, hipStream_t stream);
+// which fs2d_scan_kernel<D, FULL> serves a grid of Nx columns (the one rule launch_fs2d and lwhip_layout_2d read);
+// D = 0: no instance (Nx > 1024)
+struct Fs2dScanInstance
+{
+    int D;
+    bool full;
+};
+Fs2dScanInstance fs2d_scan_instance(int Nx);
 // packed copy of the n = 2 Nrays Nx Nz intersection records (layout: Fs2dArgs::uwS / uwA); false if a record does not
 // fit the packing (a hit further than one plane from its point), in which case pass 1 reads the records themselves
 bool fs2d_records_packed(const lwhip_intersection* rec, size_t n, int Nx, int Nz, std::vector<double>& s, std::vector<int32_t>& w);
@@ -720,6 +728,14 @@ struct Batch2dArgs
     const int32_t* slotTr;         // global transition of every slot record
     unsigned long long* dJbits;    // [Nla] max_k |1 - Jdag/J| as the bits of a non-negative double
 };
+// which gather2d_kernel<MAXL> / rates2d_kernel<MAXL, MAXM, MAXP> serve a problem with at most maxL lines, maxM mixed and
+// maxP pure continua at one wavelength (the one rule the launchers and lwhip_layout_2d read); MAXL = 0: no instance
+int gather2d_instance(int maxL);
+struct Rates2dInstance
+{
+    int maxL, maxM, maxP;
+};
+Rates2dInstance rates2d_instance(int maxL, int maxM, int maxP);
 hipError_t launch_gather2d(const Batch2dArgs& a, int maxL, hipStream_t stream);
 hipError_t launch_rates2d(const Batch2dArgs& a, int maxL, int maxM, int maxP, hipStream_t stream);
 hipError_t launch_iout2d(const Batch2dArgs& a, hipStream_t stream);

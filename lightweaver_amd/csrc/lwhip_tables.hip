@@ -29,6 +29,12 @@ int validate(const lwhip_problem* p, std::string& why)
             why = "2D grid: 2 <= Nx <= 1024, Nz >= 2, Nx * Nz = Nspace, Nrays matching";
             return LWHIP_ERR_UNSUPPORTED;
         }
+        if (g.Nrays > 32)
+        {
+            // rates2d_kernel keeps the pass's 2 Nrays directions (half weight, ray index) in an LDS table of 64 entries
+            why = "2D grid: Nrays <= 32 (rates2d_kernel's ray table in LDS holds the 64 directions of 32 rays)";
+            return LWHIP_ERR_UNSUPPORTED;
+        }
         if ((g.zLowerBc == LWHIP_BC_CALLABLE) != (p->zLowerBc.type == LWHIP_BC_CALLABLE)
             || (g.zUpperBc == LWHIP_BC_CALLABLE) != (p->zUpperBc.type == LWHIP_BC_CALLABLE))
         {

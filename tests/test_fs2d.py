@@ -99,16 +99,20 @@ def test_hip_2d_besser_matches_oracle(gpu):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('table', ['reference', 'library'])
 @pytest.mark.parametrize('Nx,Nz', [(5, 4), (70, 33), (256, 82)])
-def test_hip_2d_besser_sizes(gpu, Nx, Nz):
-    """Other sizes (incl. BASELINE config 5's 256 x 82) on stencil tables from the reference, where it is
-    present; skipped on the GPU box, which has no reference (the committed fixture covers it there)."""
-    if not HAVE_REF:
-        pytest.skip('needs oracle/_ref for the intersection table')
-    from lightweaver_amd.grid2d import formal_solver_2d
+def test_hip_2d_besser_sizes(gpu, Nx, Nz, table):
+    """Other sizes (incl. BASELINE config 5's 256 x 82) on stencil tables from the library's own builder and, where it
+    is present, from the reference (test_geom2d holds the two tables equal bit for bit)."""
+    from lightweaver_amd.grid2d import build_grid2d, formal_solver_2d
     x, z, mux, muz, T = small_grid_inputs(Nx, Nz, seed=3)
-    ref = bindings.Ref2d(x, z, mux, muz, T)
-    grid = ref.grid()
+    if table == 'reference':
+        if not HAVE_REF:
+            pytest.skip('needs oracle/_ref for the reference\'s intersection table')
+        grid = bindings.Ref2d(x, z, mux, muz, T).grid()
+    else:
+        grid = build_grid2d(x, z, mux, muz, T)
+    assert grid.substepOff.size > 1
     chi, S = fields(grid, 5)
     rays = np.arange(2 * grid.Nrays, dtype=np.int32)
     I, P = formal_solver_2d(grid, 500.0, rays, np.broadcast_to(chi, (6,) + chi.shape), np.broadcast_to(S, (6,) + S.shape))
