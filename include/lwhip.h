@@ -691,6 +691,45 @@ int lwhip_compute_rays(lwhip_context* ctx, const lwhip_rays* rays);
  * lowerBc may differ.  Each column's results are the bits of lwhip_compute_rays on it. */
 int lwhip_batch_compute_rays(lwhip_batch* batch, const lwhip_rays* perColumn);
 
+/* ---- observer rays on a caller-chosen wavelength grid (1D) -----------------------------------------------------------------
+ * LwContext.compute_rays(wavelengths, mus) (Source/LwMiddleLayer.pyx:3898-4002) from the state resident on the device: the
+ * emergent intensity of lwhip_compute_rays on `wavelength` [Nwave] instead of rows of the context's own grid.  What the reference
+ * does for a new grid (lightweaver/atomic_set.py:209-257, LwMiddleLayer.pyx:1960-1963, :2770-2774, :3866):
+ *   - active set: with Nb = searchsorted(old grid, wavelength[0]) and Nr = min(searchsorted(old grid, wavelength[Nwave - 1]) + 1,
+ *     Nlambda) (both from the left), a transition is active iff its rows [Nblue, Nred) of the old grid meet [Nb, Nr); an active
+ *     transition is active on EVERY row of the new grid, an inactive one contributes nothing (lwhip_rays_grid_active);
+ *   - J and, for PRD lines, rhoPrd on the new grid: linear interpolation in wavelength per depth point (J from the old grid,
+ *     rho from the line's own old grid), the end values held outside, a node hit exactly -- numpy.interp.  Formed on the device
+ *     from the RESIDENT J and rho; nothing is downloaded;
+ *   - the background and the continuum cross-sections on the new grid come from the model layer: here they are inputs.
+ * Then chi, S and the piecewise_bezier3_1d march of lwhip_compute_rays (the same kernel, reading the request's rows).  Nothing of
+ * the context changes, nothing is created; the request crosses in one copy, the outputs come back in one.  All pointers are host
+ * pointers.  Not served: Stokes, 2D, wavelength shards, hybrid PRD, a PRD refinement on the new grid. */
+typedef struct lwhip_rays_grid {
+    lwhip_rays rays;              /* Nmu, muz, vz, I, the depth arrays as for lwhip_compute_rays with Nla = Nwave (lowerBc
+                                   * [Nwave, Nmu], I [Nwave, Nmu], depth arrays [Nwave, Nmu, Nspace]); laStart = laEnd = 0 */
+    int32_t Nwave, _pad;          /* >= 2                                                                                */
+    const double* wavelength;     /* [Nwave] nm, finite and strictly increasing                                          */
+    const double* bgChi;          /* [Nwave, Nspace] background opacity, emissivity and scattering on the new grid       */
+    const double* bgEta;
+    const double* bgSca;
+    const double* const* contAlpha; /* [Ntrans_total] in the context's transition order (atoms in order, each atom's
+                                   * transitions in order): entry t -> [Nwave] cross-section of an ACTIVE continuum; ignored
+                                   * (may be NULL) for lines and inactive transitions; NULL itself if no continuum is active */
+} lwhip_rays_grid;
+/* The active set of `wavelength` [Nwave] by the rule above: active[t] = 1 / 0 for every transition, in the order of contAlpha.
+ * Host work only (no device needed).  A null argument, Nwave < 1: LWHIP_ERR_INVALID. */
+int lwhip_rays_grid_active(lwhip_context* ctx, const double* wavelength, int Nwave, int32_t* active);
+/* Refusals, before anything is queued and with the outputs untouched: no device LWHIP_ERR_DEVICE; everything
+ * lwhip_compute_rays refuses; a wavelength shard (J of the other rows is not resident): LWHIP_ERR_UNSUPPORTED; Nwave < 2, a grid
+ * that is not finite or not strictly increasing, a missing background array, a NULL cross-section of an active continuum,
+ * laStart or laEnd other than 0: LWHIP_ERR_INVALID. */
+int lwhip_compute_rays_grid(lwhip_context* ctx, const lwhip_rays_grid* rays);
+/* The same for every column of a batch in one set of launches: perColumn [n]; Nwave, the grid values, Nmu and the presence of the
+ * depth arrays are those of column 0 (LWHIP_ERR_INVALID otherwise, the column named); the backgrounds, cross-sections,
+ * directions, vz and lowerBc are each column's own.  Each column's results are the bits of lwhip_compute_rays_grid on it. */
+int lwhip_batch_compute_rays_grid(lwhip_batch* batch, const lwhip_rays_grid* perColumn);
+
 /* ---- full Stokes along observer rays (1D) --------------------------------------------------------------------------------
  * LwContext.compute_rays(mus, stokes=True) (Source/LwMiddleLayer.pyx:3898-4002) from the state resident on the device: for
  * every wavelength of [laStart, laEnd) and every direction the emergent Stokes vector (I, Q, U, V at k = 0) of the up-going

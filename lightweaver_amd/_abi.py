@@ -168,6 +168,14 @@ class lwhip_rays(C.Structure):
                 ('depthChi', f64p), ('depthEta', f64p), ('depthI', f64p)]
 
 
+class lwhip_rays_grid(C.Structure):
+    """Observer rays of lwhip_compute_rays_grid on a caller-chosen wavelength grid: the lwhip_rays block (laStart = laEnd = 0, Nla
+    = Nwave), the grid [Nwave], the background on it [Nwave, Nspace] and, per transition of the context (atoms in order,
+    transitions in order), the cross-section [Nwave] of an active continuum or NULL (host pointers)."""
+    _fields_ = [('rays', lwhip_rays), ('Nwave', C.c_int32), ('_pad', C.c_int32), ('wavelength', f64p),
+                ('bgChi', f64p), ('bgEta', f64p), ('bgSca', f64p), ('contAlpha', C.POINTER(f64p))]
+
+
 class lwhip_stokes_rays(C.Structure):
     """Observer rays of lwhip_compute_stokes_rays: the lwhip_rays block (no depth arrays), the projections of the field on
     the new directions [Nmu, Nspace] and the Quv output [3, Nla, Nmu] (host pointers)."""
@@ -280,6 +288,9 @@ SYMBOLS = [
     ('lwhip_batch_full_stokes_fs', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(lwhip_iter_result)]),
     ('lwhip_compute_rays', C.c_int, [ctx_p, C.POINTER(lwhip_rays)]),
     ('lwhip_batch_compute_rays', C.c_int, [C.c_void_p, C.POINTER(lwhip_rays)]),
+    ('lwhip_rays_grid_active', C.c_int, [ctx_p, f64p, C.c_int, i32p]),
+    ('lwhip_compute_rays_grid', C.c_int, [ctx_p, C.POINTER(lwhip_rays_grid)]),
+    ('lwhip_batch_compute_rays_grid', C.c_int, [C.c_void_p, C.POINTER(lwhip_rays_grid)]),
     ('lwhip_compute_stokes_rays', C.c_int, [ctx_p, C.POINTER(lwhip_stokes_rays)]),
     ('lwhip_batch_compute_stokes_rays', C.c_int, [C.c_void_p, C.POINTER(lwhip_stokes_rays)]),
     ('lwhip_compute_rays_2d', C.c_int, [ctx_p, C.POINTER(lwhip_rays2d)]),

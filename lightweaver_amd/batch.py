@@ -206,17 +206,38 @@ class ColumnBatch:
 
     # -- emergent spectra along observer rays ------------------------------------------------------------------------------
     def compute_rays(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False, stokes=False, mux=None,
-                     muy=None):
+                     muy=None, wavelengths=None, background=None, contAlpha=None):
         """Context.compute_rays of every column from its device-resident state, all columns in one set of launches and
         one copy back (lwhip_batch_compute_rays; an unfused batch runs the columns one after the other).  The same
         directions and wavelength range for every column; `vz` / `lowerBc`: None, or one array per column.  Returns I
         [Ncolumns, Nla, Nmu], or with depthData a RaysResult whose I, chi, eta, Idepth carry the column axis first.
-        stokes: Context.compute_rays(stokes=True) of every column (lwhip_batch_compute_stokes_rays): [Ncolumns, 4, Nla, Nmu]."""
+        stokes: Context.compute_rays(stokes=True) of every column (lwhip_batch_compute_stokes_rays): [Ncolumns, 4, Nla, Nmu].
+        wavelengths: Context.compute_rays(wavelengths=...) of every column (lwhip_batch_compute_rays_grid): one grid [Nwave]
+        for all columns; `background` a list of (chi, eta, sca) and `contAlpha` a list of dicts, one per column."""
         import ctypes as C
         import numpy as np
         from .context import RaysResult
         n = len(self.contexts)
         per = lambda a, i: None if a is None else a[i]  # noqa: E731
+        if wavelengths is not None:
+            if stokes:
+                raise ValueError('compute_rays: stokes=True is not served on a new wavelength grid')
+            if laStart or laEnd:
+                raise ValueError('compute_rays: laStart / laEnd select rows of the context\'s own grid: leave them 0 with wavelengths')
+            if background is None or len(background) != n or (contAlpha is not None and len(contAlpha) != n):
+                raise ValueError('compute_rays: wavelengths needs background and contAlpha per column')
+            reqs = [c._rays_grid_request(mus, wavelengths, background[i], per(contAlpha, i), per(vz, i), per(lowerBc, i),
+                                         depthData) for i, c in enumerate(self.contexts)]
+            if self._batch is not None:
+                lib = self.contexts[0].lib
+                arr = (abi.lwhip_rays_grid * n)(*[q for q, _, _ in reqs])
+                _check(lib, lib.lwhip_batch_compute_rays_grid(self._batch, arr), 'lwhip_batch_compute_rays_grid')
+            else:
+                for c, (q, _, _) in zip(self.contexts, reqs):
+                    _check(c.lib, c.lib.lwhip_compute_rays_grid(c._h, C.byref(q)), 'lwhip_compute_rays_grid')
+            return self._stack_rays([o for _, o, _ in reqs], depthData)
+        if background is not None or contAlpha is not None:
+            raise ValueError('compute_rays: background / contAlpha go with wavelengths')
         if stokes:
             if depthData:
                 raise ValueError('compute_rays: no depthData with stokes=True')
@@ -239,7 +260,13 @@ class ColumnBatch:
         else:
             for c, (r, _, _) in zip(self.contexts, reqs):
                 _check(c.lib, c.lib.lwhip_compute_rays(c._h, C.byref(r)), 'lwhip_compute_rays')
-        outs = [o for _, o, _ in reqs]
+        return self._stack_rays([o for _, o, _ in reqs], depthData)
+
+    @staticmethod
+    def _stack_rays(outs, depthData):
+        """The columns' RaysResults with the column axis first."""
+        import numpy as np
+        from .context import RaysResult
         I = np.stack([o.I for o in outs]) if outs else np.zeros((0, 0, 0))
         if not depthData:
             return I

@@ -452,15 +452,18 @@ class Context:
                                dJMaxIdx=res.dJMaxIdx if updateJ else 0, crsw=self.crsw)
 
     # -- emergent spectra along observer rays (1D) ------------------------------------------------------------------------
-    def _rays_request(self, mus, laStart, laEnd, vz, lowerBc, depthData):
-        """The lwhip_rays block of one compute_rays call and the arrays it points to: (struct, RaysResult, keepalive)."""
+    def _rays_request(self, mus, laStart, laEnd, vz, lowerBc, depthData, Nwave=None):
+        """The lwhip_rays block of one compute_rays call and the arrays it points to: (struct, RaysResult, keepalive).
+        Nwave: the rows are those of a new wavelength grid (the block's laStart = laEnd = 0)."""
         mus = check_mus(mus)
         Nmu, Ns = mus.shape[0], self.prob.Nspace
         la0 = int(laStart) if (laStart or laEnd) else self.laStart
         la1 = int(laEnd) if laEnd else self.laEnd
+        if Nwave is not None:
+            la0, la1 = 0, int(Nwave)
         nla = max(la1 - la0, 0)
         r = abi.lwhip_rays()
-        r.Nmu, r.laStart, r.laEnd = Nmu, la0, la1
+        r.Nmu, r.laStart, r.laEnd = (Nmu, la0, la1) if Nwave is None else (Nmu, int(laStart), int(laEnd))
         keep = [mus]
         r.muz = mus.ctypes.data_as(abi.f64p)
         if vz is not None:
@@ -499,8 +502,58 @@ class Context:
         q.Quv = out[1:].ctypes.data_as(abi.f64p)
         return q, out, keep + proj
 
+    # -- ... on a caller-chosen wavelength grid ---------------------------------------------------------------------------
+    def _trans_index(self):
+        """(atomIdx, transIdx) of every transition in the library's order: atoms in order, each atom's transitions in order."""
+        return [(ia, kr) for ia, a in enumerate(self.prob.atoms) for kr in range(len(a.trans))]
+
+    def rays_grid_active(self, wavelengths):
+        """Which transitions compute_rays(mus, wavelengths=...) treats as active (lwhip_rays_grid_active: the reference's
+        SpectrumConfiguration.subset_configuration rule): a bool array over the transitions, atoms in order, each atom's
+        transitions in order.  The active continua are the ones whose cross-section `contAlpha` has to carry."""
+        w = np.ascontiguousarray(np.atleast_1d(np.asarray(wavelengths, dtype=np.float64)).reshape(-1))
+        act = np.zeros(len(self._trans_index()), dtype=np.int32)
+        st = self.lib.lwhip_rays_grid_active(self._h, w.ctypes.data_as(abi.f64p), w.shape[0], act.ctypes.data_as(abi.i32p))
+        _check(self.lib, st, 'lwhip_rays_grid_active')
+        return act.astype(bool)
+
+    def _rays_grid_request(self, mus, wavelengths, background, contAlpha, vz, lowerBc, depthData):
+        """The lwhip_rays_grid block of one compute_rays(wavelengths=...) call: (struct, RaysResult, keepalive)."""
+        w = np.ascontiguousarray(np.atleast_1d(np.asarray(wavelengths, dtype=np.float64)).reshape(-1))
+        Nw, Ns = w.shape[0], self.prob.Nspace
+        if background is None or len(background) != 3:
+            raise ValueError('compute_rays: wavelengths needs background=(chi, eta, sca), each [Nwave, Nspace]')
+        r, out, keep = self._rays_request(mus, 0, 0, vz, lowerBc, depthData, Nwave=Nw)
+        q = abi.lwhip_rays_grid()
+        q.rays = r
+        q.Nwave = Nw
+        q.wavelength = w.ctypes.data_as(abi.f64p)
+        keep.append(w)
+        for name, a in zip(('bgChi', 'bgEta', 'bgSca'), background):
+            if a is None:
+                continue    # (the library refuses the request and names the array)
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (Nw, Ns):
+                raise ValueError(f'compute_rays: background {name} must be [Nwave, Nspace]')
+            keep.append(a)
+            setattr(q, name, a.ctypes.data_as(abi.f64p))
+        index = self._trans_index()
+        ptrs = (abi.f64p * max(len(index), 1))()
+        for key, a in (contAlpha or {}).items():
+            key = (int(key[0]), int(key[1]))
+            if key not in index:
+                raise ValueError(f'compute_rays: contAlpha names no transition {key}')
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (Nw,):
+                raise ValueError('compute_rays: a contAlpha entry must be [Nwave]')
+            keep.append(a)
+            ptrs[index.index(key)] = a.ctypes.data_as(abi.f64p)
+        q.contAlpha = C.cast(ptrs, C.POINTER(abi.f64p))
+        keep.append(ptrs)
+        return q, out, keep
+
     def compute_rays(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False, squeeze=True, stokes=False,
-                     mux=None, muy=None):
+                     mux=None, muy=None, wavelengths=None, background=None, contAlpha=None):
         """LwContext.compute_rays(mus, upOnly=True) (Source/LwMiddleLayer.pyx:3898-4002) from the state that is resident on
         the device: the emergent intensity I [Nla, Nmu] of the up-going rays with direction cosines `mus` (any values in
         (0, 1], no weights), over the wavelengths [laStart, laEnd) of the global grid (default: all this context holds).
@@ -515,7 +568,29 @@ class Context:
         / `muy` [Nmu] place the directions in azimuth (default mux = sqrt(1 - mu^2), muy = 0, the reference's 1D convention).
         As in the reference this I carries no scattering term (J dagger = 0 without updateJ), so it is not the I of
         stokes=False where the background scatters; Q, U, V are exact zeros where no polarised line is active; any 1D
-        formal solver is accepted.  No depthData."""
+        formal solver is accepted.  No depthData.
+        wavelengths: LwContext.compute_rays(wavelengths, mus): the same on a grid [Nwave] of the caller's choice (nm, strictly
+        increasing) instead of rows of the context's own -- lwhip_compute_rays_grid.  The transitions whose rows of the old
+        grid meet the span of the new one (rays_grid_active) are active on every new wavelength; J and the PRD lines' rho are
+        interpolated linearly in wavelength on the device from the resident arrays (numpy.interp, end values held).  What the
+        reference's model layer supplies is an input here: background = (chi, eta, sca), each [Nwave, Nspace], and
+        contAlpha = {(atomIdx, transIdx): alpha [Nwave]} for every active continuum.  laStart / laEnd must stay 0; lowerBc is
+        [Nwave, Nmu]; the results have Nwave for Nla.  Not with stokes=True, not on a shard, a 2D or hybrid-PRD context."""
+        if wavelengths is not None:
+            if stokes:
+                raise ValueError('compute_rays: stokes=True is not served on a new wavelength grid')
+            if laStart or laEnd:
+                raise ValueError('compute_rays: laStart / laEnd select rows of the context\'s own grid: leave them 0 with wavelengths')
+            q, out, keep = self._rays_grid_request(mus, wavelengths, background, contAlpha, vz, lowerBc, depthData)
+            _check(self.lib, self.lib.lwhip_compute_rays_grid(self._h, C.byref(q)), 'lwhip_compute_rays_grid')
+            del keep
+            if squeeze and np.ndim(mus) == 0:
+                out.I = out.I[:, 0]
+                if depthData:
+                    out.chi, out.eta, out.Idepth = out.chi[:, 0], out.eta[:, 0], out.Idepth[:, 0]
+            return out if depthData else out.I
+        if background is not None or contAlpha is not None:
+            raise ValueError('compute_rays: background / contAlpha go with wavelengths')
         if stokes:
             if depthData:
                 raise ValueError('compute_rays: no depthData with stokes=True')

@@ -21,6 +21,10 @@
 // FormalScalar.cpp:209-325: five dependent operations per depth point) and stores I(k = 0).  Every quantity is formed by
 // the operations of the serial algorithm, only not in its order in time.  R is chosen by the host so that R x Ns fills
 // whole passes of 256 threads within 40 KB of LDS (eight arrays of R x Ns doubles): 6 rays at 82 depth points.
+//
+// lwhip_compute_rays_grid / lwhip_batch_compute_rays_grid: the same on a wavelength grid of the caller's choice.  The kernel's
+// row sources are pointers of the column's record; for a new grid they point at the request's rows (staged background, par and
+// transition records; J and rho interpolated on the device by rays_grid_rows_kernel) instead of the context's.
 #include "lwhip_host.h"
 #include "lwhip_device.h"
 // H(a, v) under the same contraction setting as the stored profiles' unit: the same argument gives the same bits
@@ -436,133 +440,32 @@ namespace
 {
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// The call: cols[i] with request reqs[i], everything on cols[0]'s stream, staged through `st`.
-int rays_run(lwhip_context* const* cols, int n, const lwhip_rays* reqs, RaysState*& slot, const char* whatC)
+// what a column's outputs take in the `out` buffer: I [nla, Nmu], then chi, eta, I(k) [nla, Nmu, Ns] each
+size_t rays_out_bytes(size_t nRayCol, int Ns, bool depth) { return (nRayCol + (depth ? 3 * nRayCol * Ns : 0)) * sizeof(double); }
+
+// The end of a call: the staged block (st.inPinned, whose first bytes are the columns' RayCol records) goes up in one copy,
+// one launch of rays_kernel over rows [la0, la0 + nla) of what the records point at, one copy back, one wait, and every
+// column's outputs into its request's arrays.  `pre`: queued between the copy and the launch (the rows a new grid needs).
+template <typename Pre>
+int rays_launch_fetch(lwhip_context* c0, RaysState& st, const std::vector<const lwhip_rays*>& reqs, int Ns, int Nmu, int la0,
+                      int nla, size_t inBytes, const std::string& what, Pre pre)
 {
-    const std::string what(whatC);
-    if (lwhip_device_count() <= 0)
-        return fail(LWHIP_ERR_DEVICE, what + ": no gfx950 device");
-    if (n <= 0 || !cols || !reqs)
-        return fail(LWHIP_ERR_INVALID, what + ": null " + (n > 1 ? "batch" : "context") + " or request");
-    int la0 = 0, la1 = 0;
-    for (int i = 0; i < n; ++i)
-    {
-        int a0 = 0, a1 = 0;
-        const int chk = rays_check(cols[i], reqs + i, what, false, a0, a1);
-        if (chk != LWHIP_OK)
-            return n > 1 ? fail(chk, std::string(lwhip_last_error()) + " (column " + std::to_string(i) + ")") : chk;
-        if (i == 0)
-        {
-            la0 = a0;
-            la1 = a1;
-        }
-        const lwhip_context* c = cols[i];
-        if (c->Ns != cols[0]->Ns || c->device != cols[0]->device || reqs[i].Nmu != reqs[0].Nmu || a0 != la0 || a1 != la1
-            || (reqs[i].depthI != nullptr) != (reqs[0].depthI != nullptr))
-            return fail(LWHIP_ERR_INVALID, what + ": column " + std::to_string(i)
-                                               + " differs from column 0 (depth points, Nmu, wavelength range and depth outputs "
-                                                 "are the same for every column)");
-    }
-    lwhip_context* c0 = cols[0];
-    const int Ns = c0->Ns, Nmu = reqs[0].Nmu, nla = la1 - la0;
-    const bool depth = reqs[0].depthI != nullptr;
-    HIP_TRY(hipSetDevice(c0->device));
-    HIP_TRY(rays_init_table(c0->device));
-    std::vector<RaysState*> tabs(n);
-    for (int i = 0; i < n; ++i)
-    {
-        lwhip_context* o = cols[i]->tablesFrom ? cols[i]->tablesFrom : cols[i];
-        const int stp = rays_tables(o, tabs[i]);
-        if (stp != LWHIP_OK)
-            return stp;
-    }
-    RaysState& st = *rays_state(slot);
-    // ---- the staged request: [RayCol x n | vz | lowerBc], one copy up ------------------------------------------------------
+    const int n = (int)reqs.size();
+    const bool depth = reqs[0]->depthI != nullptr;
     const size_t nRayCol = (size_t)nla * Nmu;
-    const size_t colsBytes = align256((size_t)n * sizeof(RayCol));
-    size_t inBytes = colsBytes;
-    std::vector<size_t> vzOff(n, 0), bcOff(n, 0);
-    for (int i = 0; i < n; ++i)
-    {
-        if (reqs[i].vz)
-        {
-            vzOff[i] = inBytes;
-            inBytes += align256((size_t)Ns * sizeof(double));
-        }
-        if (cols[i]->prob.zLowerBc.type == LWHIP_BC_CALLABLE)
-        {
-            bcOff[i] = inBytes;
-            inBytes += align256(nRayCol * sizeof(double));
-        }
-    }
-    const size_t perColOut = (nRayCol + (depth ? 3 * nRayCol * Ns : 0)) * sizeof(double);
+    const size_t perColOut = rays_out_bytes(nRayCol, Ns, depth);
     const size_t outBytes = (size_t)n * perColOut;
-    if (st.in.n < inBytes || st.out.n < outBytes)
-    {
-        HIP_TRY(hipStreamSynchronize(c0->stream));
-        if (st.in.n < inBytes)
-            HIP_TRY(st.in.alloc(c0->mem, inBytes, false));
-        if (st.out.n < outBytes)
-            HIP_TRY(st.out.alloc(c0->mem, outBytes, false));
-    }
-    HIP_TRY(st.inPinned.reserve(c0->device, inBytes, c0->stream));
-    HIP_TRY(st.outPinned.reserve(c0->device, outBytes, c0->stream));
     unsigned char* hin = st.inPinned.as<unsigned char>();
-    RayCol* hc = (RayCol*)hin;
-    for (int i = 0; i < n; ++i)
-    {
-        lwhip_context* c = cols[i];
-        const lwhip_rays& r = reqs[i];
-        RayCol a{};
-        a.height = c->height.p;
-        a.temperature = c->temperature.p;
-        a.wavelength = c->wavelength.p;
-        a.bgChi = c->bgChi.p;
-        a.bgEta = c->bgEta.p;
-        a.bgSca = c->bgSca.p;
-        a.J = c->J.p;
-        a.n = c->n.p;
-        a.ratio = c->ratio.p;
-        a.par = c->par.p;
-        a.rho = c->rho.p;
-        a.vlosMu = c->vlosMu.p;
-        a.muzCtx = c->muz.p;
-        a.vBroad = c->vBroad.p;
-        a.aDamp = c->aDamp.p;
-        a.lineWave = c->lineWave.p;
-        a.tr = tabs[i]->tr.p;
-        a.laOff = tabs[i]->laOff.p;
-        a.laTr = tabs[i]->laTr.p;
-        if (r.vz)
-        {
-            std::memcpy(hin + vzOff[i], r.vz, (size_t)Ns * sizeof(double));
-            a.vz = (const double*)(st.in.p + vzOff[i]);
-        }
-        a.lowerType = c->prob.zLowerBc.type;
-        if (a.lowerType == LWHIP_BC_CALLABLE)
-        {
-            std::memcpy(hin + bcOff[i], r.lowerBc, nRayCol * sizeof(double));
-            a.lowerBc = (const double*)(st.in.p + bcOff[i]);
-        }
-        double* o = (double*)(st.out.p + (size_t)i * perColOut);
-        a.I = o;
-        if (depth)
-        {
-            a.depthChi = o + nRayCol;
-            a.depthEta = o + nRayCol + nRayCol * Ns;
-            a.depthI = o + nRayCol + 2 * nRayCol * Ns;
-        }
-        for (int m = 0; m < Nmu; ++m)
-            a.mu[m] = r.muz[m];
-        hc[i] = a;
-    }
     HIP_TRY(c0->mem.h2d(st.in.p, hin, inBytes));
+    const int stp = pre();
+    if (stp != LWHIP_OK)
+        return stp;
     // ---- one launch ------------------------------------------------------------------------------------------------------------
     RaysArgs g{};
     g.cols = (const RayCol*)st.in.p;
     g.Ns = Ns;
     g.Nmu = Nmu;
-    g.la0 = la0 - c0->laStart;
+    g.la0 = la0;
     g.nla = nla;
     g.R = rays_per_group(Ns);
     g.blocksPerCol = (int)((nRayCol + g.R - 1) / g.R);
@@ -579,15 +482,440 @@ int rays_run(lwhip_context* const* cols, int n, const lwhip_rays* reqs, RaysStat
     for (int i = 0; i < n; ++i)
     {
         const double* o = (const double*)(hout + (size_t)i * perColOut);
-        std::memcpy(reqs[i].I, o, nRayCol * sizeof(double));
+        std::memcpy(reqs[i]->I, o, nRayCol * sizeof(double));
         if (depth)
         {
-            std::memcpy(reqs[i].depthChi, o + nRayCol, nRayCol * Ns * sizeof(double));
-            std::memcpy(reqs[i].depthEta, o + nRayCol + nRayCol * Ns, nRayCol * Ns * sizeof(double));
-            std::memcpy(reqs[i].depthI, o + nRayCol + 2 * nRayCol * Ns, nRayCol * Ns * sizeof(double));
+            std::memcpy(reqs[i]->depthChi, o + nRayCol, nRayCol * Ns * sizeof(double));
+            std::memcpy(reqs[i]->depthEta, o + nRayCol + nRayCol * Ns, nRayCol * Ns * sizeof(double));
+            std::memcpy(reqs[i]->depthI, o + nRayCol + 2 * nRayCol * Ns, nRayCol * Ns * sizeof(double));
         }
     }
     return LWHIP_OK;
+}
+
+// the context's resident state as a column's record reads it; the rows of a wavelength grid are filled in by the caller
+RayCol rays_col_base(const lwhip_context* c, const lwhip_rays& r)
+{
+    RayCol a{};
+    a.height = c->height.p;
+    a.temperature = c->temperature.p;
+    a.n = c->n.p;
+    a.ratio = c->ratio.p;
+    a.vlosMu = c->vlosMu.p;
+    a.muzCtx = c->muz.p;
+    a.vBroad = c->vBroad.p;
+    a.aDamp = c->aDamp.p;
+    a.lowerType = c->prob.zLowerBc.type;
+    for (int m = 0; m < r.Nmu; ++m)
+        a.mu[m] = r.muz[m];
+    return a;
+}
+
+// ---- a new wavelength grid -----------------------------------------------------------------------------------------------------
+// The active set of the grid w [Nwave] (lightweaver/atomic_set.py:209-257): the rows [Nb, Nr) of the old grid it spans, both
+// searches from the left; a transition is active iff its old rows [Nblue, Nred) meet them.  The one place the rule lives.
+void grid_active(const lwhip_context* c, const double* w, int Nwave, std::vector<int32_t>& active)
+{
+    const double* old = c->prob.wavelength;
+    const int N = c->prob.Nlambda;
+    const int Nb = (int)(std::lower_bound(old, old + N, w[0]) - old);
+    const int Nr = std::min((int)(std::lower_bound(old, old + N, w[Nwave - 1]) - old) + 1, N);
+    active.assign(c->trans.size(), 0);
+    for (size_t t = 0; t < c->trans.size(); ++t)
+        active[t] = std::max(Nb, c->trans[t].t.Nblue) < std::min(Nr, c->trans[t].t.Nred) ? 1 : 0;
+}
+
+// what a new grid adds to the refusals of rays_check; the active set comes back
+int grid_check(lwhip_context* c, const lwhip_rays_grid* q, const std::string& what, std::vector<int32_t>& active)
+{
+    if (c->worldSize > 1 || c->laStart != 0 || c->laEnd != c->prob.Nlambda)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": not on a wavelength shard (J of the other rows is not resident)");
+    if (q->Nwave < 2)
+        return fail(LWHIP_ERR_INVALID, what + ": Nwave >= 2 is required");
+    if (!q->wavelength)
+        return fail(LWHIP_ERR_INVALID, what + ": wavelength is required");
+    for (int l = 0; l < q->Nwave; ++l)
+    {
+        if (!std::isfinite(q->wavelength[l]))
+            return fail(LWHIP_ERR_INVALID, what + ": wavelength " + std::to_string(l) + " is not finite");
+        if (l > 0 && !(q->wavelength[l] > q->wavelength[l - 1]))
+            return fail(LWHIP_ERR_INVALID, what + ": the wavelengths are not strictly increasing (at " + std::to_string(l) + ")");
+    }
+    if (!q->bgChi || !q->bgEta || !q->bgSca)
+        return fail(LWHIP_ERR_INVALID, what + ": bgChi, bgEta and bgSca [Nwave, Nspace] are required (missing: "
+                                           + (!q->bgChi ? "bgChi" : !q->bgEta ? "bgEta" : "bgSca") + ")");
+    grid_active(c, q->wavelength, q->Nwave, active);
+    for (size_t t = 0; t < c->trans.size(); ++t)
+        if (active[t] && c->trans[t].t.type != LWHIP_LINE && (!q->contAlpha || !q->contAlpha[t]))
+            return fail(LWHIP_ERR_INVALID, what + ": contAlpha of transition " + std::to_string(t)
+                                               + " is NULL (an active continuum needs its cross-section [Nwave])");
+    return LWHIP_OK;
+}
+
+// One row-interpolation of the prep kernel: f [nOld, Ns] given at x [nOld] -> out [Nwave, Ns] at the new wavelengths.
+struct InterpJob
+{
+    const double* x;
+    const double* f;
+    double* out;
+    int32_t nOld, _pad;
+};
+struct InterpArgs
+{
+    const InterpJob* jobs;
+    const double* xNew;
+    int32_t nJobs, Nwave, Ns, _pad;
+};
+
+// numpy.interp at one point: the bracket x[j] <= xv < x[j + 1], slope (xv - x[j]) + f[j]; the end values held outside the
+// grid; a node gives its value exactly.  f is strided by Ns (one depth point's column of a [rows, Ns] array).
+__device__ double d_interp_row(const double* x, const double* f, int n, int Ns, double xv)
+{
+    if (xv > x[n - 1])
+        return f[(size_t)(n - 1) * Ns];
+    if (xv < x[0])
+        return f[0];
+    int lo = 0, hi = n - 1; // x[lo] <= xv throughout
+    while (hi - lo > 1)
+    {
+        const int mid = (lo + hi) >> 1;
+        if (x[mid] <= xv)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    if (x[hi] <= xv) // (the last node itself)
+        lo = hi;
+    if (lo == n - 1 || x[lo] == xv)
+        return f[(size_t)lo * Ns];
+    const double f0 = f[(size_t)lo * Ns], f1 = f[(size_t)(lo + 1) * Ns];
+    const double slope = (f1 - f0) / (x[lo + 1] - x[lo]);
+    return slope * (xv - x[lo]) + f0;
+}
+
+// J and rho of the PRD lines on the new grid, from the resident arrays: a thread per (new wavelength, depth point), depth
+// fastest (the reads of a row and the stores are contiguous in k); the jobs along y.
+__global__ void __launch_bounds__(RAYS_THREADS) rays_grid_rows_kernel(const InterpArgs g)
+{
+    const int nPt = g.Nwave * g.Ns;
+    for (int j = blockIdx.y; j < g.nJobs; j += gridDim.y)
+    {
+        const InterpJob job = g.jobs[j];
+        for (int idx = blockIdx.x * RAYS_THREADS + threadIdx.x; idx < nPt; idx += gridDim.x * RAYS_THREADS)
+        {
+            const int l = idx / g.Ns, k = idx - l * g.Ns;
+            job.out[idx] = d_interp_row(job.x, job.f + k, job.nOld, g.Ns, g.xNew[l]);
+        }
+    }
+}
+
+// a staged block's layout, piece by piece
+struct Stage
+{
+    size_t bytes = 0;
+    size_t take(size_t b)
+    {
+        const size_t at = bytes;
+        bytes += align256(b);
+        return at;
+    }
+};
+
+// The call: cols[i] with request reqs[i], everything on cols[0]'s stream, staged through `st`.  grids: empty, or the new-grid
+// requests reqs[i] is embedded in -- then the rows the kernel reads are the request's, not the context's.
+int rays_run(lwhip_context* const* cols, int n, const std::vector<const lwhip_rays*>& reqs,
+             const std::vector<const lwhip_rays_grid*>& grids, RaysState*& slot, const std::string& what)
+{
+    const bool grid = !grids.empty();
+    int la0 = 0, la1 = 0;
+    std::vector<int32_t> active; // (new grid) of column 0, which every column shares
+    for (int i = 0; i < n; ++i)
+    {
+        auto named = [&](int code) {
+            return n > 1 ? fail(code, std::string(lwhip_last_error()) + " (column " + std::to_string(i) + ")") : code;
+        };
+        if (grid && (reqs[i]->laStart != 0 || reqs[i]->laEnd != 0))
+            return fail(LWHIP_ERR_INVALID, what + ": laStart and laEnd must be 0 with a wavelength grid (they select rows of the "
+                                               "context's own)" + (n > 1 ? " (column " + std::to_string(i) + ")" : ""));
+        int a0 = 0, a1 = 0;
+        const int chk = rays_check(cols[i], reqs[i], what, false, a0, a1);
+        if (chk != LWHIP_OK)
+            return named(chk);
+        if (i == 0)
+        {
+            la0 = a0;
+            la1 = a1;
+        }
+        const lwhip_context* c = cols[i];
+        if (c->Ns != cols[0]->Ns || c->device != cols[0]->device || reqs[i]->Nmu != reqs[0]->Nmu || a0 != la0 || a1 != la1
+            || (reqs[i]->depthI != nullptr) != (reqs[0]->depthI != nullptr))
+            return fail(LWHIP_ERR_INVALID, what + ": column " + std::to_string(i)
+                                               + " differs from column 0 (depth points, Nmu, wavelength range and depth outputs "
+                                                 "are the same for every column)");
+        if (grid)
+        {
+            std::vector<int32_t> act;
+            const int gchk = grid_check(cols[i], grids[i], what, act);
+            if (gchk != LWHIP_OK)
+                return named(gchk);
+            if (i == 0)
+                active = act;
+            else if (grids[i]->Nwave != grids[0]->Nwave
+                     || std::memcmp(grids[i]->wavelength, grids[0]->wavelength, (size_t)grids[0]->Nwave * sizeof(double)) != 0
+                     || act != active)
+                return fail(LWHIP_ERR_INVALID, what + ": column " + std::to_string(i)
+                                                   + " differs from column 0 (Nwave, the wavelengths and the active transitions "
+                                                     "are the same for every column)");
+        }
+    }
+    lwhip_context* c0 = cols[0];
+    const int Ns = c0->Ns, Nmu = reqs[0]->Nmu, nla = grid ? grids[0]->Nwave : la1 - la0;
+    const bool depth = reqs[0]->depthI != nullptr;
+    HIP_TRY(hipSetDevice(c0->device));
+    HIP_TRY(rays_init_table(c0->device));
+    std::vector<RaysState*> tabs(n, nullptr);
+    for (int i = 0; i < n && !grid; ++i)
+    {
+        lwhip_context* o = cols[i]->tablesFrom ? cols[i]->tablesFrom : cols[i];
+        const int stp = rays_tables(o, tabs[i]);
+        if (stp != LWHIP_OK)
+            return stp;
+    }
+    RaysState& st = *rays_state(slot);
+    // ---- the staged request: [RayCol x n | vz | lowerBc], one copy up ------------------------------------------------------
+    // a new grid adds [wavelength | row lists] once and per column [RayTrans | par | bgChi | bgEta | bgSca], then the jobs of
+    // the prep kernel; the rows that kernel fills (J', rho' of each active PRD line) follow the outputs in st.out
+    const size_t nRayCol = (size_t)nla * Nmu;
+    const size_t rowBytes = (size_t)nla * Ns * sizeof(double);
+    Stage in, rows;
+    in.take((size_t)n * sizeof(RayCol));
+    std::vector<int> act; // the active transitions, context order
+    for (size_t t = 0; t < active.size(); ++t)
+        if (active[t])
+            act.push_back((int)t);
+    const size_t nA = act.size();
+    std::vector<int> prdLines; // positions in `act` of the lines that carry rho
+    if (grid)
+        for (size_t a = 0; a < nA; ++a)
+        {
+            const HostTrans& h = c0->trans[act[a]];
+            if (h.t.type == LWHIP_LINE && h.t.prd && h.rhoOff >= 0)
+                prdLines.push_back((int)a);
+        }
+    const size_t jobsPerCol = 1 + prdLines.size();
+    size_t waveOff = 0, laOffOff = 0, laTrOff = 0, jobsOff = 0;
+    if (grid)
+    {
+        waveOff = in.take((size_t)nla * sizeof(double));
+        laOffOff = in.take((size_t)(nla + 1) * sizeof(int32_t));
+        laTrOff = in.take(std::max<size_t>((size_t)nla * nA, 1) * sizeof(int32_t));
+        jobsOff = in.take((size_t)n * jobsPerCol * sizeof(InterpJob));
+    }
+    std::vector<size_t> vzOff(n, 0), bcOff(n, 0), trOff(n, 0), parOff(n, 0), bgOff(n, 0), rowsOff(n, 0);
+    for (int i = 0; i < n; ++i)
+    {
+        if (reqs[i]->vz)
+            vzOff[i] = in.take((size_t)Ns * sizeof(double));
+        if (cols[i]->prob.zLowerBc.type == LWHIP_BC_CALLABLE)
+            bcOff[i] = in.take(nRayCol * sizeof(double));
+        if (grid)
+        {
+            trOff[i] = in.take(std::max<size_t>(nA, 1) * sizeof(RayTrans));
+            parOff[i] = in.take(std::max<size_t>(nA * 4 * nla, 1) * sizeof(double));
+            bgOff[i] = in.take(3 * rowBytes);
+            rowsOff[i] = rows.take(jobsPerCol * rowBytes);
+        }
+    }
+    const size_t inBytes = in.bytes;
+    const size_t perColOut = rays_out_bytes(nRayCol, Ns, depth);
+    const size_t outBytes = (size_t)n * perColOut;
+    // (the rows a new grid needs are device-only: they follow the outputs in the `out` buffer and are not copied back)
+    const size_t rowsBase = align256(outBytes);
+    if (st.in.n < inBytes || st.out.n < rowsBase + rows.bytes)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        if (st.in.n < inBytes)
+            HIP_TRY(st.in.alloc(c0->mem, inBytes, false));
+        if (st.out.n < rowsBase + rows.bytes)
+            HIP_TRY(st.out.alloc(c0->mem, rowsBase + rows.bytes, false));
+    }
+    HIP_TRY(st.inPinned.reserve(c0->device, inBytes, c0->stream));
+    HIP_TRY(st.outPinned.reserve(c0->device, outBytes, c0->stream));
+    unsigned char* hin = st.inPinned.as<unsigned char>();
+    RayCol* hc = (RayCol*)hin;
+    if (grid)
+    {
+        // every active transition on every row, reference order
+        std::memcpy(hin + waveOff, grids[0]->wavelength, (size_t)nla * sizeof(double));
+        int32_t* lo = (int32_t*)(hin + laOffOff);
+        int32_t* lt = (int32_t*)(hin + laTrOff);
+        for (int l = 0; l <= nla; ++l)
+            lo[l] = (int32_t)((size_t)l * nA);
+        for (size_t e = 0; e < (size_t)nla * nA; ++e)
+            lt[e] = (int32_t)(e % nA);
+    }
+    for (int i = 0; i < n; ++i)
+    {
+        lwhip_context* c = cols[i];
+        const lwhip_rays& r = *reqs[i];
+        RayCol a = rays_col_base(c, r);
+        if (!grid)
+        {
+            a.wavelength = c->wavelength.p;
+            a.bgChi = c->bgChi.p;
+            a.bgEta = c->bgEta.p;
+            a.bgSca = c->bgSca.p;
+            a.J = c->J.p;
+            a.par = c->par.p;
+            a.rho = c->rho.p;
+            a.lineWave = c->lineWave.p;
+            a.tr = tabs[i]->tr.p;
+            a.laOff = tabs[i]->laOff.p;
+            a.laTr = tabs[i]->laTr.p;
+        }
+        else
+        {
+            const lwhip_rays_grid& q = *grids[i];
+            const double* wl = q.wavelength;
+            double* rowsDev = (double*)(st.out.p + rowsBase + rowsOff[i]); // J', then rho' of each PRD line
+            const size_t rowLen = (size_t)nla * Ns;
+            a.wavelength = a.lineWave = (const double*)(st.in.p + waveOff);
+            std::memcpy(hin + bgOff[i], q.bgChi, rowBytes);
+            std::memcpy(hin + bgOff[i] + rowBytes, q.bgEta, rowBytes);
+            std::memcpy(hin + bgOff[i] + 2 * rowBytes, q.bgSca, rowBytes);
+            a.bgChi = (const double*)(st.in.p + bgOff[i]);
+            a.bgEta = a.bgChi + rowLen;
+            a.bgSca = a.bgEta + rowLen;
+            a.J = rowsDev;
+            a.rho = rowsDev;
+            a.par = (const double*)(st.in.p + parOff[i]);
+            a.tr = (const RayTrans*)(st.in.p + trOff[i]);
+            a.laOff = (const int32_t*)(st.in.p + laOffOff);
+            a.laTr = (const int32_t*)(st.in.p + laTrOff);
+            InterpJob* jobs = (InterpJob*)(hin + jobsOff) + (size_t)i * jobsPerCol;
+            jobs[0] = InterpJob{ c->wavelength.p, c->J.p, rowsDev, c->Nla, 0 };
+            RayTrans* trs = (RayTrans*)(hin + trOff[i]);
+            double* par = (double*)(hin + parOff[i]);
+            const std::vector<LineEval> ev = line_eval_records(c->trans);
+            size_t nPrd = 0;
+            for (size_t k = 0; k < nA; ++k)
+            {
+                const HostTrans& h = c->trans[act[k]];
+                RayTrans t{};
+                t.type = h.t.type;
+                t.gi = c->levelOff[h.atom] + h.t.i;
+                t.gj = c->levelOff[h.atom] + h.t.j;
+                t.Nblue = 0;
+                t.prd = (h.t.type == LWHIP_LINE && h.t.prd && h.rhoOff >= 0) ? 1 : 0;
+                t.row = ev[act[k]].row;
+                t.atom = ev[act[k]].atom;
+                t.ltStart = 0;
+                t.parOff = (int64_t)(k * 4 * nla);
+                t.waveOff = 0;
+                t.lambda0 = h.t.lambda0;
+                if (t.prd)
+                {
+                    if (++nPrd > prdLines.size())
+                        break;
+                    t.rhoOff = (int64_t)(nPrd * rowLen);
+                    jobs[nPrd] = InterpJob{ c->lineWave.p + h.waveOff + h.rhoLt0, c->rho.p + h.rhoOff, rowsDev + nPrd * rowLen,
+                                            h.rhoRows, 0 };
+                }
+                trs[k] = t;
+                // the per-(transition, wavelength) scalars of build_tables (lwhip_tables.hip) on the new grid; the quadrature
+                // weight [1] has no meaning here and is not read
+                double* p = par + k * 4 * (size_t)nla;
+                for (int l = 0; l < nla; ++l, p += 4)
+                {
+                    if (h.t.type == LWHIP_LINE)
+                    {
+                        const double hnu_4pi = HC_4PI * (h.t.lambda0 / wl[l]);
+                        p[0] = hnu_4pi * h.t.Bij;
+                        p[1] = 0.0;
+                        p[2] = h.t.Bji / h.t.Bij;
+                        p[3] = h.t.Aji / h.t.Bji;
+                    }
+                    else
+                    {
+                        p[0] = q.contAlpha[act[k]][l];
+                        p[1] = 0.0;
+                        p[2] = TWO_HC_NM3 / (wl[l] * wl[l] * wl[l]);
+                        p[3] = 0.0;
+                    }
+                }
+            }
+            if (nPrd != prdLines.size()) // (before anything is queued)
+                return fail(LWHIP_ERR_INVALID, what + ": column " + std::to_string(i) + " differs from column 0 (its PRD lines)");
+        }
+        if (r.vz)
+        {
+            std::memcpy(hin + vzOff[i], r.vz, (size_t)Ns * sizeof(double));
+            a.vz = (const double*)(st.in.p + vzOff[i]);
+        }
+        if (a.lowerType == LWHIP_BC_CALLABLE)
+        {
+            std::memcpy(hin + bcOff[i], r.lowerBc, nRayCol * sizeof(double));
+            a.lowerBc = (const double*)(st.in.p + bcOff[i]);
+        }
+        double* o = (double*)(st.out.p + (size_t)i * perColOut);
+        a.I = o;
+        if (depth)
+        {
+            a.depthChi = o + nRayCol;
+            a.depthEta = o + nRayCol + nRayCol * Ns;
+            a.depthI = o + nRayCol + 2 * nRayCol * Ns;
+        }
+        hc[i] = a;
+    }
+    if (!grid)
+        return rays_launch_fetch(c0, st, reqs, Ns, Nmu, la0 - c0->laStart, nla, inBytes, what, [] { return LWHIP_OK; });
+    // the rows of the new grid first, on the same stream
+    InterpArgs ia{};
+    ia.jobs = (const InterpJob*)(st.in.p + jobsOff);
+    ia.xNew = (const double*)(st.in.p + waveOff);
+    ia.nJobs = (int32_t)((size_t)n * jobsPerCol);
+    ia.Nwave = nla;
+    ia.Ns = Ns;
+    if ((size_t)nla * Ns > 0x7fffffffu || (size_t)n * jobsPerCol > 0x7fffffffu)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": too many rows for one launch");
+    const unsigned bx = (unsigned)std::min<size_t>(((size_t)nla * Ns + RAYS_THREADS - 1) / RAYS_THREADS, 4096);
+    const unsigned by = (unsigned)std::min<size_t>((size_t)n * jobsPerCol, 65535);
+    hipStream_t stream = c0->stream;
+    return rays_launch_fetch(c0, st, reqs, Ns, Nmu, 0, nla, inBytes, what, [&]() -> int {
+        LWHIP_LAUNCH(rays_grid_rows_kernel, dim3(bx, by), dim3(RAYS_THREADS), 0, stream, ia);
+        HIP_TRY(hipGetLastError());
+        return LWHIP_OK;
+    });
+}
+
+int rays_run_plain(lwhip_context* const* cols, int n, const lwhip_rays* reqs, RaysState*& slot, const char* whatC)
+{
+    const std::string what(whatC);
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, what + ": no gfx950 device");
+    if (n <= 0 || !cols || !reqs)
+        return fail(LWHIP_ERR_INVALID, what + ": null " + (n > 1 ? "batch" : "context") + " or request");
+    std::vector<const lwhip_rays*> ptrs(n);
+    for (int i = 0; i < n; ++i)
+        ptrs[i] = reqs + i;
+    return rays_run(cols, n, ptrs, {}, slot, what);
+}
+
+int rays_run_grid(lwhip_context* const* cols, int n, const lwhip_rays_grid* reqs, RaysState*& slot, const char* whatC)
+{
+    const std::string what(whatC);
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, what + ": no gfx950 device");
+    if (n <= 0 || !cols || !reqs)
+        return fail(LWHIP_ERR_INVALID, what + ": null " + (n > 1 ? "batch" : "context") + " or request");
+    std::vector<const lwhip_rays*> ptrs(n);
+    std::vector<const lwhip_rays_grid*> grids(n);
+    for (int i = 0; i < n; ++i)
+    {
+        grids[i] = reqs + i;
+        ptrs[i] = &reqs[i].rays;
+    }
+    return rays_run(cols, n, ptrs, grids, slot, what);
 }
 } // namespace
 } // namespace lwhip
@@ -601,7 +929,7 @@ int lwhip_compute_rays(lwhip_context* c, const lwhip_rays* rays)
     if (!c)
         return fail(LWHIP_ERR_INVALID, "lwhip_compute_rays: null context");
     lwhip_context* cols[1] = { c };
-    return rays_run(cols, 1, rays, c->rays, "lwhip_compute_rays");
+    return rays_run_plain(cols, 1, rays, c->rays, "lwhip_compute_rays");
 }
 
 int lwhip_batch_compute_rays(lwhip_batch* b, const lwhip_rays* perColumn)
@@ -610,6 +938,35 @@ int lwhip_batch_compute_rays(lwhip_batch* b, const lwhip_rays* perColumn)
         return fail(LWHIP_ERR_DEVICE, "lwhip_batch_compute_rays: no gfx950 device");
     if (!b || b->ctxs.empty())
         return fail(LWHIP_ERR_INVALID, "lwhip_batch_compute_rays: null batch");
-    return rays_run(b->ctxs.data(), (int)b->ctxs.size(), perColumn, b->rays, "lwhip_batch_compute_rays");
+    return rays_run_plain(b->ctxs.data(), (int)b->ctxs.size(), perColumn, b->rays, "lwhip_batch_compute_rays");
+}
+
+int lwhip_rays_grid_active(lwhip_context* c, const double* wavelength, int Nwave, int32_t* active)
+{
+    if (!c || !wavelength || !active || Nwave < 1)
+        return fail(LWHIP_ERR_INVALID, "lwhip_rays_grid_active: a context, wavelength [Nwave >= 1] and active are required");
+    std::vector<int32_t> act;
+    grid_active(c, wavelength, Nwave, act);
+    std::copy(act.begin(), act.end(), active);
+    return LWHIP_OK;
+}
+
+int lwhip_compute_rays_grid(lwhip_context* c, const lwhip_rays_grid* rays)
+{
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, "lwhip_compute_rays_grid: no gfx950 device");
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, "lwhip_compute_rays_grid: null context");
+    lwhip_context* cols[1] = { c };
+    return rays_run_grid(cols, 1, rays, c->rays, "lwhip_compute_rays_grid");
+}
+
+int lwhip_batch_compute_rays_grid(lwhip_batch* b, const lwhip_rays_grid* perColumn)
+{
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, "lwhip_batch_compute_rays_grid: no gfx950 device");
+    if (!b || b->ctxs.empty())
+        return fail(LWHIP_ERR_INVALID, "lwhip_batch_compute_rays_grid: null batch");
+    return rays_run_grid(b->ctxs.data(), (int)b->ctxs.size(), perColumn, b->rays, "lwhip_batch_compute_rays_grid");
 }
 }

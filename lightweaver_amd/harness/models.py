@@ -297,6 +297,23 @@ def build_problem(atmos: Atmosphere1d, models: List[AtomModel], Nrays=5,
     return prob
 
 
+def observer_grid_inputs(atmos: Atmosphere1d, models: List[AtomModel], wavelengths, detailed: Tuple[str, ...] = ()):
+    """What the model layer supplies for compute_rays / observer_problem on a new wavelength grid [Nwave] (nm), by the rules of
+    build_problem: (bgChi, bgEta, bgSca) [Nwave, Nspace] from physics.h_minus_background, and contAlpha = {(atomIdx, transIdx):
+    alpha [Nwave]} for every continuum, alpha0 (lambda / lambda_edge)^3 at or below the edge and 0 beyond it.  The indices are
+    those of the Problem build_problem makes of `models` (active atoms first, then the `detailed` ones; an atom's lines, then
+    its continua)."""
+    w = np.ascontiguousarray(np.atleast_1d(wavelengths), dtype=np.float64)
+    chi, eta, sca = ph.h_minus_background(w, atmos.temperature, atmos.ne, atmos.nH[0])
+    order = [m for m in models if m.name not in detailed] + [m for m in models if m.name in detailed]
+    contAlpha = {}
+    for ia, m in enumerate(order):
+        for ic, c in enumerate(m.continua):
+            lamEdge = m.lambda0(c.i, c.j)
+            contAlpha[(ia, len(m.lines) + ic)] = np.where(w <= lamEdge, c.alpha0 * (w / lamEdge)**3, 0.0)
+    return chi, eta, sca, contAlpha
+
+
 def compute_profiles_host(prob: Problem):
     """phi, wphi of every line on the host with SciPy's wofz (the same Faddeeva package the
     reference vendors as Source/Faddeeva.cc).  Formulae: Transition::compute_phi_la and

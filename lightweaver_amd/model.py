@@ -420,7 +420,67 @@ def check_mus(mus):
     return mus
 
 
-def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None, stokes=False, mux=None, muy=None) -> Problem:
+def grid_active_transitions(prob: Problem, wavelengths):
+    """The active set of a new wavelength grid, SpectrumConfiguration.subset_configuration (lightweaver/atomic_set.py:209-257):
+    with Nb = searchsorted(old, w[0]) and Nr = min(searchsorted(old, w[-1]) + 1, Nlambda), a transition is active iff its rows
+    [Nblue, Nred) of the old grid meet [Nb, Nr).  Returns {(atomIdx, transIdx): bool} in the order of prob.atoms."""
+    w = _f64(np.atleast_1d(wavelengths))
+    Nb = int(np.searchsorted(prob.wavelength, w[0]))
+    Nr = min(int(np.searchsorted(prob.wavelength, w[-1])) + 1, prob.Nlambda)
+    return {(ia, kr): max(Nb, t.Nblue) < min(Nr, t.Nred)
+            for ia, a in enumerate(prob.atoms) for kr, t in enumerate(a.trans)}
+
+
+def _interp_rows(xNew, xOld, f):
+    """numpy.interp along the first axis of f [len(xOld), Nspace], depth by depth: linear, the end values held outside."""
+    out = np.empty((xNew.shape[0], f.shape[1]))
+    for k in range(f.shape[1]):
+        out[:, k] = np.interp(xNew, xOld, f[:, k])
+    return out
+
+
+def _observer_regrid(prob: Problem, new: Problem, Nr, wavelengths, background, contAlpha, lowerBc):
+    """`new` (observer_problem's copy of `prob` with Nr rays) moved onto the grid `wavelengths`: what the reference's second
+    context holds after compute_rays(wavelengths, mus) (LwMiddleLayer.pyx:1960-1963, :2770-2774, :3866)."""
+    w = _f64(np.atleast_1d(wavelengths)).copy()
+    if w.ndim != 1 or w.shape[0] < 2 or not np.all(np.isfinite(w)) or not np.all(np.diff(w) > 0.0):
+        raise ValueError('observer_problem: wavelengths must be at least two finite, strictly increasing values')
+    if background is None or len(background) != 3:
+        raise ValueError('observer_problem: wavelengths needs background=(chi, eta, sca), each [Nwave, Nspace]')
+    Nw, Ns = w.shape[0], prob.Nspace
+    active = grid_active_transitions(prob, w)
+    contAlpha = {(int(k[0]), int(k[1])): v for k, v in (contAlpha or {}).items()}
+    new.wavelength = w
+    new.Nlambda = Nw
+    new.bgChi, new.bgEta, new.bgSca = (_f64(a, (Nw, Ns)).copy() for a in background)
+    new.J = _interp_rows(w, prob.wavelength, prob.J)
+    new.I = np.zeros((Nw, Nr))
+    if new.storeDepthData:
+        new.depthChi, new.depthEta, new.depthI = (np.zeros((Nw, Nr, 2, Ns)) for _ in range(3))
+    for ia, a in enumerate(new.atoms):
+        kept = []
+        for kr, t in enumerate(a.trans):
+            if not active[(ia, kr)]:
+                continue    # (for formal_sol an inactive transition and a missing one are the same)
+            old = prob.atoms[ia].trans[kr]
+            t.Nblue, t.Nred = 0, Nw
+            t.wavelength = w.copy()
+            if t.type == abi.LINE:
+                t.phi = np.zeros((Nw, Nr, 2, Ns))
+                if old.rhoPrd is not None:
+                    t.rhoPrd = _interp_rows(w, old.wavelength, old.rhoPrd)
+            else:
+                if (ia, kr) not in contAlpha:
+                    raise ValueError(f'observer_problem: contAlpha has no cross-section for the active continuum {(ia, kr)}')
+                t.alpha = _f64(contAlpha[(ia, kr)], (Nw,)).copy()
+            kept.append(t)
+        a.trans = kept
+    if new.zLowerBc.type == abi.BC_CALLABLE:
+        new.zLowerBc.bcData = _f64(lowerBc, (Nw, Nr)).copy()
+
+
+def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None, stokes=False, mux=None, muy=None,
+                     wavelengths=None, background=None, contAlpha=None) -> Problem:
     """The problem LwContext.compute_rays (Source/LwMiddleLayer.pyx:3898-4002) hands to its second context: a deep copy
     of `prob` (populations, J, background, rhoPrd: equal, not shared) whose rays are `mus`, with wmu = 0 as
     Atmosphere.rays leaves it unless `wmu` is given, and vlosMu = mu (x) v_z.  `vz` [Nspace] defaults to
@@ -435,9 +495,18 @@ def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None, stokes
     profiles of the new ray count (make them with compute_polarised_profiles) and the field projected onto the new
     directions (update_projections).  `mux` / `muy` [Nmu] default to the reference's 1D convention mux = sqrt(1 - mu^2),
     muy = 0 (lightweaver/atmosphere.py:1509-1510).  Context.compute_rays(stokes=True) computes single_stokes_fs(upOnly=True)
-    of this problem on the device."""
+    of this problem on the device.
+    wavelengths: the problem of compute_rays(wavelengths, mus), on a grid [Nwave] of the caller's choice: the new grid, the
+    `background` = (chi, eta, sca) given for it, J and every PRD line's rhoPrd by numpy.interp in wavelength per depth point
+    (end values held).  The transitions active by the reference's rule (grid_active_transitions) cover the whole new grid
+    (Nblue, Nred = 0, Nwave; a zero phi of the new shape; continua take `contAlpha[(atomIdx, transIdx)]` [Nwave]); the others
+    are removed from their atoms.  `lowerBc` is then [Nwave, Nmu].  Not with stokes."""
     if prob.grid2d is not None:
         raise ValueError('observer_problem: 1D plane-parallel problems only')
+    if wavelengths is not None and stokes:
+        raise ValueError('observer_problem: stokes=True is not served on a new wavelength grid')
+    if wavelengths is None and (background is not None or contAlpha is not None):
+        raise ValueError('observer_problem: background / contAlpha go with wavelengths')
     mus = check_mus(mus)
     Nr, Ns = mus.shape[0], prob.Nspace
     vz = (prob.vlosMu[0] / prob.muz[0]) if vz is None else _f64(vz, (Ns,))
@@ -460,11 +529,14 @@ def observer_problem(prob: Problem, mus, vz=None, wmu=None, lowerBc=None, stokes
                              '[Nlambda, Nmu]')
         idxs = np.full((Nr, 2), -1, dtype=np.int32)
         idxs[:, 1] = np.arange(Nr)
-        new.zLowerBc = Boundary(abi.BC_CALLABLE, idxs=idxs, bcData=_f64(lowerBc, (prob.Nlambda, Nr)).copy())
+        NlaBc = prob.Nlambda if wavelengths is None else np.size(wavelengths)
+        new.zLowerBc = Boundary(abi.BC_CALLABLE, idxs=idxs, bcData=_f64(lowerBc, (NlaBc, Nr)).copy())
     if new.zUpperBc.type == abi.BC_CALLABLE:
         new.zUpperBc = Boundary(abi.BC_ZERO)
     new.stokes = None
     new.Quv = None
+    if wavelengths is not None:
+        _observer_regrid(prob, new, Nr, wavelengths, background, contAlpha, lowerBc)
     if stokes:
         st = prob.stokes
         if st is None:
