@@ -828,6 +828,17 @@ int lwhip_depth_split(lwhip_context* ctx);
  *   out[9]          NlongChar of the context's grid
  * LWHIP_ERR_UNSUPPORTED for a 1D context, LWHIP_ERR_INVALID for a null argument. */
 int lwhip_layout_2d(lwhip_context* ctx, int32_t out[10]);
+/* What a 1D context launches, read from the members its launches read; launches nothing, changes nothing:
+ *   out[0]          sweep kind: 0 the ray-column march, 1 the depth-across-lanes sweep
+ *   out[1 .. 3]     lane sweep: D points per lane, LR lanes per ray, R wavelengths per wavefront (0 on the march)
+ *   out[4]          wavefronts per workgroup (tileWaves)
+ *   out[5], out[6]  wavefronts a tile's rays are split over in the main sweep / in the PRD rates pass (1 on the march)
+ *   out[7]          nTiles
+ *   out[8]          1: the two rays of an angle are paired (symmetric profiles of the resident atmosphere, LWHIP_PAIR_RAYS)
+ *   out[9]          1: the iso-ray hoist is in force as well (direction-independent profiles, LWHIP_ISO_RAYS)
+ * (out[8], out[9]: of a context's own launches; a fused batch launch pairs only if every column does.)
+ * LWHIP_ERR_UNSUPPORTED for a 2D context, LWHIP_ERR_INVALID for a null argument. */
+int lwhip_layout_1d(lwhip_context* ctx, int32_t out[10]);
 
 #ifdef __cplusplus
 }

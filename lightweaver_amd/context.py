@@ -765,6 +765,16 @@ class Context:
         return {'scan': (v[0], bool(v[1])), 'gather': v[2], 'rates': (v[3], v[4], v[5]), 'batch2d': v[6], 'groups2d': v[7],
                 'packed': bool(v[8]), 'NlongChar': v[9]}
 
+    def layout_1d(self):
+        """What a 1D context launches (include/lwhip.h: lwhip_layout_1d): the sweep kind, the lane sweep's (D, LR, R),
+        wavefronts per workgroup, the ray split of the main sweep and of the PRD rates pass, the tile count, and whether ray
+        pairing / the iso-ray hoist are in force for the resident atmosphere.  A 2D context raises."""
+        out = (C.c_int32 * 10)()
+        _check(self.lib, self.lib.lwhip_layout_1d(self._h, out), 'lwhip_layout_1d')
+        v = list(out)
+        return {'sweep': {0: 'march', 1: 'lanes'}[v[0]], 'D': v[1], 'LR': v[2], 'R': v[3], 'tileWaves': v[4], 'laneSplit': v[5],
+                'laneSplitPrd': v[6], 'nTiles': v[7], 'pairRays': bool(v[8]), 'isoRays': bool(v[9])}
+
     def algorithmic_bytes(self):
         b = C.c_double()
         _check(self.lib, self.lib.lwhip_algorithmic_bytes(self._h, C.byref(b)), 'lwhip_algorithmic_bytes')

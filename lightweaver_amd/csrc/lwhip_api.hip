@@ -1980,6 +1980,27 @@ int lwhip_layout_2d(lwhip_context* c, int32_t out[10])
     return LWHIP_OK;
 }
 
+int lwhip_layout_1d(lwhip_context* c, int32_t out[10])
+{
+    if (!c || !out)
+        return fail(LWHIP_ERR_INVALID, "layout_1d: null argument");
+    if (c->is2d)
+        return fail(LWHIP_ERR_UNSUPPORTED, "layout_1d: not a 1D context");
+    // the members build_tables set and the launches read, and the flags make_dyn gives the next launch's TileDyn
+    const TileDyn dyn = make_dyn(c, false, 0);
+    out[0] = c->laneSweep ? 1 : 0;
+    out[1] = c->laneSweep ? c->laneD : 0;
+    out[2] = c->laneSweep ? c->laneLR : 0;
+    out[3] = c->laneSweep ? c->laneR : 0;
+    out[4] = c->tileWaves;
+    out[5] = c->laneSweep ? c->laneSplit : 1;
+    out[6] = c->laneSweep ? c->laneSplitPrd : 1;
+    out[7] = c->nTiles;
+    out[8] = dyn.phiSym;
+    out[9] = dyn.phiIso;
+    return LWHIP_OK;
+}
+
 int lwhip_algorithmic_bytes(lwhip_context* c, double* bytes)
 {
     if (!c || !bytes)

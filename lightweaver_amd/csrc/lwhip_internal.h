@@ -373,7 +373,14 @@ hipError_t launch_tile_post(const TileArgs* devArgs, const TileArgs& hostArgs, c
                             const TileArgs* const* apList, int nBatch, hipStream_t stream);
 // the depth-across-lanes sweep (lwhip_lanesweep.hip); D = hostArgs.laneD
 bool lane_sweep_supported(int Ns, int Nrays, int solver, int* D, int* LR, int* R);
+// (reads maxCT, laneLRD, laneD, maxC, L, depBytes and whether detSlab is set: sizes the launches and build_tables' checks)
 size_t lane_sweep_lds_bytes(const TileArgs& a, int waves);
+// the lane sweep's depth arena -- n | wphi | ratio | geoT (+ padding) back to back, staged whole in every workgroup's LDS --
+// in doubles: the one place that sizes it, for the allocation (lwhip_state.hip) and for TileArgs::depBytes in the checks
+inline size_t lane_dep_arena_doubles(int NlevTot, int Nline, int Ncont, int Ns, int laneLRD)
+{
+    return (size_t)NlevTot * Ns + (size_t)(Nline > 1 ? Nline : 1) * Ns + (size_t)(Ncont > 1 ? Ncont : 1) * Ns + (size_t)4 * (laneLRD + 2) + 16;
+}
 hipError_t launch_lane_sweep(const TileArgs* devArgs, const TileArgs& hostArgs, const TileDyn& dyn, int solver, bool rates,
                              int nChunks, int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream);
 // Diagnosis (LWHIP_DEBUG=1 LWHIP_SCRATCH_POISON=1): fills every wavefront slot's private-segment ("scratch") memory with a

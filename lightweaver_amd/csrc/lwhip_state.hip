@@ -241,7 +241,8 @@ int alloc_state(lwhip_context* c)
         // the depth-only pools the lane sweep reads, back to back (+ padding: a ray's last block reads past its row)
         const size_t nN = (size_t)c->NlevTot * Ns, nW = (size_t)std::max(c->Nline, 1) * Ns, nR = (size_t)std::max(c->Ncont, 1) * Ns;
         const size_t nG = (size_t)4 * (c->laneLR * c->laneD + 2);
-        HIP_TRY(c->depArena.alloc(c->mem, nN + nW + nR + nG + 16));
+        // (= nN + nW + nR + nG + 16: build_tables sized the launches' LDS with the same function)
+        HIP_TRY(c->depArena.alloc(c->mem, lane_dep_arena_doubles(c->NlevTot, c->Nline, c->Ncont, (int)Ns, c->laneLR * c->laneD)));
         HIP_TRY(c->depArena.clear_padding(c->mem));
         c->n.view(c->depArena.p, nN);
         c->wphi.view(c->depArena.p + nN, nW);

@@ -633,6 +633,24 @@ int build_tables(lwhip_context* c)
         return fail(LWHIP_ERR_UNSUPPORTED, "2D: more than 4 continua coupled to the lines of one wavelength (rates2d_kernel's MAXM)");
     if (c->maxC < 1)
         c->maxC = 1;
+    // LDS of a lane-sweep launch of this problem with `waves` wavefronts per workgroup and maxCT accumulator slots, sized where
+    // the launches size it (lane_sweep_lds_bytes on the members build_tile_args will set)
+    auto lane_lds = [&](int waves, int maxCT, int D, int LR, int R) {
+        static double fixedOrder; // (only whether detSlab is set is read)
+        TileArgs t{};
+        t.maxCT = maxCT;
+        t.laneD = D;
+        t.laneLRD = LR * D;
+        t.L = R;
+        t.maxC = c->maxC;
+        t.depBytes = (uint32_t)(lane_dep_arena_doubles(c->NlevTot, c->Nline, c->Ncont, (int)c->Ns, LR * D) * sizeof(double));
+        t.detSlab = c->deterministic ? &fixedOrder : nullptr;
+        return lane_sweep_lds_bytes(t, waves);
+    };
+    // ... and whether a workgroup can have it: the launch within a workgroup's LDS, the accumulators within their 64 KB
+    auto lane_fits = [&](int waves, int maxCT, int D, int LR, int R) {
+        return sizeof(double) * (size_t)maxCT * 4 * (LR * D) <= 64 * 1024 && lane_lds(waves, maxCT, D, LR, R) <= LWHIP_LDS_WORKGROUP;
+    };
 
     int numCU = 256;
     hipDeviceProp_t prop;
@@ -787,6 +805,20 @@ int build_tables(lwhip_context* c)
                 }
                 if (ok)
                 {
+                    // Every workgroup stages the depth arena -- n, wphi, ratio of every level, line and continuum at every
+                    // depth -- in its LDS.  The least a launch can ask for is one wavefront with one tile, whose accumulator
+                    // slots are its wavelengths' transitions: a problem for which even that is more than a workgroup has runs
+                    // the march (H(6) + Ca II(6), 37 arena rows and 7 slots, fits at 256 points; H + three blended Ca II, 69 rows and
+                    // 17 slots, does not at 129: its accumulators alone are 71 808 bytes of the 65 536 they may have -- until
+                    // this check lwhip_create refused that problem instead of taking the march).  The wavefronts per workgroup
+                    // are chosen below by the same functions.
+                    int slotsLa = 1;
+                    for (int la = 0; la < c->Nla; ++la)
+                        slotsLa = std::max(slotsLa, (int)hdr[la].nLine + (int)hdr[la].nMixed + (int)hdr[la].nPure);
+                    ok = lane_fits(1, slotsLa, D, LR, R);
+                }
+                if (ok)
+                {
                     c->laneSweep = true;
                     c->laneD = D;
                     c->laneLR = LR;
@@ -796,7 +828,8 @@ int build_tables(lwhip_context* c)
         }
         if (c->hprd && !c->laneSweep)
             return fail(LWHIP_ERR_UNSUPPORTED, "hybrid PRD needs the depth-across-lanes sweep (1D, 13 <= Nspace <= 256, at most "
-                                               "two lines or a line and a mixed continuum per wavelength)");
+                                               "two lines or a line and a mixed continuum per wavelength, its depth arena within "
+                                               "a workgroup's LDS)");
         const int L = c->laneSweep ? c->laneR : std::max(1, std::min({ 16, 64 / Nmu, dbg_env_int("LWHIP_TILE_L", 16) }));
         const int LRD = c->laneLR * c->laneD;
         c->tileL = L;
@@ -1014,10 +1047,6 @@ int build_tables(lwhip_context* c)
             c->tileWaves = 1;
         if (!c->laneSweep)
             c->deterministic = false; // (not served by the ray-column march: the flag is ignored there)
-        const int W = c->tileWaves;
-        int wgPerCU = std::max(1, 8 / W);
-        if (c->batchHint > 1)
-            wgPerCU = 1;
         struct TileChunking
         {
             std::vector<int32_t> chunkTile, slotTr;
@@ -1103,6 +1132,26 @@ int build_tables(lwhip_context* c)
             if (tiles[i].hasPrd)
                 tileListPrd.push_back(i);
         }
+        if (c->laneSweep)
+        {
+            // The wavefronts of a workgroup: halved while the launch asks for more LDS than a workgroup has -- the per-wavefront
+            // blocks shrink, and so do the accumulator slots, one per transition of the workgroup's tiles.  Counted for whole
+            // tiles (W per workgroup): the groups of a ray split are parts of those.  H(6) + Ca II(6) with seven slots: four
+            // wavefronts are 138 656 bytes at 200 points, 162 944 at 244, 164 264 at 245 and 168 680 at 253, where two are
+            // 154 776.  (Until this check every launch of such a context failed at hipFuncSetAttribute.)  One wavefront fits:
+            // the sweep was chosen so.
+            auto slots_of = [&](const std::vector<int32_t>& list, int mode, int perWg) {
+                return list.empty() ? 1 : chunk_tiles(list, 0, mode, perWg).maxCT;
+            };
+            while (c->tileWaves > 1
+                   && !lane_fits(c->tileWaves, std::max(slots_of(all, 2, c->tileWaves), slots_of(tileListPrd, 0, c->tileWaves)), c->laneD,
+                                 c->laneLR, c->laneR))
+                c->tileWaves /= 2;
+        }
+        const int W = c->tileWaves;
+        int wgPerCU = std::max(1, 8 / W);
+        if (c->batchHint > 1)
+            wgPerCU = 1;
         // (dispatching the lane sweep's long tasks -- tiles with more slots -- first was measured and is WORSE: 0.288 against
         // 0.204 ms at 10 240 wavelengths; co-resident long tasks slow each other down)
         int tgtSweep = std::min((2 * c->nTiles + W - 1) / W, numCU * wgPerCU); // two tasks per tile (down, up)
@@ -1386,6 +1435,8 @@ int build_tables(lwhip_context* c)
         }
         if (c->laneSweep && sizeof(double) * (size_t)c->maxCTTile * 4 * (c->laneLR * c->laneD) > 64 * 1024)
             return fail(LWHIP_ERR_UNSUPPORTED, "more transitions per workgroup than the lane sweep's LDS accumulators hold");
+        if (c->laneSweep && lane_lds(W, c->maxCTTile, c->laneD, c->laneLR, c->laneR) > LWHIP_LDS_WORKGROUP)
+            return fail(LWHIP_ERR_UNSUPPORTED, "the lane sweep of this problem does not fit the 160 KB LDS of one workgroup");
     }
 
     const int NR2 = 2 * c->Nrays;

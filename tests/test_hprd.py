@@ -18,13 +18,18 @@ from tests.helpers import TOL_ONE_CALL, rel_err
 HAVE_REF = os.path.exists(bindings.REF_LIB)
 
 
-def hprd_problem(Nrays=3, lineScale=0.3, vamp=8.0e3, seed=7, formalSolver=None):
+def hprd_problem(Nrays=3, lineScale=0.3, vamp=8.0e3, seed=7, formalSolver=None, Nspace=None):
     """FAL-C H + Ca II with Ca II H & K as PRD lines on a column with a few km/s of line-of-sight velocity (what makes
-    the rest-frame and observer-frame grids differ)."""
+    the rest-frame and observer-frame grids differ).  Nspace: the column resampled to that many points first, the sine's
+    period scaled with it (37 points of 82)."""
     atmos = models.falc82()
+    period = 37.0
+    if Nspace is not None:
+        atmos = models.resample(atmos, Nspace)
+        period = 37.0 * Nspace / 82.0
     rng = np.random.default_rng(seed)
     k = np.arange(atmos.Nspace)
-    atmos.vlos = vamp * np.sin(2.0 * np.pi * k / 37.0) + 0.2 * vamp * rng.standard_normal(atmos.Nspace)
+    atmos.vlos = vamp * np.sin(2.0 * np.pi * k / period) + 0.2 * vamp * rng.standard_normal(atmos.Nspace)
     kw = {} if formalSolver is None else {'formalSolver': formalSolver}
     return models.falc_h_ca(Nrays=Nrays, lineScale=lineScale, prd=True, atmos=atmos, **kw)
 
