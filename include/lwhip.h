@@ -839,6 +839,17 @@ int lwhip_layout_2d(lwhip_context* ctx, int32_t out[10]);
  * (out[8], out[9]: of a context's own launches; a fused batch launch pairs only if every column does.)
  * LWHIP_ERR_UNSUPPORTED for a 2D context, LWHIP_ERR_INVALID for a null argument. */
 int lwhip_layout_1d(lwhip_context* ctx, int32_t out[10]);
+/* Which instance of lanesweep_kernel a 1D context's launches take, by the launcher's own rule on the members
+ * the launches read; launches nothing, changes nothing.  The plain instance leaves out what a launch does not use -- the depth
+ * data stores, the z-plane rows, the CALLABLE boundary lookup; Bezier3 with rates, not hybrid PRD -- and computes the same bits:
+ *   out[0]          1: the main sweep of an iteration takes the plain instance
+ *   out[1]          1: the PRD rates pass does (it writes no depth data even where the context stores them; 0 without one)
+ *   out[2]          1: the depth-across-lanes sweep serves this context (0: the march, which has one instance)
+ *   out[3]          the switch LWHIP_LS_PLAIN as read at lwhip_create (0: every launch takes the full instance)
+ * LWHIP_ERR_UNSUPPORTED for a 2D context, LWHIP_ERR_INVALID for a null argument.
+ * lwhip_batch_sweep_instance: the same of a column batch's one sweep launch, plain only if every column's would be (out[1] = 0). */
+int lwhip_sweep_instance(lwhip_context* ctx, int32_t out[4]);
+int lwhip_batch_sweep_instance(lwhip_batch* batch, int32_t out[4]);
 
 #ifdef __cplusplus
 }

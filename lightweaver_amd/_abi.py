@@ -282,6 +282,8 @@ SYMBOLS = [
     ('lwhip_depth_split', C.c_int, [ctx_p]),
     ('lwhip_layout_2d', C.c_int, [ctx_p, i32p]),
     ('lwhip_layout_1d', C.c_int, [ctx_p, i32p]),
+    ('lwhip_sweep_instance', C.c_int, [ctx_p, i32p]),
+    ('lwhip_batch_sweep_instance', C.c_int, [C.c_void_p, i32p]),
     ('lwhip_set_stokes', C.c_int, [ctx_p, C.POINTER(lwhip_stokes)]),
     ('lwhip_compute_polarised_profiles', C.c_int, [ctx_p]),
     ('lwhip_full_stokes_fs', C.c_int, [ctx_p, C.c_int, C.c_int, C.POINTER(lwhip_iter_result)]),

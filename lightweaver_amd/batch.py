@@ -94,6 +94,17 @@ class ColumnBatch:
         for c in self.contexts:
             c.compute_profiles(deviceResident=True)
 
+    def sweep_instance(self):
+        """Context.sweep_instance() of the fused batch's one sweep launch: plain only if every column's own launch would
+        be (lwhip_batch_sweep_instance).  Not fused: the columns launch by themselves -- ask them."""
+        if self._batch is None:
+            raise RuntimeError('sweep_instance: the batch is not fused; see the columns\' Context.sweep_instance()')
+        import ctypes as C
+        lib = self.contexts[0].lib
+        out = (C.c_int32 * 4)()
+        _check(lib, lib.lwhip_batch_sweep_instance(self._batch, out), 'lwhip_batch_sweep_instance')
+        return {'main': bool(out[0]), 'prdRates': bool(out[1]), 'lanes': bool(out[2]), 'switch': bool(out[3])}
+
     def close(self):
         if self._batch is not None:
             self.contexts[0].lib.lwhip_batch_destroy(self._batch)

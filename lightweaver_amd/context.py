@@ -775,6 +775,15 @@ class Context:
         return {'sweep': {0: 'march', 1: 'lanes'}[v[0]], 'D': v[1], 'LR': v[2], 'R': v[3], 'tileWaves': v[4], 'laneSplit': v[5],
                 'laneSplitPrd': v[6], 'nTiles': v[7], 'pairRays': bool(v[8]), 'isoRays': bool(v[9])}
 
+    def sweep_instance(self):
+        """Which instance of the lane sweep this context's launches take (include/lwhip.h: lwhip_sweep_instance): 'main' /
+        'prdRates' True where the iteration's sweep / the PRD rates pass run the plain instance (no depth data, z-plane rows
+        or CALLABLE boundary compiled in), 'lanes' whether the lane sweep serves the context at all, 'switch' LWHIP_LS_PLAIN
+        as the context read it.  A 2D context raises."""
+        out = (C.c_int32 * 4)()
+        _check(self.lib, self.lib.lwhip_sweep_instance(self._h, out), 'lwhip_sweep_instance')
+        return {'main': bool(out[0]), 'prdRates': bool(out[1]), 'lanes': bool(out[2]), 'switch': bool(out[3])}
+
     def algorithmic_bytes(self):
         b = C.c_double()
         _check(self.lib, self.lib.lwhip_algorithmic_bytes(self._h, C.byref(b)), 'lwhip_algorithmic_bytes')

@@ -803,6 +803,7 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
         return bail(LWHIP_ERR_DEVICE);
     c->pairRays = dbg_env_int("LWHIP_PAIR_RAYS", 1) != 0;
     c->isoRays = dbg_env_int("LWHIP_ISO_RAYS", 1) != 0;
+    c->lsPlain = dbg_env_int("LWHIP_LS_PLAIN", 1) != 0;
     c->prdPipeline = dbg_env_int("LWHIP_PRD_PIPELINE", 1) != 0;
     c->prdGeneral = dbg_env_int("LWHIP_PRD_GENERAL", 0) != 0;
     const bool timing = std::getenv("LWHIP_CREATE_TIMING") != nullptr;
@@ -1998,6 +1999,23 @@ int lwhip_layout_1d(lwhip_context* c, int32_t out[10])
     out[7] = c->nTiles;
     out[8] = dyn.phiSym;
     out[9] = dyn.phiIso;
+    return LWHIP_OK;
+}
+
+int lwhip_sweep_instance(lwhip_context* c, int32_t out[4])
+{
+    if (!c || !out)
+        return fail(LWHIP_ERR_INVALID, "sweep_instance: null argument");
+    if (c->is2d)
+        return fail(LWHIP_ERR_UNSUPPORTED, "sweep_instance: not a 1D context");
+    // what run_sweep passes launch_lane_sweep for an iteration and for the PRD rates pass, and the launcher's own rule
+    TileDyn dyn = make_dyn(c, false, 0);
+    const bool lanes = c->laneSweep && c->tiled;
+    out[0] = (lanes && c->lsPlain && lane_sweep_plain(c->htargs, dyn, c->prob.formalSolver, true)) ? 1 : 0;
+    dyn.prdOnly = 1;
+    out[1] = (lanes && c->lsPlain && c->nTileChunksPrd > 0 && lane_sweep_plain(c->htargsPrd, dyn, c->prob.formalSolver, true)) ? 1 : 0;
+    out[2] = lanes ? 1 : 0;
+    out[3] = c->lsPlain ? 1 : 0;
     return LWHIP_OK;
 }
 

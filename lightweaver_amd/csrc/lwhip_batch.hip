@@ -48,6 +48,16 @@ static int batch_compute_profiles(lwhip_batch* b, bool all)
     return batch_retile(b, todo);
 }
 
+// one sweep launch for all columns: the lane sweep's plain instance only if every column's own launch would take it (the
+// rule of the pair flags: lwhip_batch_formal_sol_gamma_matrices)
+static bool batch_plain_ok(const lwhip_batch* b, const TileDyn& dyn)
+{
+    for (const lwhip_context* c : b->ctxs)
+        if (!c->lsPlain || !lane_sweep_plain(c->htargs, dyn, b->ctxs[0]->prob.formalSolver, true))
+            return false;
+    return true;
+}
+
 namespace lwhip
 {
 int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols)
@@ -252,7 +262,7 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
         HIP_TRY(launch_tile_pre(c0->dtargs.p, c0->htargs, c0->nTiles, b->apList.p, n, c0->stream));
     if (c0->laneSweep)
         HIP_TRY(launch_lane_sweep(c0->dtargs.p, c0->htargs, dyn, c0->prob.formalSolver, true, c0->nTileChunks, c0->tileWaves, b->apList.p, n,
-                                  c0->stream));
+                                  c0->stream, batch_plain_ok(b, dyn)));
     else
     {
         HIP_TRY(launch_tile_sweep(c0->dtargs.p, c0->htargs, dyn, c0->prob.formalSolver, c0->tileCap, true, fuse, c0->nTileChunks,
@@ -287,6 +297,23 @@ int lwhip_batch_compute_profiles(lwhip_batch* b)
         return fail(LWHIP_ERR_INVALID, "null batch");
     HIP_TRY(hipSetDevice(b->ctxs[0]->device));
     return batch_compute_profiles(b, true);
+}
+
+int lwhip_batch_sweep_instance(lwhip_batch* b, int32_t out[4])
+{
+    if (!b || b->ctxs.empty() || !out)
+        return fail(LWHIP_ERR_INVALID, "batch_sweep_instance: null argument");
+    // (what lwhip_batch_formal_sol_gamma_matrices passes its one sweep launch; a batch has no PRD rates pass)
+    const lwhip_context* c0 = b->ctxs[0];
+    const bool lanes = c0->laneSweep && c0->tiled;
+    bool sw = true;
+    for (const lwhip_context* c : b->ctxs)
+        sw = sw && c->lsPlain;
+    out[0] = (lanes && batch_plain_ok(b, make_dyn(b->ctxs[0], false, 0))) ? 1 : 0;
+    out[1] = 0;
+    out[2] = lanes ? 1 : 0;
+    out[3] = sw ? 1 : 0;
+    return LWHIP_OK;
 }
 
 int lwhip_batch_stat_equil(lwhip_batch* b)

@@ -581,7 +581,9 @@ struct lwhip_context
     // LWHIP_DEBUG like the other layout knobs: the first changes the order of the arithmetic)
     // LWHIP_ISO_RAYS=0: angle-independent profiles are not made use of (the stencils are formed once per angle as for
     // profiles that are only direction-symmetric; the same arithmetic, so the same bits)
-    bool pairRays = true, isoRays = true, prdPipeline = true, prdGeneral = false;
+    // LWHIP_LS_PLAIN=0: every launch of the lane sweep takes the full instance (the plain one leaves out code the launch
+    // does not need: the same arithmetic, so the same bits); for A/B runs and tests
+    bool pairRays = true, isoRays = true, prdPipeline = true, prdGeneral = false, lsPlain = true;
     PinnedBlock prdPinnedPipe;
     int prdPipeIter = 0;     // > 0: the sub-iteration the calls of lwhip_prd_partial / _finalise belong to
     double prdPipeTol = 0.0;

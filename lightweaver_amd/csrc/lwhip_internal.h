@@ -381,8 +381,11 @@ inline size_t lane_dep_arena_doubles(int NlevTot, int Nline, int Ncont, int Ns, 
 {
     return (size_t)NlevTot * Ns + (size_t)(Nline > 1 ? Nline : 1) * Ns + (size_t)(Ncont > 1 ? Ncont : 1) * Ns + (size_t)4 * (laneLRD + 2) + 16;
 }
+// plainOk: the launch may take the plain instance (no depth data, no z-plane rows, no CALLABLE boundary compiled in) if
+// lane_sweep_plain says its argument block and flags qualify; a fused batch passes true only if every column qualifies
 hipError_t launch_lane_sweep(const TileArgs* devArgs, const TileArgs& hostArgs, const TileDyn& dyn, int solver, bool rates,
-                             int nChunks, int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream);
+                             int nChunks, int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream, bool plainOk);
+bool lane_sweep_plain(const TileArgs& hostArgs, const TileDyn& dyn, int solver, bool rates);
 // Diagnosis (LWHIP_DEBUG=1 LWHIP_SCRATCH_POISON=1): fills every wavefront slot's private-segment ("scratch") memory with a
 // finite pattern in front of a kernel launch (lwhip_lanesweep.hip: scratch_poison_kernel).  Nothing otherwise.
 void dbg_scratch_poison(hipStream_t stream);

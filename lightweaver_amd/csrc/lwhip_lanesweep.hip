@@ -306,6 +306,11 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
 {
     constexpr bool RATES = (MODE & 1) != 0, HPRD = (MODE & 2) != 0; // MODE: bit 0 rates, bit 1 hybrid PRD (compiled in only where used)
     constexpr bool MOM = RATES && !HPRD;                            // the slots' rates from angle moments
+    // MODE bit 2: the PLAIN launch -- it writes no depth data and no z-plane rows and has no CALLABLE boundary on either side
+    // (the host's choice per launch: lane_sweep_plain).  These three depend on the launch alone, yet their guards and their
+    // arguments (spilled scalars, reloaded by lane moves) were evaluated by every ray of every tile: here they are compiled
+    // out, and nothing that serves only them stays live over the ray loop.  The arithmetic is the full instance's.
+    constexpr bool PLAIN = (MODE & 4) != 0;
     // Two lines (a blend): the moments of both would be 72 registers, and this kernel has none to spare and must not spill
     // (what a value spilled inside divergent control flow did).  Every integral is LINEAR in the moments,
     // so such a tile walks its rays TWICE -- run 0 accumulates J, M1, W and the moments of line 0 (and Q_01), run 1 those of
@@ -514,7 +519,7 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
     for (int p = 0; p < D; ++p)
         mP0[p] = mP1[p] = mQ1[p] = mQ2[p] = mQ12[p] = 0.0;
 
-    const bool storeDepth = RATES && a.storeDepth && !dyn.prdOnly;
+    const bool storeDepth = !PLAIN && RATES && a.storeDepth && !dyn.prdOnly;
     const double lamf = dyn.lambdaIterate ? 0.0 : 1.0;
     // which moment row a line's Psi* eta goes to: with fewer than two lines row 0 stands for the line's moment slot
     const int meSlot0 = NL == 1 ? lms[0] : 0;
@@ -771,20 +776,23 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
                     phiK[0][p] = hPhi[p];
             }
             ls_lds<D + 1>(sDep, c.vK, c.oG, dhK);
-            if (storeDepth && act)
+            if constexpr (!PLAIN)
             {
-                const size_t o = ((size_t)(la * Nmu + mu) * 2 + dirI) * Ns + k0;
+                if (storeDepth && act)
+                {
+                    const size_t o = ((size_t)(la * Nmu + mu) * 2 + dirI) * Ns + k0;
 #pragma unroll
-                for (int p = 0; p < D; ++p)
-                    if (p < c.nV)
-                    {
-                        // (eta formed again, with cont_unit's operations, instead of four registers held for a rare output)
-                        double eC = (c.sRow3 + c.lane * D)[64 * D + p];
-                        if constexpr (PAIRABLE)
-                            eC = fma(cer[0][p], hPhi[p], eC);
-                        GD(a.depthChi)[o + p] = hChi[p];
-                        GD(a.depthEta)[o + p] = eC;
-                    }
+                    for (int p = 0; p < D; ++p)
+                        if (p < c.nV)
+                        {
+                            // (eta formed again, with cont_unit's operations, instead of four registers held for a rare output)
+                            double eC = (c.sRow3 + c.lane * D)[64 * D + p];
+                            if constexpr (PAIRABLE)
+                                eC = fma(cer[0][p], hPhi[p], eC);
+                            GD(a.depthChi)[o + p] = hChi[p];
+                            GD(a.depthEta)[o + p] = eC;
+                        }
+                }
             }
         }
         else
@@ -890,16 +898,19 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
                         phiK[s][p] = 0.0;
                 }
             }
-            if (storeDepth && act)
+            if constexpr (!PLAIN)
             {
-                const size_t o = ((size_t)(la * Nmu + mu) * 2 + dirI) * Ns + k0;
+                if (storeDepth && act)
+                {
+                    const size_t o = ((size_t)(la * Nmu + mu) * 2 + dirI) * Ns + k0;
 #pragma unroll
-                for (int p = 0; p < D; ++p)
-                    if (p < c.nV)
-                    {
-                        GD(a.depthChi)[o + p] = cC[p];
-                        GD(a.depthEta)[o + p] = eC[p];
-                    }
+                    for (int p = 0; p < D; ++p)
+                        if (p < c.nV)
+                        {
+                            GD(a.depthChi)[o + p] = cC[p];
+                            GD(a.depthEta)[o + p] = eC[p];
+                        }
+                }
             }
             double sc[D];
 #pragma unroll
@@ -1020,11 +1031,15 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
                             const double B0 = sb[0], B1 = sb[1];
                             Ib = UP ? B1 - (B0 - B1) * rdtb : B0 - (B1 - B0) * rdtb;
                         }
-                        else if (bcType == LWHIP_BC_CALLABLE)
+                        else if constexpr (!PLAIN)
                         {
-                            const int mi = UP ? CTAB(int32_t, a.lowerIdx)[mu * 2 + 1] : CTAB(int32_t, a.upperIdx)[mu * 2 + 0];
-                            if (mi >= 0)
-                                Ib = UP ? GCD(a.lowerBcData)[(size_t)la * a.lowerNmu + mi] : GCD(a.upperBcData)[(size_t)la * a.upperNmu + mi];
+                            if (bcType == LWHIP_BC_CALLABLE)
+                            {
+                                const int mi = UP ? CTAB(int32_t, a.lowerIdx)[mu * 2 + 1] : CTAB(int32_t, a.upperIdx)[mu * 2 + 0];
+                                if (mi >= 0)
+                                    Ib = UP ? GCD(a.lowerBcData)[(size_t)la * a.lowerNmu + mi]
+                                            : GCD(a.upperBcData)[(size_t)la * a.upperNmu + mi];
+                            }
                         }
                         bb[i] = Ib;
                     }
@@ -1120,11 +1135,14 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
                     const double B0 = sb[0], B1 = sb[1];
                     Ib = UP ? B1 - (B0 - B1) * rdtb : B0 - (B1 - B0) * rdtb;
                 }
-                else if (bcType == LWHIP_BC_CALLABLE)
+                else if constexpr (!PLAIN)
                 {
-                    const int mi = UP ? CTAB(int32_t, a.lowerIdx)[mu * 2 + 1] : CTAB(int32_t, a.upperIdx)[mu * 2 + 0];
-                    if (mi >= 0)
-                        Ib = UP ? GCD(a.lowerBcData)[(size_t)la * a.lowerNmu + mi] : GCD(a.upperBcData)[(size_t)la * a.upperNmu + mi];
+                    if (bcType == LWHIP_BC_CALLABLE)
+                    {
+                        const int mi = UP ? CTAB(int32_t, a.lowerIdx)[mu * 2 + 1] : CTAB(int32_t, a.upperIdx)[mu * 2 + 0];
+                        if (mi >= 0)
+                            Ib = UP ? GCD(a.lowerBcData)[(size_t)la * a.lowerNmu + mi] : GCD(a.upperBcData)[(size_t)la * a.upperNmu + mi];
+                    }
                 }
                 return Ib;
             };
@@ -1231,21 +1249,24 @@ DEVINL int lane_rays(const CONST_AS TileArgs& a, const TileDyn& dyn, const DevLa
         LS_KEEPI(la); // (output addresses are formed here, not held from the start of the tile)
         if (UP && act && c.blk == 0)
             GD(a.I)[(size_t)la * Nmu + mu] = Iv[D - 1]; // spect.I(la, mu, 0) :349
-        if ((UP ? a.zUp : a.zDown) != nullptr && act)
+        if constexpr (!PLAIN)
         {
-            // ZPlaneDecomposition :351-361: depth 1 of an up ray, depth Nz - 2 of a down ray
+            if ((UP ? a.zUp : a.zDown) != nullptr && act)
+            {
+                // ZPlaneDecomposition :351-361: depth 1 of an up ray, depth Nz - 2 of a down ray
 #pragma unroll
-            for (int i = 0; i < D; ++i)
-                if (k0 + MI(i) == (UP ? 1 : Ns - 2))
-                    GD(UP ? a.zUp : a.zDown)[(size_t)la * Nmu + mu] = Iv[i];
-        }
-        if (storeDepth && act)
-        {
-            const size_t o = ((size_t)(la * Nmu + mu) * 2 + dirI) * Ns + k0;
+                for (int i = 0; i < D; ++i)
+                    if (k0 + MI(i) == (UP ? 1 : Ns - 2))
+                        GD(UP ? a.zUp : a.zDown)[(size_t)la * Nmu + mu] = Iv[i];
+            }
+            if (storeDepth && act)
+            {
+                const size_t o = ((size_t)(la * Nmu + mu) * 2 + dirI) * Ns + k0;
 #pragma unroll
-            for (int i = 0; i < D; ++i)
-                if (is_ok(i))
-                    GD(a.depthI)[o + MI(i)] = Iv[i];
+                for (int i = 0; i < D; ++i)
+                    if (is_ok(i))
+                        GD(a.depthI)[o + MI(i)] = Iv[i];
+            }
         }
         if (HPRD && RATES && a.hJOff && td.hasPrd && act)
         {
@@ -3394,7 +3415,11 @@ __global__ void __launch_bounds__(256) det_reduce_kernel(const double* __restric
 #ifdef LS_ISA_ONLY /* one instance, for instruction counts of the listing (tools/isa_loops.py) */
 #ifndef LS_ISA_SOLVER
 #define LS_ISA_SOLVER LWHIP_FS_BEZIER3_1D
+#ifdef LS_ISA_PLAIN /* the plain instance (MODE bit 2) */
+#define LS_ISA_MODE 5
+#else
 #define LS_ISA_MODE 1
+#endif
 #define LS_ISA_BATCH false
 #endif
 template __global__ void lanesweep_kernel<LS_ISA_SOLVER, 4, LS_ISA_MODE, LS_ISA_BATCH>(const TileArgs* __restrict__, const TileArgs* const* __restrict__,
@@ -3496,14 +3521,30 @@ size_t lane_sweep_lds_bytes(const TileArgs& a, int waves)
            + a.depBytes + (a.detSlab ? ((size_t)a.maxCT * a.laneD * sizeof(int) + 7) / 8 * 8 : 0); // (+ the fixed-order mode's turn counters)
 }
 
+// The plain instance (MODE bit 2 of lanesweep_kernel) serves a launch that writes no depth data (the PRD rates pass never
+// does) and no z-plane rows and has no CALLABLE boundary; it exists for Bezier3 with rates, not hybrid PRD.
+bool lane_sweep_plain(const TileArgs& a, const TileDyn& dyn, int solver, bool rates)
+{
+    if (solver != LWHIP_FS_BEZIER3_1D || !rates || a.hRho != nullptr || a.hJOff != nullptr)
+        return false;
+    if (a.storeDepth && !dyn.prdOnly)
+        return false;
+    if (a.zUp != nullptr || a.zDown != nullptr)
+        return false;
+    return a.lowerBc != LWHIP_BC_CALLABLE && a.upperBc != LWHIP_BC_CALLABLE;
+}
+
 #ifndef LS_ISA_ONLY
 hipError_t launch_lane_sweep(const TileArgs* devArgs, const TileArgs& a, const TileDyn& dyn, int solver, bool rates, int nChunks,
-                             int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream)
+                             int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream, bool plainOk)
 {
     if (nChunks <= 0)
         return hipSuccess;
     if (waves < 1 || waves > LS_MAX_WAVES || a.laneD != 4)
         return hipErrorInvalidValue;
+    // (plainOk: the caller's switch, and for a fused batch that every column qualifies; `a` is then column 0's block)
+    if (plainOk && lane_sweep_plain(a, dyn, solver, rates))
+        return launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 5>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream);
     // (the linear and BESSER solvers: one instance each per rates / no rates, with the hybrid-PRD paths compiled in)
     if (solver == LWHIP_FS_LINEAR_1D)
         return rates ? launch_ls_t<LWHIP_FS_LINEAR_1D, 4, 3>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream)

@@ -607,7 +607,7 @@ hipError_t run_sweep(lwhip_context* c, const TileDyn& dyn, bool rates, hipEvent_
         (void)hipEventRecord(e0, c->stream);
     if (c->laneSweep)
         e = launch_lane_sweep(da, ha, td, c->prob.formalSolver, rates, tprd ? c->nTileChunksPrd : c->nTileChunks, c->tileWaves, nullptr, 0,
-                              c->stream);
+                              c->stream, c->lsPlain);
     else
         e = launch_tile_sweep(da, ha, td, c->prob.formalSolver, c->tileCap, rates, fuse, tprd ? c->nTileChunksPrd : c->nTileChunks,
                               (fuse && ha.depthSplit > 1) ? 2 * ha.depthSplit : c->tileWaves, nullptr, 0, c->stream);
