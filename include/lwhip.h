@@ -572,6 +572,39 @@ int lwhip_batch_stat_equil(lwhip_batch* batch);
  * uploaded later (LWHIP_ATMOS) are brought up to date the same way by the next lwhip_batch_formal_sol_gamma_matrices. */
 int lwhip_batch_compute_profiles(lwhip_batch* batch);
 
+/* Column batches to convergence: the population change per column, and an ACTIVE SET of columns.
+ *
+ * lwhip_batch_stat_equil_report: lwhip_batch_stat_equil of the active columns that also reports, per column and solved
+ * (not detailed) atom, max |(new - old) / new| over the populations and the flattened [level, depth] index of its first
+ * occurrence (Ng::max_change, Source/Ng.hpp:138-156: what lwhip_stat_equil_report gives for one context).  dPops and
+ * dPopsMaxIdx (or NULL) are [n][Natoms], rows indexed by the ORIGINAL column number, Natoms the number of solved atoms
+ * (the same for every column of a batch); rows of inactive columns are left untouched.  On the device every column's
+ * per-block maxima are combined by one wavefront (batch_conv_kernel) into one record [dJMax, dJMaxIdx, dPops_0, idx_0,
+ * ...] per column -- dJMax as the last lwhip_batch_formal_sol_gamma_matrices left it --, so a reported iteration costs one
+ * copy of the records and one stream wait.  lwhip_batch_conv_records copies the records of the last report,
+ * [n][2 + 2 Natoms] doubles, rows of columns that were inactive then left untouched; *stride (or NULL) receives
+ * 2 + 2 Natoms.  A singular matrix in any active column: LWHIP_ERR_SINGULAR, as lwhip_batch_stat_equil.
+ *
+ * lwhip_batch_set_active: `columns` is a strictly increasing list of nActive column indices; NULL / 0 restores all columns.
+ * Afterwards lwhip_batch_formal_sol_gamma_matrices, lwhip_batch_stat_equil and lwhip_batch_stat_equil_report launch only those
+ * columns; their results[i] / rows stay indexed by the original column number and entries of inactive columns are untouched.
+ * Every other batch entry point (profiles, Stokes, observer rays, sweep_instance) keeps acting on all columns.  An index out
+ * of range, a list that is not strictly increasing, nActive < 0 or nActive > 0 with columns == NULL: LWHIP_ERR_INVALID, the
+ * active set left as it was.  lwhip_batch_active reads the set back: columns [n] (or NULL) and *nActive.
+ * Three invariants:
+ *  - a retired (inactive) column's device state -- J, I, n, Gamma, rates -- is exactly what its last iteration left: later
+ *    batch iterations never touch it;
+ *  - the launch-wide choices made "only if every column qualifies" (symmetric / angle-independent profiles, the plain sweep
+ *    instance) are evaluated over ALL columns of the batch, not the active ones: the code path a column runs, and so its
+ *    bits, do not depend on who else is still active;
+ *  - with all columns active the launches and copies of the three entry points are what they were before there was an
+ *    active set.
+ * Out of scope for batches: Ng acceleration, PRD sub-iterations, time-dependent and charge-conserving updates. */
+int lwhip_batch_stat_equil_report(lwhip_batch* batch, double* dPops /* [n][Natoms] */, int32_t* dPopsMaxIdx /* [n][Natoms] or NULL */);
+int lwhip_batch_conv_records(lwhip_batch* batch, double* records /* [n][2 + 2 Natoms] */, int* stride /* or NULL */);
+int lwhip_batch_set_active(lwhip_batch* batch, const int32_t* columns, int nActive);
+int lwhip_batch_active(lwhip_batch* batch, int32_t* columns /* [n] or NULL */, int* nActive);
+
 /* The intersection table of an x-periodic grid: build_intersection_list (Source/FormalScalar2d.cpp:1188-1327) with
  * dw_intersection_2d (:60-105), uw_intersection_2d (:107-152), uw_intersection_2d_frac_x (:166-206).  Host-side
  * geometry, once per atmosphere; reads Nx, Nz, Nrays, periodic, x, z, mux, muz of `grid`.  Call with uw == NULL to

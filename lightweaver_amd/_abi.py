@@ -258,6 +258,10 @@ SYMBOLS = [
     ('lwhip_batch_formal_sol_gamma_matrices', C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(lwhip_iter_result)]),
     ('lwhip_batch_stat_equil', C.c_int, [C.c_void_p]),
     ('lwhip_batch_compute_profiles', C.c_int, [C.c_void_p]),
+    ('lwhip_batch_stat_equil_report', C.c_int, [C.c_void_p, f64p, i32p]),
+    ('lwhip_batch_conv_records', C.c_int, [C.c_void_p, f64p, C.POINTER(C.c_int)]),
+    ('lwhip_batch_set_active', C.c_int, [C.c_void_p, i32p, C.c_int]),
+    ('lwhip_batch_active', C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_int)]),
     ('lwhip_build_intersections', C.c_int, [C.POINTER(lwhip_grid2d), C.POINTER(lwhip_intersection),
                                              C.POINTER(lwhip_intersection), i32p, i32p, C.c_int32,
                                              C.POINTER(lwhip_intersection), C.c_int64, C.POINTER(C.c_int32),

@@ -9,11 +9,20 @@ the device per column (lwhip_compute_profiles), so phi never crosses PCIe.
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
 from . import _abi as abi
 from .context import Context, _check
 from .model import Problem
+
+
+@dataclass
+class BatchConvergence:
+    """What ColumnBatch.iterate_to_convergence returns, one entry per column."""
+    iterations: List[int]     # the value iterate_ctx_se would return for the column (NmaxIter - 1 where it did not converge)
+    converged: List[bool]
+    final: List[list]         # [JUpdate, popsUpdate] of the column's stop iteration ([] where it did not converge)
 
 
 def columns_of_rank(ncolumns: int, world: int, rank: int) -> List[int]:
@@ -33,6 +42,7 @@ class ColumnBatch:
         that the small reduce / apply / solve kernels of one column overlap the sweep of the next."""
         self.problems = list(problems)
         self._batch = None
+        self._active = None     # (None: every column; else the increasing list of active columns -- set_active)
         if streams:
             self.contexts = [Context(p, device=device, stream=streams[i % len(streams)])
                              for i, p in enumerate(self.problems)]
@@ -122,7 +132,10 @@ class ColumnBatch:
     def formal_sol_gamma_matrices(self, lambdaIterate=False, sync_host=True):
         """One iteration of every column; kernels of all columns are queued before the first
         result is read back.  sync_host=False reads nothing back (no host wait per column): use it for
-        all but the iterations whose dJMax is wanted."""
+        all but the iterations whose dJMax is wanted.  With an active set (set_active) only its columns advance and the
+        entries of the others are None."""
+        if self._active is not None and not self._active:
+            return [None] * len(self.contexts) if sync_host else None
         if self._batch is not None:
             import ctypes as C
             from .context import IterationUpdate
@@ -135,26 +148,156 @@ class ColumnBatch:
             res = (abi.lwhip_iter_result * len(self.contexts))()
             _check(lib, lib.lwhip_batch_formal_sol_gamma_matrices(self._batch, int(lambdaIterate), crsw, res),
                    'lwhip_batch_formal_sol_gamma_matrices')
-            return [IterationUpdate(updatedJ=True, dJMax=r.dJMax, dJMaxIdx=r.dJMaxIdx, crsw=crsw) for r in res]
-        for c in self.contexts:
+            ups = [IterationUpdate(updatedJ=True, dJMax=r.dJMax, dJMaxIdx=r.dJMaxIdx, crsw=crsw) for r in res]
+            return ups if self._active is None else self._only_active(ups)
+        cols = [self.contexts[i] for i in self.active]
+        for c in cols:
             c.gamma_prefill_from_C(c.crsw)
             c.fs_partial(lambdaIterate)
         if not sync_host:
-            for c in self.contexts:
+            for c in cols:
                 _check(c.lib, c.lib.lwhip_fs_finalise(c._h, None), 'lwhip_fs_finalise')
             return None
-        return [c.fs_finalise() for c in self.contexts]
+        ups = [None] * len(self.contexts)
+        for i in self.active:
+            ups[i] = self.contexts[i].fs_finalise()
+        return ups
 
-    def stat_equil(self):
-        """Queued for every column without a host wait in between; one status check at the end."""
+    def _only_active(self, per_column):
+        """per_column with None in the places of the inactive columns."""
+        act = set(self.active)
+        return [u if i in act else None for i, u in enumerate(per_column)]
+
+    def stat_equil(self, report=False):
+        """Queued for every (active) column without a host wait in between; one status check at the end.
+        report=True: returns one IterationUpdate(updatedPops=True, dPops=[...], dPopsMaxIdx=[...]) per column -- what
+        Context.stat_equil gives for the column alone --, None for an inactive column (lwhip_batch_stat_equil_report: the
+        columns' change records are combined on the device and come back in one copy; not fused: each column's own
+        Context.stat_equil(deviceResident=True))."""
+        if report:
+            return self._stat_equil_report()[1]
+        if self._active is not None and not self._active:
+            return
         if self._batch is not None:
             lib = self.contexts[0].lib
             _check(lib, lib.lwhip_batch_stat_equil(self._batch), 'lwhip_batch_stat_equil')
             return
-        for c in self.contexts:
+        cols = [self.contexts[i] for i in self.active]
+        for c in cols:
             c.stat_equil(deviceResident=True, sync_host=False)
-        for c in self.contexts:
+        for c in cols:
             c.check_status()
+
+    def _stat_equil_report(self):
+        """stat_equil(report=True): (JUpdates, popsUpdates), one entry per column, None for inactive columns.  JUpdates: on a
+        fused batch the dJMax the last formal_sol_gamma_matrices left on the device, which the columns' convergence records
+        carry (so that call needs no host wait of its own); None when not fused."""
+        from .context import IterationUpdate
+        n = len(self.contexts)
+        pops = [None] * n
+        if self._active is not None and not self._active:
+            return None, pops
+        if self._batch is None:
+            for i in self.active:
+                pops[i] = self.contexts[i].stat_equil(deviceResident=True)
+            return None, pops
+        import ctypes as C
+        import numpy as np
+        lib = self.contexts[0].lib
+        nAct = sum(1 for a in self.problems[0].atoms if not a.detailed)
+        if nAct == 0:
+            for i in self.active:
+                pops[i] = IterationUpdate(updatedPops=True, dPops=[], dPopsMaxIdx=[])
+            return None, pops
+        dPops = np.zeros((n, nAct))
+        dIdx = np.zeros((n, nAct), dtype=np.int32)
+        _check(lib, lib.lwhip_batch_stat_equil_report(self._batch, dPops.ctypes.data_as(abi.f64p), dIdx.ctypes.data_as(abi.i32p)),
+               'lwhip_batch_stat_equil_report')
+        rec = np.zeros((n, 2 + 2 * nAct))
+        stride = C.c_int(0)
+        _check(lib, lib.lwhip_batch_conv_records(self._batch, rec.ctypes.data_as(abi.f64p), C.byref(stride)), 'lwhip_batch_conv_records')
+        assert stride.value == rec.shape[1]
+        crsw = self.contexts[0].crsw
+        Js = [None] * n
+        # (plain lists first: this runs between two iterations with the device idle -- 512 columns, 3 ms element by element, 1 ms so)
+        dP, dI, rc = dPops.tolist(), dIdx.tolist(), rec.tolist()
+        for i in self.active:
+            pops[i] = IterationUpdate(updatedPops=True, dPops=dP[i], dPopsMaxIdx=dI[i])
+            Js[i] = IterationUpdate(updatedJ=True, dJMax=rc[i][0], dJMaxIdx=int(rc[i][1]), crsw=crsw)
+        return Js, pops
+
+    # -- the active set: the columns formal_sol_gamma_matrices and stat_equil advance ---------------------------------------
+    @property
+    def active(self) -> List[int]:
+        """The columns formal_sol_gamma_matrices / stat_equil advance, increasing."""
+        return list(range(len(self.contexts))) if self._active is None else list(self._active)
+
+    def set_active(self, columns=None):
+        """Only `columns` (a strictly increasing list of column indices; None: all) are advanced by formal_sol_gamma_matrices
+        and stat_equil from now on (lwhip_batch_set_active; kept here where the batch is not fused).  An inactive
+        ("retired") column's device state stays exactly what its last iteration left; every other method -- profiles,
+        Stokes, compute_rays, download -- keeps acting on all columns; and what a column computes does not depend on which
+        others are active.  An empty list: those two calls do nothing."""
+        n = len(self.contexts)
+        cols = None if columns is None else [int(i) for i in columns]
+        if cols is not None and (any(not (0 <= i < n) for i in cols) or any(b <= a for a, b in zip(cols, cols[1:]))):
+            raise ValueError('set_active: a strictly increasing list of column indices below %d' % n)
+        if cols is not None and len(cols) == n:
+            cols = None
+        if self._batch is not None and (cols is None or cols):
+            import numpy as np
+            lib = self.contexts[0].lib
+            arr = np.asarray(cols if cols is not None else [], dtype=np.int32)
+            _check(lib, lib.lwhip_batch_set_active(self._batch, arr.ctypes.data_as(abi.i32p) if cols is not None else None,
+                                                   len(arr)), 'lwhip_batch_set_active')
+        self._active = cols
+
+    def iterate_to_convergence(self, Nscatter: int = 3, NmaxIter: int = 2000, JTol: float = 5e-3, popsTol: float = 1e-3,
+                               retire: bool = True, callback: Optional[Callable] = None):
+        """iterate_ctx_se (iterate.py; lightweaver/iterate_ctx.py:85-208) for every column at once, each column judged by its
+        own numbers: a column is converged at the first iteration it >= Nscatter whose own dJMax < JTol and max dPops <
+        popsTol (DefaultConvergenceCriteria).  retire=True: it leaves the active set at once, so its state stays what that
+        iteration left and the launches shrink; retire=False: it is only recorded and keeps iterating.  Starts from all
+        columns; ends when every column has converged or after NmaxIter iterations, and restores the full active set
+        before returning (also when an exception passes through).
+        Returns BatchConvergence(iterations, converged, final): per column what iterate_ctx_se would return for it alone
+        (NmaxIter - 1 where it did not converge), whether it converged, and its final [JUpdate, popsUpdate] ([] where it
+        did not).  callback(it, JUpdates, popsUpdates, active): per-column lists (None for columns inactive in that
+        iteration; popsUpdates None while it < Nscatter) and the active set after the iteration's retirements.
+        No Ng acceleration, PRD sub-iterations, time-dependent or charge-conserving updates here."""
+        from .iterate import DefaultConvergenceCriteria
+        n = len(self.contexts)
+        convs = [DefaultConvergenceCriteria(c, JTol, popsTol, None) for c in self.contexts]
+        out = BatchConvergence(iterations=[max(NmaxIter - 1, 0)] * n, converged=[False] * n, final=[[] for _ in range(n)])
+        pending = list(range(n))
+        self.set_active(None)
+        try:
+            for it in range(NmaxIter):
+                if not pending:
+                    break
+                # (fused: the reported solve brings this iteration's dJMax back with the population changes -- one host wait)
+                solve = it >= Nscatter
+                want = callback is not None if not solve else self._batch is None
+                JUps = self.formal_sol_gamma_matrices(sync_host=want)
+                if not solve:
+                    if callback is not None:
+                        callback(it, JUps, None, self.active)
+                    continue
+                recJ, pUps = self._stat_equil_report()
+                if JUps is None:
+                    JUps = recJ
+                new = [i for i in pending if convs[i].is_converged(JUps[i], pUps[i], None)]
+                for i in new:
+                    out.iterations[i], out.converged[i], out.final[i] = it, True, [JUps[i], pUps[i]]
+                if new:
+                    pending = [i for i in pending if not out.converged[i]]
+                    if retire:
+                        self.set_active(pending)
+                if callback is not None:
+                    callback(it, JUps, pUps, self.active)
+        finally:
+            self.set_active(None)
+        return out
 
     def iterate(self, niter: int, nscatter: int = 3, callback: Optional[Callable] = None):
         """iterate_ctx_se-style loop (lightweaver/iterate_ctx.py:157-176) over the whole batch."""

@@ -58,6 +58,56 @@ static bool batch_plain_ok(const lwhip_batch* b, const TileDyn& dyn)
     return true;
 }
 
+// the compacted argument lists of a proper subset of the columns (lwhip_batch_set_active): position p is column act[p].  The
+// buffers are made once, for n columns; the copies are ordered on the batch's stream behind the launches that read the last set.
+// (The apply blocks follow in the next lwhip_batch_formal_sol_gamma_matrices: aValid is off.)
+template <class T> static hipError_t upload_compact(lwhip_batch* b, DevBuf<T>& dev, std::vector<T>& host, const std::vector<T>& full)
+{
+    lwhip_context* c0 = b->ctxs[0];
+    if (!dev.p)
+    {
+        const hipError_t e = dev.alloc(c0->mem, full.size(), false);
+        if (e != hipSuccess)
+            return e;
+    }
+    host.resize(b->act.size());
+    for (size_t p = 0; p < b->act.size(); ++p)
+        host[p] = full[b->act[p]];
+    return hipMemcpyAsync(dev.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, c0->stream);
+}
+static int batch_upload_active(lwhip_batch* b)
+{
+    lwhip_context* c0 = b->ctxs[0];
+    HIP_TRY(upload_compact(b, b->apAct, b->apActHost, b->apHost));
+    HIP_TRY(upload_compact(b, b->rAct, b->rActHost, b->rHost));
+    HIP_TRY(upload_compact(b, b->seAct, b->seActHost, b->seHost));
+    if (b->change.p)
+        HIP_TRY(upload_compact(b, b->seRepAct, b->seRepActHost, b->seRepHost));
+    if (!b->aAct.p)
+        HIP_TRY(b->aAct.alloc(c0->mem, b->ctxs.size()));
+    b->aActHost.resize(b->act.size());
+    if (!b->colsAct.p)
+        HIP_TRY(b->colsAct.alloc(c0->mem, b->ctxs.size(), false));
+    HIP_TRY(hipMemcpyAsync(b->colsAct.p, b->act.data(), b->act.size() * sizeof(int32_t), hipMemcpyHostToDevice, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream)); // (the host lists may change with the next set; a retirement is rare)
+    return LWHIP_OK;
+}
+
+// the status words of the columns just solved: the first singular one is reported (and cleared)
+static int batch_singular(lwhip_batch* b)
+{
+    for (const int32_t i : b->act)
+    {
+        lwhip_context* c = b->ctxs[i];
+        if (*c->statusHost == LWHIP_ERR_SINGULAR)
+        {
+            *c->statusHost = 0;
+            return fail(LWHIP_ERR_SINGULAR, "Singular Matrix");
+        }
+    }
+    return LWHIP_OK;
+}
+
 namespace lwhip
 {
 int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols)
@@ -146,6 +196,11 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
     }
     HIP_TRY(b->apList.upload(c0->mem, ap));
     HIP_TRY(b->rList.upload(c0->mem, rl));
+    b->apHost = ap;
+    b->rHost = rl;
+    b->act.resize(n);
+    for (int i = 0; i < n; ++i)
+        b->act[i] = i;
     HIP_TRY(b->aList.alloc(c0->mem, (size_t)n));
     b->aHost.resize(n);
     {
@@ -194,6 +249,7 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
                 return fail(LWHIP_ERR_INVALID, "batch_create: the columns must share their active atoms");
         }
         HIP_TRY(b->seList.upload(c0->mem, sl));
+        b->seHost = sl;
     }
     HIP_TRY(b->tailPinned.reserve(c0->device, (size_t)2 * n * sizeof(double), c0->stream));
     *out = b.release();
@@ -233,8 +289,13 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
         if (stp != LWHIP_OK)
             return stp;
     }
+    // the columns this call launches: all of them, or the compacted lists of the active set (lwhip_batch_set_active)
+    const int nAct = (int)b->act.size();
+    const TileArgs* const* apL = b->allActive ? b->apList.p : b->apAct.p;
+    const ReduceArgs* rL = b->allActive ? b->rList.p : b->rAct.p;
+    const ApplyArgs* aL = b->allActive ? b->aList.p : b->aAct.p;
     // Gamma <- crsw * C of every column is fused into its slice of the apply launch
-    for (int i = 0; i < n; ++i)
+    for (const int32_t i : b->act)
     {
         lwhip_context* c = b->ctxs[i];
         if (c->partialPending || c->prdPending)
@@ -247,7 +308,14 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
     }
     if (!b->aValid || b->aCrsw != crsw)
     {
-        HIP_TRY(hipMemcpyAsync(b->aList.p, b->aHost.data(), (size_t)n * sizeof(ApplyArgs), hipMemcpyHostToDevice, c0->stream));
+        if (b->allActive)
+            HIP_TRY(hipMemcpyAsync(b->aList.p, b->aHost.data(), (size_t)n * sizeof(ApplyArgs), hipMemcpyHostToDevice, c0->stream));
+        else
+        {
+            for (int p = 0; p < nAct; ++p)
+                b->aActHost[p] = b->aHost[b->act[p]];
+            HIP_TRY(hipMemcpyAsync(b->aAct.p, b->aActHost.data(), (size_t)nAct * sizeof(ApplyArgs), hipMemcpyHostToDevice, c0->stream));
+        }
         b->aValid = true;
         b->aCrsw = crsw;
     }
@@ -259,29 +327,29 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
         dyn.phiIso = (b->ctxs[q]->phiIso && dyn.phiSym) ? 1 : 0;
     const bool fuse = c0->tileFuse;
     if (!c0->laneSweep) // (the lane sweep's tasks do their own pre-pass)
-        HIP_TRY(launch_tile_pre(c0->dtargs.p, c0->htargs, c0->nTiles, b->apList.p, n, c0->stream));
+        HIP_TRY(launch_tile_pre(c0->dtargs.p, c0->htargs, c0->nTiles, apL, nAct, c0->stream));
     if (c0->laneSweep)
-        HIP_TRY(launch_lane_sweep(c0->dtargs.p, c0->htargs, dyn, c0->prob.formalSolver, true, c0->nTileChunks, c0->tileWaves, b->apList.p, n,
+        HIP_TRY(launch_lane_sweep(c0->dtargs.p, c0->htargs, dyn, c0->prob.formalSolver, true, c0->nTileChunks, c0->tileWaves, apL, nAct,
                                   c0->stream, batch_plain_ok(b, dyn)));
     else
     {
         HIP_TRY(launch_tile_sweep(c0->dtargs.p, c0->htargs, dyn, c0->prob.formalSolver, c0->tileCap, true, fuse, c0->nTileChunks,
-                                  c0->tileWaves, b->apList.p, n, c0->stream));
+                                  c0->tileWaves, apL, nAct, c0->stream));
         if (!fuse)
-            HIP_TRY(launch_tile_post(c0->dtargs.p, c0->htargs, dyn, c0->nPostChunks, b->apList.p, n, c0->stream));
+            HIP_TRY(launch_tile_post(c0->dtargs.p, c0->htargs, dyn, c0->nPostChunks, apL, nAct, c0->stream));
     }
     {
         ReduceArgs r0 = make_reduce_args(c0);
         r0.zeroParts = 1;
-        HIP_TRY(launch_reduce_sum(r0, c0->stream, b->rList.p, n));
+        HIP_TRY(launch_reduce_sum(r0, c0->stream, rL, nAct));
     }
     if (c0->Natom > 0)
-        HIP_TRY(launch_apply(b->aHost[0], c0->stream, b->aList.p, n));
+        HIP_TRY(launch_apply(b->aHost[b->act[0]], c0->stream, aL, nAct));
     if (results)
     {
         HIP_TRY(hipMemcpyAsync(b->tailPinned.host, b->tail.p, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
         HIP_TRY(hipStreamSynchronize(c0->stream));
-        for (int i = 0; i < n; ++i)
+        for (const int32_t i : b->act) // (entries of inactive columns stay as the caller filled them)
         {
             results[i].updatedJ = 1;
             results[i].dJMax = b->tailPinned.as<double>()[2 * i];
@@ -324,21 +392,127 @@ int lwhip_batch_stat_equil(lwhip_batch* b)
     HIP_TRY(hipSetDevice(c0->device));
     if (b->se0.Natoms <= 0)
         return LWHIP_OK;
-    for (lwhip_context* c : b->ctxs)
+    for (const int32_t i : b->act)
     {
+        lwhip_context* c = b->ctxs[i];
         const int stp = flush_prefill(c);
         if (stp != LWHIP_OK)
             return stp;
         *c->statusHost = 0;
     }
-    HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, b->seList.p, (int)b->ctxs.size()));
+    HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, b->allActive ? b->seList.p : b->seAct.p, (int)b->act.size()));
     HIP_TRY(hipStreamSynchronize(c0->stream));
-    for (lwhip_context* c : b->ctxs)
-        if (*c->statusHost == LWHIP_ERR_SINGULAR)
+    return batch_singular(b);
+}
+
+int lwhip_batch_stat_equil_report(lwhip_batch* b, double* dPops, int32_t* dPopsMaxIdx)
+{
+    if (!b || b->ctxs.empty() || !dPops)
+        return fail(LWHIP_ERR_INVALID, "batch_stat_equil_report: null argument");
+    lwhip_context* c0 = b->ctxs[0];
+    HIP_TRY(hipSetDevice(c0->device));
+    const int Na = b->se0.Natoms;
+    if (Na <= 0)
+        return LWHIP_OK;
+    const int n = (int)b->ctxs.size(), nAct = (int)b->act.size();
+    const size_t stride = 2 + 2 * (size_t)Na;
+    if (!b->change.p)
+    {
+        // the change records of all columns, a second list of solve arguments that aims at them, the records they become
+        b->seBlocks = stat_eq_blocks(c0->Ns, b->seMaxNl);
+        HIP_TRY(b->change.alloc(c0->mem, (size_t)n * Na * b->seBlocks * 2));
+        HIP_TRY(b->rec.alloc(c0->mem, (size_t)n * stride));
+        HIP_TRY(b->recPinned.reserve(c0->device, (size_t)n * stride * sizeof(double), c0->stream));
+        b->seRepHost = b->seHost;
+        for (int i = 0; i < n; ++i)
+            b->seRepHost[i].change = b->change.p + (size_t)i * Na * b->seBlocks * 2;
+        HIP_TRY(b->seRepList.upload(c0->mem, b->seRepHost));
+        if (!b->allActive)
         {
-            *c->statusHost = 0;
-            return fail(LWHIP_ERR_SINGULAR, "Singular Matrix");
+            const int stu = batch_upload_active(b);
+            if (stu != LWHIP_OK)
+                return stu;
         }
+    }
+    for (const int32_t i : b->act)
+    {
+        lwhip_context* c = b->ctxs[i];
+        const int stp = flush_prefill(c);
+        if (stp != LWHIP_OK)
+            return stp;
+        *c->statusHost = 0;
+    }
+    HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, b->allActive ? b->seRepList.p : b->seRepAct.p, nAct));
+    BatchConvArgs ca{};
+    ca.change = b->change.p;
+    ca.tail = b->tail.p;
+    ca.rec = b->rec.p;
+    ca.cols = b->allActive ? nullptr : b->colsAct.p;
+    ca.Natoms = Na;
+    ca.nBlocks = b->seBlocks;
+    HIP_TRY(launch_batch_conv(ca, nAct, c0->stream));
+    HIP_TRY(hipMemcpyAsync(b->recPinned.host, b->rec.p, (size_t)n * stride * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    b->recCols = b->act;
+    const int st = batch_singular(b);
+    if (st != LWHIP_OK)
+        return st;
+    const double* rec = b->recPinned.as<double>();
+    for (const int32_t i : b->act)
+        for (int q = 0; q < Na; ++q)
+        {
+            dPops[(size_t)i * Na + q] = rec[i * stride + 2 + 2 * q];
+            if (dPopsMaxIdx)
+                dPopsMaxIdx[(size_t)i * Na + q] = (int32_t)rec[i * stride + 3 + 2 * q];
+        }
+    return LWHIP_OK;
+}
+
+int lwhip_batch_conv_records(lwhip_batch* b, double* records, int* strideOut)
+{
+    if (!b || b->ctxs.empty() || !records)
+        return fail(LWHIP_ERR_INVALID, "batch_conv_records: null argument");
+    const size_t stride = 2 + 2 * (size_t)std::max(b->se0.Natoms, 0);
+    if (strideOut)
+        *strideOut = (int)stride;
+    const double* rec = b->recPinned.as<double>();
+    for (const int32_t i : b->recCols)
+        std::memcpy(records + i * stride, rec + i * stride, stride * sizeof(double));
+    return LWHIP_OK;
+}
+
+int lwhip_batch_set_active(lwhip_batch* b, const int32_t* columns, int nActive)
+{
+    if (!b || b->ctxs.empty())
+        return fail(LWHIP_ERR_INVALID, "null batch");
+    const int n = (int)b->ctxs.size();
+    if (nActive < 0 || (nActive > 0 && !columns))
+        return fail(LWHIP_ERR_INVALID, "batch_set_active: nActive < 0, or a count without a list");
+    for (int p = 0; p < nActive; ++p)
+        if (columns[p] < 0 || columns[p] >= n || (p > 0 && columns[p] <= columns[p - 1]))
+            return fail(LWHIP_ERR_INVALID, "batch_set_active: entry " + std::to_string(p) + " (" + std::to_string(columns[p])
+                                               + ") is out of range or not above the one before it");
+    lwhip_context* c0 = b->ctxs[0];
+    HIP_TRY(hipSetDevice(c0->device));
+    const bool all = nActive == 0 || !columns || nActive == n;
+    std::vector<int32_t> act(all ? n : nActive);
+    for (int p = 0; p < (int)act.size(); ++p)
+        act[p] = all ? p : columns[p];
+    if (act == b->act)
+        return LWHIP_OK;
+    b->act = act;
+    b->allActive = all;
+    b->aValid = false; // (the device copy of the apply blocks is that of another set)
+    return all ? LWHIP_OK : batch_upload_active(b);
+}
+
+int lwhip_batch_active(lwhip_batch* b, int32_t* columns, int* nActive)
+{
+    if (!b || b->ctxs.empty() || !nActive)
+        return fail(LWHIP_ERR_INVALID, "batch_active: null argument");
+    *nActive = (int)b->act.size();
+    if (columns)
+        std::copy(b->act.begin(), b->act.end(), columns);
     return LWHIP_OK;
 }
 }

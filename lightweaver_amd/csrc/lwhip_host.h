@@ -762,6 +762,25 @@ struct lwhip_batch
     DevBuf<StatEqArgs> seList; // stat_equil of all active atoms of every column
     StatEqArgs se0{};
     int seMaxNl = 0;
+    // The active set (lwhip_batch_set_active): the lists above stay those of ALL columns; a proper subset gets compacted
+    // copies (position p = column act[p]), which is all a batched kernel needs to run a smaller batch.
+    bool allActive = true;
+    std::vector<int32_t> act;                  // the active columns, increasing (0 .. n-1 when all are)
+    std::vector<const TileArgs*> apHost, apActHost;
+    std::vector<ReduceArgs> rHost, rActHost;
+    std::vector<StatEqArgs> seHost, seRepHost, seActHost, seRepActHost; // (seRep*: change -> this batch's change buffer)
+    std::vector<ApplyArgs> aActHost;
+    DevBuf<const TileArgs*> apAct;
+    DevBuf<ReduceArgs> rAct;
+    DevBuf<ApplyArgs> aAct;
+    DevBuf<StatEqArgs> seAct, seRepList, seRepAct;
+    DevBuf<int32_t> colsAct;                   // act on the device (batch_conv_kernel)
+    // lwhip_batch_stat_equil_report (made by the first call)
+    int seBlocks = 0;                          // solve blocks per atom and column
+    DevBuf<double> change;                     // [n][Natoms][seBlocks][2], what stat_eq_body writes per column
+    DevBuf<double> rec;                        // [n][2 + 2 Natoms]: dJMax, idx, then (dPops, idx) per atom
+    PinnedBlock recPinned;
+    std::vector<int32_t> recCols;              // the columns the last report solved (whose rows of recPinned are its)
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments
     DevBuf<PolLineArgs> polList;     // every column's polarised lines, as polHost (lwhip_batch_compute_polarised_profiles)

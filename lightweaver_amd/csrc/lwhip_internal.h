@@ -630,6 +630,17 @@ struct StatEqArgs
 hipError_t launch_stat_eq(const StatEqArgs& a, int maxNlevel, hipStream_t stream, const StatEqArgs* list = nullptr,
                           int nBatch = 0);
 int stat_eq_blocks(int Ns, int maxNlevel);
+// column batches: the change records of nActive columns (launch_stat_eq with `list`, StatEqArgs::change into `change`) combined
+// into one record per column, one wavefront each
+struct BatchConvArgs
+{
+    const double* change;   // [n][Natoms][nBlocks][2]
+    const double* tail;     // [n][2]: dJMax, idx as the batch's stage 2 left them
+    double* rec;            // [n][2 + 2 Natoms]
+    const int32_t* cols;    // [nActive] original column numbers, or null: block q is column q
+    int32_t Natoms, nBlocks;
+};
+hipError_t launch_batch_conv(const BatchConvArgs& a, int nActive, hipStream_t stream);
 hipError_t launch_peer_publish(const PeerPublishArgs& a, hipStream_t stream);
 // self-test of the exchange: fill `buf` with the rank's pattern / wait for the world's flags (bounded by spinLimit polls) and
 // compare every slot with its rank's pattern; *result = 0 ok, 1 a flag never came, 2 a slot holds something else

@@ -374,6 +374,63 @@ hipError_t launch_stat_eq(const StatEqArgs& a, int maxNlevel, hipStream_t stream
     return hipGetLastError();
 }
 
+// ---- column batches: one convergence record per column -----------------------------------------------------
+// One wavefront per active column.  Per solved atom it combines the column's nBlocks (value, index) pairs of report_change
+// by the rule of Ng::max_change (Source/Ng.hpp:138-156; the host loop of stat_equil_impl for one context): the largest
+// value, the first flattened [level, depth] index among equal values, index 0 for the value 0.  Lane l takes blocks l,
+// l + 64, ...; the lanes' candidates meet in a butterfly (the rule does not depend on the order of combination).  The record
+// [dJMax, idx, dPops_0, idx_0, ...] goes to the row of the column's ORIGINAL number, so one copy of `rec` reports all columns.
+__global__ void __launch_bounds__(64) batch_conv_kernel(const BatchConvArgs a)
+{
+    dbg_poison_lds();
+    const int col = a.cols ? a.cols[blockIdx.x] : (int)blockIdx.x;
+    double* rec = a.rec + (size_t)col * (2 + 2 * a.Natoms);
+    for (int q = 0; q < a.Natoms; ++q)
+    {
+        const double* ch = a.change + ((size_t)col * a.Natoms + q) * a.nBlocks * 2;
+        double v = 0.0;
+        int idx = 0x7fffffff;
+        for (int b = threadIdx.x; b < a.nBlocks; b += 64)
+        {
+            const double x = ch[2 * b];
+            const int i = (int)ch[2 * b + 1];
+            if (x > v || (x == v && x > 0.0 && i < idx))
+            {
+                v = x;
+                idx = i;
+            }
+        }
+        for (int s = 32; s > 0; s >>= 1)
+        {
+            const double ov = __shfl_xor(v, s);
+            const int oi = __shfl_xor(idx, s);
+            if (ov > v || (ov == v && oi < idx))
+            {
+                v = ov;
+                idx = oi;
+            }
+        }
+        if (threadIdx.x == 0)
+        {
+            rec[2 + 2 * q] = v;
+            rec[3 + 2 * q] = (v > 0.0) ? (double)idx : 0.0;
+        }
+    }
+    if (threadIdx.x == 0)
+    {
+        rec[0] = a.tail[2 * (size_t)col];
+        rec[1] = a.tail[2 * (size_t)col + 1];
+    }
+}
+
+hipError_t launch_batch_conv(const BatchConvArgs& a, int nActive, hipStream_t stream)
+{
+    if (nActive < 1 || a.Natoms < 1 || a.nBlocks < 1)
+        return hipErrorInvalidValue;
+    LWHIP_LAUNCH(batch_conv_kernel, dim3(nActive), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
 // ---- time_dependent_update_impl: Source/UpdatePopulations.cpp:120-151 --------------------------------------
 template <int N>
 DEVINL bool time_dep_point_reg(double* n, const double* nOld, const double* Gamma, const double dt, const int Ns, const int k)
