@@ -592,18 +592,47 @@ int lwhip_batch_compute_profiles(lwhip_batch* batch);
  * of range, a list that is not strictly increasing, nActive < 0 or nActive > 0 with columns == NULL: LWHIP_ERR_INVALID, the
  * active set left as it was.  lwhip_batch_active reads the set back: columns [n] (or NULL) and *nActive.
  * Three invariants:
- *  - a retired (inactive) column's device state -- J, I, n, Gamma, rates -- is exactly what its last iteration left: later
- *    batch iterations never touch it;
+ *  - a retired (inactive) column's device state -- J, I, n, Gamma, rates, and with Ng (below) its history and call count --
+ *    is exactly what its last iteration left: later batch iterations never touch it;
  *  - the launch-wide choices made "only if every column qualifies" (symmetric / angle-independent profiles, the plain sweep
  *    instance) are evaluated over ALL columns of the batch, not the active ones: the code path a column runs, and so its
- *    bits, do not depend on who else is still active;
+ *    bits, do not depend on who else is still active -- the Ng step included: a column's store slot, its accelerate
+ *    decision and its coefficients come from its own count and history alone;
  *  - with all columns active the launches and copies of the three entry points are what they were before there was an
- *    active set.
- * Out of scope for batches: Ng acceleration, PRD sub-iterations, time-dependent and charge-conserving updates. */
+ *    active set; and with Ng off they are what they were before there was Ng for batches.
+ * Out of scope for batches: PRD sub-iterations, time-dependent and charge-conserving updates. */
 int lwhip_batch_stat_equil_report(lwhip_batch* batch, double* dPops /* [n][Natoms] */, int32_t* dPopsMaxIdx /* [n][Natoms] or NULL */);
 int lwhip_batch_conv_records(lwhip_batch* batch, double* records /* [n][2 + 2 Natoms] */, int* stride /* or NULL */);
 int lwhip_batch_set_active(lwhip_batch* batch, const int32_t* columns, int nActive);
 int lwhip_batch_active(lwhip_batch* batch, int32_t* columns /* [n] or NULL */, int* nActive);
+
+/* Ng acceleration for column batches: every column behaves as a lone context with lwhip_ng_configure would (struct Ng,
+ * Source/Ng.hpp:16-156, driven as LwContext.stat_equil drives it), with its own history and its own call count, both on the
+ * device; one launch (batch_ng_kernel, one workgroup per active column and solved atom) serves all active columns, whatever
+ * their schedules.  This is the BATCH's Ng: it is separate from a column's own lwhip_ng_configure / lwhip_ng_accelerate,
+ * which keep acting on that context alone and which the batch never reads.
+ *
+ * lwhip_batch_ng_configure: validated as lwhip_ng_configure (0 <= Norder <= 6, Nperiod >= 1 when Norder > 0; else
+ * LWHIP_ERR_INVALID with the previous configuration kept); Ndelay becomes max(Ndelay, Nperiod + 2).  Stores the current
+ * populations of ALL columns, active or not, as their first solution (count = 1) in one launch; a repeated call seeds them
+ * again.  (0, 0, 0) turns Ng off and releases the history.
+ * While configured, lwhip_batch_stat_equil and lwhip_batch_stat_equil_report run the Ng step of the active columns after
+ * their solve, in the same stream and before the one wait; the report's dPops / indices (and the conv records, whose layout
+ * does not change) are then Ng's max_change, taken after any extrapolation -- what Context.stat_equil reports with Ng.  A
+ * reported iteration still costs one copy and one wait.  A column that is inactive for some calls keeps its schedule, as a
+ * lone context whose stat_equil was not called.
+ * lwhip_batch_ng_accelerate: the Ng step alone on the active columns (the batch form of lwhip_ng_accelerate): one launch, one
+ * copy, one wait.  accelerated [n], dPops and dPopsMaxIdx [n][Natoms] may each be NULL; rows of inactive columns are left
+ * untouched.  Before lwhip_batch_ng_configure: LWHIP_ERR_INVALID.  A singular Ng system in an active column:
+ * LWHIP_ERR_SINGULAR (outputs untouched); that column's populations are recorded without extrapolation, as
+ * lwhip_ng_accelerate leaves them, and the other columns are not affected.
+ * lwhip_batch_ng_state (reads only): opts[3] = Norder, Nperiod, Ndelay in effect (Ndelay after the max rule; all zero: off),
+ * counts [n] every column's Ng call count as the device holds it, lastAccelerated [n] whether the column's last Ng step
+ * extrapolated.  Each may be NULL; off: all zero. */
+int lwhip_batch_ng_configure(lwhip_batch* batch, int Norder, int Nperiod, int Ndelay);
+int lwhip_batch_ng_accelerate(lwhip_batch* batch, int32_t* accelerated /* [n] or NULL */, double* dPops /* [n][Natoms] or NULL */,
+                              int32_t* dPopsMaxIdx /* [n][Natoms] or NULL */);
+int lwhip_batch_ng_state(lwhip_batch* batch, int32_t opts[3], int32_t* counts /* [n] or NULL */, int32_t* lastAccelerated /* [n] or NULL */);
 
 /* The intersection table of an x-periodic grid: build_intersection_list (Source/FormalScalar2d.cpp:1188-1327) with
  * dw_intersection_2d (:60-105), uw_intersection_2d (:107-152), uw_intersection_2d_frac_x (:166-206).  Host-side

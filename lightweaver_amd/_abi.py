@@ -262,6 +262,9 @@ SYMBOLS = [
     ('lwhip_batch_conv_records', C.c_int, [C.c_void_p, f64p, C.POINTER(C.c_int)]),
     ('lwhip_batch_set_active', C.c_int, [C.c_void_p, i32p, C.c_int]),
     ('lwhip_batch_active', C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_int)]),
+    ('lwhip_batch_ng_configure', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ('lwhip_batch_ng_accelerate', C.c_int, [C.c_void_p, i32p, f64p, i32p]),
+    ('lwhip_batch_ng_state', C.c_int, [C.c_void_p, i32p, i32p, i32p]),
     ('lwhip_build_intersections', C.c_int, [C.POINTER(lwhip_grid2d), C.POINTER(lwhip_intersection),
                                              C.POINTER(lwhip_intersection), i32p, i32p, C.c_int32,
                                              C.POINTER(lwhip_intersection), C.c_int64, C.POINTER(C.c_int32),

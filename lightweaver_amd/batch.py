@@ -33,6 +33,10 @@ def columns_of_rank(ncolumns: int, world: int, rank: int) -> List[int]:
 
 
 class ColumnBatch:
+    _ng = None          # (Norder, Nperiod, Ndelay) in effect, Ndelay after the max rule -- configure_ng; None: no Ng acceleration
+    _ngCounts = None    # not fused: the Ng calls this batch has made per column (1 after configure_ng) ...
+    _ngLast = None      # ... and whether each column's last one extrapolated
+
     def __init__(self, problems: Sequence[Problem], device: int = 0, stream: Optional[int] = None,
                  device_profiles: bool = True, streams: Optional[Sequence[int]] = None, fused: bool = True):
         """`fused` (default): the columns advance in ONE set of launches per iteration (lwhip_batch_*: one grid
@@ -182,6 +186,9 @@ class ColumnBatch:
             lib = self.contexts[0].lib
             _check(lib, lib.lwhip_batch_stat_equil(self._batch), 'lwhip_batch_stat_equil')
             return
+        if self._ng is not None:    # (a column's Ng step follows its solve and reads its result back: the reporting route)
+            self._stat_equil_report()
+            return
         cols = [self.contexts[i] for i in self.active]
         for c in cols:
             c.stat_equil(deviceResident=True, sync_host=False)
@@ -200,6 +207,7 @@ class ColumnBatch:
         if self._batch is None:
             for i in self.active:
                 pops[i] = self.contexts[i].stat_equil(deviceResident=True)
+            self._ng_note(pops)
             return None, pops
         import ctypes as C
         import numpy as np
@@ -221,10 +229,96 @@ class ColumnBatch:
         Js = [None] * n
         # (plain lists first: this runs between two iterations with the device idle -- 512 columns, 3 ms element by element, 1 ms so)
         dP, dI, rc = dPops.tolist(), dIdx.tolist(), rec.tolist()
+        # (with Ng the solve was followed by every active column's Ng step: whether it extrapolated is the device's word)
+        acc = self.ng_state()['lastAccelerated'] if self._ng is not None else [False] * n
         for i in self.active:
-            pops[i] = IterationUpdate(updatedPops=True, dPops=dP[i], dPopsMaxIdx=dI[i])
+            pops[i] = IterationUpdate(updatedPops=True, dPops=dP[i], dPopsMaxIdx=dI[i], ngAccelerated=acc[i])
             Js[i] = IterationUpdate(updatedJ=True, dJMax=rc[i][0], dJMaxIdx=int(rc[i][1]), crsw=crsw)
         return Js, pops
+
+    # -- Ng acceleration: every column as a lone Context with configure_ng ---------------------------------------------------
+    def configure_ng(self, Norder=0, Nperiod=0, Ndelay=0):
+        """Context.configure_ng for every column (NgOptions; struct Ng, Source/Ng.hpp): each column keeps its own history and
+        its own call count, seeded with its current populations -- all columns, active or not.  From then on stat_equil
+        runs each active column's Ng step after its solve and reports Ng's max_change, taken after any extrapolation.
+        Fused: lwhip_batch_ng_configure -- histories and counts on the device, one launch for the active columns.  Not
+        fused: each column's own Context.configure_ng.  (0, 0, 0) turns it off again; a repeated call seeds again."""
+        No, Np, Nd = int(Norder), int(Nperiod), int(Ndelay)
+        off = (No, Np, Nd) == (0, 0, 0)
+        if self._batch is not None:
+            lib = self.contexts[0].lib
+            _check(lib, lib.lwhip_batch_ng_configure(self._batch, No, Np, Nd), 'lwhip_batch_ng_configure')
+        else:
+            for c in self.contexts:
+                c.configure_ng(No, Np, Nd)
+                if off:
+                    c._ng = None    # (the column's stat_equil takes its plain route again)
+        self._ng = None if off else (No, Np, max(Nd, Np + 2))
+        self._ngCounts = None if off else [1] * len(self.contexts)
+        self._ngLast = None if off else [False] * len(self.contexts)
+
+    def _ng_note(self, pops):
+        """Not fused: count the Ng call each column's update stands for."""
+        if self._ng is None or self._ngCounts is None:
+            return
+        for i, u in enumerate(pops):
+            if u is not None:
+                self._ngCounts[i] += 1
+                self._ngLast[i] = bool(u.ngAccelerated)
+
+    def ng_state(self):
+        """{'options': (Norder, Nperiod, Ndelay) in effect (Ndelay after the max rule) or None when off, 'counts': every
+        column's Ng call count (1 after configure_ng), 'lastAccelerated': whether its last Ng step extrapolated}.  Fused:
+        lwhip_batch_ng_state, the device's own words; not fused: the calls this batch has made."""
+        n = len(self.contexts)
+        if self._batch is None:
+            on = self._ng is not None
+            return dict(options=self._ng, counts=list(self._ngCounts) if on else [0] * n,
+                        lastAccelerated=list(self._ngLast) if on else [False] * n)
+        import ctypes as C
+        import numpy as np
+        lib = self.contexts[0].lib
+        opts = (C.c_int32 * 3)()
+        counts = np.zeros(n, dtype=np.int32)
+        last = np.zeros(n, dtype=np.int32)
+        _check(lib, lib.lwhip_batch_ng_state(self._batch, opts, counts.ctypes.data_as(abi.i32p), last.ctypes.data_as(abi.i32p)),
+               'lwhip_batch_ng_state')
+        o = tuple(opts)
+        return dict(options=None if o == (0, 0, 0) else o, counts=counts.tolist(), lastAccelerated=[bool(x) for x in last])
+
+    def ng_accelerate(self):
+        """The Ng step alone on the active columns, from the populations now on the device (fused:
+        lwhip_batch_ng_accelerate, one launch; not fused: each column's lwhip_ng_accelerate): one
+        IterationUpdate(updatedPops=True, dPops, dPopsMaxIdx, ngAccelerated) per active column, None for the others."""
+        import numpy as np
+        from .context import IterationUpdate
+        if self._ng is None:
+            raise RuntimeError('ng_accelerate before configure_ng')
+        n = len(self.contexts)
+        ups = [None] * n
+        if self._active is not None and not self._active:
+            return ups
+        nAct = sum(1 for a in self.problems[0].atoms if not a.detailed)
+        acc = np.zeros(n, dtype=np.int32)
+        dPops = np.zeros((n, max(nAct, 1)))
+        dIdx = np.zeros((n, max(nAct, 1)), dtype=np.int32)
+        if self._batch is not None:
+            lib = self.contexts[0].lib
+            _check(lib, lib.lwhip_batch_ng_accelerate(self._batch, acc.ctypes.data_as(abi.i32p), dPops.ctypes.data_as(abi.f64p),
+                                                      dIdx.ctypes.data_as(abi.i32p)), 'lwhip_batch_ng_accelerate')
+        else:
+            for i in self.active:
+                c = self.contexts[i]
+                a1 = np.zeros(max(nAct, 1), dtype=np.int32)
+                _check(c.lib, c.lib.lwhip_ng_accelerate(c._h, a1.ctypes.data_as(abi.i32p), dPops[i].ctypes.data_as(abi.f64p),
+                                                        dIdx[i].ctypes.data_as(abi.i32p)), 'lwhip_ng_accelerate')
+                acc[i] = int(a1[:nAct].any())
+        for i in self.active:
+            ups[i] = IterationUpdate(updatedPops=True, dPops=dPops[i, :nAct].tolist(), dPopsMaxIdx=dIdx[i, :nAct].tolist(),
+                                     ngAccelerated=bool(acc[i]))
+        if self._batch is None:
+            self._ng_note(ups)
+        return ups
 
     # -- the active set: the columns formal_sol_gamma_matrices and stat_equil advance ---------------------------------------
     @property
@@ -253,7 +347,7 @@ class ColumnBatch:
         self._active = cols
 
     def iterate_to_convergence(self, Nscatter: int = 3, NmaxIter: int = 2000, JTol: float = 5e-3, popsTol: float = 1e-3,
-                               retire: bool = True, callback: Optional[Callable] = None):
+                               retire: bool = True, callback: Optional[Callable] = None, ng: Optional[tuple] = None):
         """iterate_ctx_se (iterate.py; lightweaver/iterate_ctx.py:85-208) for every column at once, each column judged by its
         own numbers: a column is converged at the first iteration it >= Nscatter whose own dJMax < JTol and max dPops <
         popsTol (DefaultConvergenceCriteria).  retire=True: it leaves the active set at once, so its state stays what that
@@ -264,13 +358,18 @@ class ColumnBatch:
         (NmaxIter - 1 where it did not converge), whether it converged, and its final [JUpdate, popsUpdate] ([] where it
         did not).  callback(it, JUpdates, popsUpdates, active): per-column lists (None for columns inactive in that
         iteration; popsUpdates None while it < Nscatter) and the active set after the iteration's retirements.
-        No Ng acceleration, PRD sub-iterations, time-dependent or charge-conserving updates here."""
+        ng: (Norder, Nperiod, Ndelay) -- configure_ng with them once all columns are active, before the first iteration;
+        None leaves the batch as it is configured.  With Ng each column's popsUpdate carries its own ngAccelerated, and a
+        retired column's history and call count stay frozen with the rest of its state.
+        No PRD sub-iterations, time-dependent or charge-conserving updates here."""
         from .iterate import DefaultConvergenceCriteria
         n = len(self.contexts)
         convs = [DefaultConvergenceCriteria(c, JTol, popsTol, None) for c in self.contexts]
         out = BatchConvergence(iterations=[max(NmaxIter - 1, 0)] * n, converged=[False] * n, final=[[] for _ in range(n)])
         pending = list(range(n))
         self.set_active(None)
+        if ng is not None:
+            self.configure_ng(*ng)
         try:
             for it in range(NmaxIter):
                 if not pending:

@@ -781,6 +781,15 @@ struct lwhip_batch
     DevBuf<double> rec;                        // [n][2 + 2 Natoms]: dJMax, idx, then (dPops, idx) per atom
     PinnedBlock recPinned;
     std::vector<int32_t> recCols;              // the columns the last report solved (whose rows of recPinned are its)
+    // lwhip_batch_ng_configure: Ng acceleration of every column, all state on the device (batch_ng_kernel); off: all empty
+    bool ngOn = false;
+    int ngOrder = 0, ngPeriod = 0, ngDelay = 0; // (ngDelay after the max rule, Ng.hpp:32)
+    int64_t ngHistStride = 0;                  // doubles of history per column
+    DevBuf<BatchNgCol> ngCols;                 // [n] every column's n pool and status word
+    DevBuf<NgAtom> ngAtoms;                    // [Natoms] the solved atoms, offsets inside one column
+    DevBuf<double> ngHistory;                  // [n][Natoms][Norder + 2][Nlevel * Ns]
+    DevBuf<double> ngOut;                      // change [n][Natoms][2], then int32 count [n], accel [n], ticket [n]: one copy
+    PinnedBlock ngPinned;                      // ... lands here (change, count, accel)
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments
     DevBuf<PolLineArgs> polList;     // every column's polarised lines, as polHost (lwhip_batch_compute_polarised_profiles)

@@ -760,4 +760,207 @@ hipError_t launch_ng(const NgArgs& a, int nAtoms, hipStream_t stream)
     LWHIP_LAUNCH(ng_kernel, dim3(nAtoms), dim3(256), lds, stream, a);
     return hipGetLastError();
 }
+
+// ---- column batches: Ng::accelerate + Ng::max_change of every active column in ONE launch -----------------------------------
+// One workgroup per (active column, solved atom); the column is picked through the compacted list as in batch_conv_kernel.
+// What ng_kernel is handed by the host per call -- store slot, accelerate decision, slot list -- is derived here from the
+// column's own count[col] and the three options, so columns on different schedules (one was inactive for some calls) share the
+// launch and nothing per column is uploaded.
+// The No + No^2 weighted sums keep the reference's order without being one thread's work: lane e < No + No^2 owns b(j) or
+// A(i, j) and adds its terms for k = 0 .. L-1 in sequence; the workgroup stages weight(k) = 1 / |n[k]| and the No + 1 rows
+// Delta(i, k) for BNG_CHUNK values of k at a time through LDS (coalesced loads by all lanes; each Delta formed once -- one
+// subtraction, the same bits as ng_kernel's repeated ones).  The term expressions and the `+=` are ng_kernel's, contraction is
+// off in this file, and so the coefficients -- and everything after them -- have ng_kernel's bits.  Rows are BNG_CHUNK + 1
+// doubles apart: the lanes of a sum read different rows at the same k, which would otherwise all sit in one bank pair.
+// count[col] is read by every workgroup of the column and written once, by the workgroup that finishes last (a ticket per
+// column): no workgroup can see the new count in the launch that made it.
+enum { BNG_CHUNK = 64, BNG_ROW = BNG_CHUNK + 1, BNG_THREADS = 256 };
+size_t batch_ng_lds_bytes(int Norder)
+{
+    const int No = Norder > 0 ? Norder : 1;
+    return (8 + (size_t)(No + 2) * BNG_ROW + solve_ws_doubles(No)) * sizeof(double);
+}
+
+__global__ void __launch_bounds__(BNG_THREADS) batch_ng_kernel(const BatchNgArgs a)
+{
+    dbg_poison_lds();
+    extern __shared__ double lds[];
+    __shared__ int sSlot[LWHIP_NG_MAX_ORDER + 2];
+    __shared__ double sV[BNG_THREADS / 64];
+    __shared__ int sI[BNG_THREADS / 64];
+    const int col = a.cols ? a.cols[blockIdx.x] : (int)blockIdx.x;
+    const NgAtom at = a.atoms[blockIdx.y];
+    const BatchNgCol cc = a.columns[col];
+    const int L = at.len, No = a.Norder, nslots = No + 2;
+    double* n = cc.n + (size_t)at.nOff;
+    double* prev = a.history + (size_t)col * a.histStride + (size_t)at.histOff;
+    auto slot = [&](int s) { return prev + (size_t)s * L; };
+    // Ng::accelerate :52-65 for this column's own call count
+    const int stored = a.count[col];
+    const int storeSlot = stored % nslots; // :62
+    const int count = stored + 1;
+    const bool doAccel = No > 0 && count >= a.Ndelay && ((count - a.Ndelay) % a.Nperiod) == 0;
+    if (threadIdx.x < nslots) // slots of count-1, count-2, ... count-Norder-2
+        sSlot[threadIdx.x] = ((count - 1 - (int)threadIdx.x) % nslots + nslots) % nslots;
+    for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+        slot(storeSlot)[k] = n[k];
+    __syncthreads();
+    if (doAccel)
+    {
+        double* bco = lds;               // [No]
+        double* rows = lds + 8;          // [No + 2][BNG_ROW]: weight, Delta(0) .. Delta(No)
+        const SolveWs w(rows + (size_t)(No + 2) * BNG_ROW, No, 1, 0); // the solving lane's workspace
+        const int e = threadIdx.x, nSums = No + No * No;
+        // lane e: b(j) for e < No, else A(i, j) -- rows of Delta(j + 1) and Delta(i + 1)
+        const int j = e < No ? e : (e - No) / No, i = e < No ? 0 : (e - No) % No;
+        const double* rW = rows;
+        const double* rD0 = rows + BNG_ROW;
+        const double* rDj = rows + (size_t)(j + 2) * BNG_ROW;
+        const double* rDi = rows + (size_t)(i + 2) * BNG_ROW;
+        double acc = 0.0;
+        for (int k0 = 0; k0 < L; k0 += BNG_CHUNK)
+        {
+            const int m = min((int)BNG_CHUNK, L - k0);
+            for (int q = threadIdx.x; q < nslots * BNG_CHUNK; q += BNG_THREADS)
+            {
+                const int r = q / BNG_CHUNK, kk = q % BNG_CHUNK;
+                if (kk < m)
+                {
+                    const int k = k0 + kk;
+                    rows[r * BNG_ROW + kk] = r == 0 ? 1.0 / fabs(n[k]) : slot(sSlot[r - 1])[k] - slot(sSlot[r])[k];
+                }
+            }
+            __syncthreads();
+            if (e < No)
+                for (int kk = 0; kk < m; ++kk)
+                    acc += rW[kk] * rD0[kk] * (rD0[kk] - rDj[kk]);
+            else if (e < nSums)
+                for (int kk = 0; kk < m; ++kk)
+                    acc += rW[kk] * (rDj[kk] - rD0[kk]) * (rDi[kk] - rD0[kk]);
+            __syncthreads();
+        }
+        if (e < No)
+            w.b[j] = acc;
+        else if (e < nSums)
+            w.A[i * No + j] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0)
+        {
+            const bool ok = d_solve_lin_eq(No, w);
+            for (int q = 0; q < No; ++q)
+                bco[q] = ok ? (double)w.b[q] : 0.0;
+            if (!ok)
+                atomicExch(cc.status, LWHIP_ERR_SINGULAR);
+        }
+        __syncthreads();
+        // sol += sum_i b_i (previous(count-i-2) - previous(count-1)), then previous(count-1) = sol  :104-113
+        double* p0 = slot(sSlot[0]);
+        for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+        {
+            double v = n[k];
+            const double p0k = p0[k];
+            for (int q = 0; q < No; ++q)
+                v += bco[q] * (slot(sSlot[q + 1])[k] - p0k);
+            n[k] = v;
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+            p0[k] = n[k];
+        __syncthreads();
+    }
+    // max_change :138-156 between the last two stored solutions (count >= 2 here: configure stored the first)
+    double best = 0.0;
+    int bestIdx = 0x7fffffff;
+    {
+        const double* old = slot(sSlot[1]);
+        const double* cur = slot(storeSlot);
+        for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+        {
+            const double c = cur[k];
+            if (c != 0.0)
+            {
+                const double change = fabs((c - old[k]) / c);
+                if (change > best)
+                {
+                    best = change;
+                    bestIdx = k;
+                }
+            }
+        }
+    }
+    // (the largest value, the first index among equal values: the rule does not depend on the order of combination)
+    for (int s = 32; s > 0; s >>= 1)
+    {
+        const double ov = __shfl_xor(best, s);
+        const int oi = __shfl_xor(bestIdx, s);
+        if (ov > best || (ov == best && oi < bestIdx))
+        {
+            best = ov;
+            bestIdx = oi;
+        }
+    }
+    if ((threadIdx.x & 63) == 0)
+    {
+        sV[threadIdx.x >> 6] = best;
+        sI[threadIdx.x >> 6] = bestIdx;
+    }
+    __syncthreads(); // (also: every lane's read of count[col] lies before the ticket below)
+    if (threadIdx.x == 0)
+    {
+        for (int q = 1; q < BNG_THREADS / 64; ++q)
+            if (sV[q] > best || (sV[q] == best && sI[q] < bestIdx))
+            {
+                best = sV[q];
+                bestIdx = sI[q];
+            }
+        double* ch = a.change + ((size_t)col * a.Natoms + blockIdx.y) * 2;
+        ch[0] = best;
+        ch[1] = best > 0.0 ? (double)bestIdx : 0.0;
+        // the column's last workgroup writes count + 1 back, after every workgroup's read of it
+        __threadfence();
+        if (atomicAdd(a.ticket + col, 1) == (int)gridDim.y - 1)
+        {
+            a.ticket[col] = 0;
+            a.accel[col] = doAccel ? 1 : 0;
+            a.count[col] = count;
+        }
+    }
+}
+
+// lwhip_batch_ng_configure: every column's current populations into slot 0, the other slots cleared, count = 1 -- one launch,
+// one workgroup per (column, solved atom), ALL columns
+__global__ void __launch_bounds__(BNG_THREADS) batch_ng_seed_kernel(const BatchNgArgs a)
+{
+    const int col = blockIdx.x;
+    const NgAtom at = a.atoms[blockIdx.y];
+    const double* n = a.columns[col].n + (size_t)at.nOff;
+    double* prev = a.history + (size_t)col * a.histStride + (size_t)at.histOff;
+    const int L = at.len;
+    for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+        prev[k] = n[k];
+    for (size_t k = (size_t)L + threadIdx.x; k < (size_t)(a.Norder + 2) * L; k += BNG_THREADS)
+        prev[k] = 0.0;
+    if (blockIdx.y == 0 && threadIdx.x == 0)
+    {
+        a.count[col] = 1; // the constructor stores the current solution, Ng.hpp:34-38
+        a.accel[col] = 0;
+        a.ticket[col] = 0;
+    }
+}
+
+hipError_t launch_batch_ng(const BatchNgArgs& a, int nActive, hipStream_t stream)
+{
+    if (nActive < 1 || a.Natoms < 1 || a.Norder < 0 || a.Norder > LWHIP_NG_MAX_ORDER || (a.Norder > 0 && a.Nperiod < 1))
+        return hipErrorInvalidValue;
+    LWHIP_LAUNCH(batch_ng_kernel, dim3(nActive, a.Natoms), dim3(BNG_THREADS), batch_ng_lds_bytes(a.Norder), stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_ng_seed(const BatchNgArgs& a, int n, hipStream_t stream)
+{
+    if (n < 1 || a.Natoms < 1)
+        return hipErrorInvalidValue;
+    LWHIP_LAUNCH(batch_ng_seed_kernel, dim3(n, a.Natoms), dim3(BNG_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
 }
