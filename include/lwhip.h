@@ -464,9 +464,14 @@ int lwhip_prd_finalise(lwhip_context* ctx, double* dRho, int32_t* dRhoMaxIdx, do
  * lwhip_ng_accelerate: call after each population update: records the new populations, every Nperiod
  *   calls from the Ndelay-th on replaces them by the Ng extrapolation, and reports per active atom whether
  *   it accelerated, the max relative change between the last two recorded solutions and its flattened
- *   [level, depth] index. */
+ *   [level, depth] index.
+ * lwhip_ng_state (reads only): lwhip_batch_ng_state for this one context -- opts[3] = Norder, Nperiod, Ndelay in effect
+ *   (Ndelay after the max rule), *count the Ng call count as the device holds it (1 after lwhip_ng_configure),
+ *   *lastAccelerated whether the last step extrapolated.  Each may be NULL; not configured: all zero.
+ * The history and the call count live on the device; a context is served as a column batch of one column (below). */
 int lwhip_ng_configure(lwhip_context* ctx, int Norder, int Nperiod, int Ndelay);
 int lwhip_ng_accelerate(lwhip_context* ctx, int32_t* accelerated, double* dPops, int32_t* dPopsMaxIdx);
+int lwhip_ng_state(lwhip_context* ctx, int32_t opts[3], int32_t* count, int32_t* lastAccelerated);
 
 /* time_dependent_update (FsIterationFns::time_dep_update, Source/LwFormalInterface.hpp:92,123;
  * time_dependent_update_impl, Source/UpdatePopulations.cpp:120-151): for atom `atom`, per depth
@@ -608,8 +613,8 @@ int lwhip_batch_active(lwhip_batch* batch, int32_t* columns /* [n] or NULL */, i
 
 /* Ng acceleration for column batches: every column behaves as a lone context with lwhip_ng_configure would (struct Ng,
  * Source/Ng.hpp:16-156, driven as LwContext.stat_equil drives it), with its own history and its own call count, both on the
- * device; one launch (batch_ng_kernel, one workgroup per active column and solved atom) serves all active columns, whatever
- * their schedules.  This is the BATCH's Ng: it is separate from a column's own lwhip_ng_configure / lwhip_ng_accelerate,
+ * device; one launch (ng_kernel, one workgroup per active column and solved atom -- the kernel of lwhip_ng_accelerate, for
+ * which a lone context is a batch of one) serves all active columns, whatever their schedules.  This is the BATCH's Ng: it is separate from a column's own lwhip_ng_configure / lwhip_ng_accelerate,
  * which keep acting on that context alone and which the batch never reads.
  *
  * lwhip_batch_ng_configure: validated as lwhip_ng_configure (0 <= Norder <= 6, Nperiod >= 1 when Norder > 0; else

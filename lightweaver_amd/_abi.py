@@ -275,6 +275,7 @@ SYMBOLS = [
     ('lwhip_prd_finalise', C.c_int, [ctx_p, f64p, i32p, f64p, i32p]),
     ('lwhip_ng_configure', C.c_int, [ctx_p, C.c_int, C.c_int, C.c_int]),
     ('lwhip_ng_accelerate', C.c_int, [ctx_p, i32p, f64p, i32p]),
+    ('lwhip_ng_state', C.c_int, [ctx_p, i32p, i32p, i32p]),
     ('lwhip_time_dep_update', C.c_int, [ctx_p, C.c_int, f64p, C.c_double]),
     ('lwhip_nr_post_update', C.c_int, [ctx_p, C.POINTER(lwhip_nr_args)]),
     ('lwhip_set_depth_range', C.c_int, [ctx_p, C.c_int, C.c_int]),

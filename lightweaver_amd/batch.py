@@ -34,8 +34,6 @@ def columns_of_rank(ncolumns: int, world: int, rank: int) -> List[int]:
 
 class ColumnBatch:
     _ng = None          # (Norder, Nperiod, Ndelay) in effect, Ndelay after the max rule -- configure_ng; None: no Ng acceleration
-    _ngCounts = None    # not fused: the Ng calls this batch has made per column (1 after configure_ng) ...
-    _ngLast = None      # ... and whether each column's last one extrapolated
 
     def __init__(self, problems: Sequence[Problem], device: int = 0, stream: Optional[int] = None,
                  device_profiles: bool = True, streams: Optional[Sequence[int]] = None, fused: bool = True):
@@ -207,7 +205,6 @@ class ColumnBatch:
         if self._batch is None:
             for i in self.active:
                 pops[i] = self.contexts[i].stat_equil(deviceResident=True)
-            self._ng_note(pops)
             return None, pops
         import ctypes as C
         import numpy as np
@@ -254,27 +251,17 @@ class ColumnBatch:
                 if off:
                     c._ng = None    # (the column's stat_equil takes its plain route again)
         self._ng = None if off else (No, Np, max(Nd, Np + 2))
-        self._ngCounts = None if off else [1] * len(self.contexts)
-        self._ngLast = None if off else [False] * len(self.contexts)
-
-    def _ng_note(self, pops):
-        """Not fused: count the Ng call each column's update stands for."""
-        if self._ng is None or self._ngCounts is None:
-            return
-        for i, u in enumerate(pops):
-            if u is not None:
-                self._ngCounts[i] += 1
-                self._ngLast[i] = bool(u.ngAccelerated)
 
     def ng_state(self):
         """{'options': (Norder, Nperiod, Ndelay) in effect (Ndelay after the max rule) or None when off, 'counts': every
-        column's Ng call count (1 after configure_ng), 'lastAccelerated': whether its last Ng step extrapolated}.  Fused:
-        lwhip_batch_ng_state, the device's own words; not fused: the calls this batch has made."""
+        column's Ng call count (1 after configure_ng), 'lastAccelerated': whether its last Ng step extrapolated}: the device's
+        own words -- fused: lwhip_batch_ng_state; not fused: each column's Context.ng_state."""
         n = len(self.contexts)
         if self._batch is None:
-            on = self._ng is not None
-            return dict(options=self._ng, counts=list(self._ngCounts) if on else [0] * n,
-                        lastAccelerated=list(self._ngLast) if on else [False] * n)
+            if self._ng is None:
+                return dict(options=None, counts=[0] * n, lastAccelerated=[False] * n)
+            sts = [c.ng_state() for c in self.contexts]
+            return dict(options=self._ng, counts=[s['count'] for s in sts], lastAccelerated=[s['lastAccelerated'] for s in sts])
         import ctypes as C
         import numpy as np
         lib = self.contexts[0].lib
@@ -316,8 +303,6 @@ class ColumnBatch:
         for i in self.active:
             ups[i] = IterationUpdate(updatedPops=True, dPops=dPops[i, :nAct].tolist(), dPopsMaxIdx=dIdx[i, :nAct].tolist(),
                                      ngAccelerated=bool(acc[i]))
-        if self._batch is None:
-            self._ng_note(ups)
         return ups
 
     # -- the active set: the columns formal_sol_gamma_matrices and stat_equil advance ---------------------------------------

@@ -281,6 +281,15 @@ class Context:
                'lwhip_ng_configure')
         self._ng = (Norder, Nperiod, Ndelay)
 
+    def ng_state(self):
+        """ColumnBatch.ng_state for this one context (lwhip_ng_state, the device's own words): {'options': (Norder, Nperiod,
+        Ndelay) in effect (Ndelay after the max rule) or None before configure_ng, 'count': the Ng call count (1 after
+        configure_ng), 'lastAccelerated': whether the last Ng step extrapolated}."""
+        opts, count, last = (C.c_int32 * 3)(), C.c_int32(0), C.c_int32(0)
+        _check(self.lib, self.lib.lwhip_ng_state(self._h, opts, C.byref(count), C.byref(last)), 'lwhip_ng_state')
+        o = tuple(opts)
+        return dict(options=None if o == (0, 0, 0) else o, count=count.value, lastAccelerated=bool(last.value))
+
     def prd_redistribute(self, maxIter=3, tol=1e-2, deviceResident=False, include_detailed_atoms=None) -> IterationUpdate:
         """PRD sub-iterations, LwContext.prd_redistribute (Source/LwMiddleLayer.pyx:3647-3684): updates rhoPrd of
         every PRD line of the active atoms -- and, on a Context created with prdDetailed=True (ExtraParams

@@ -1406,87 +1406,197 @@ int stat_equil_impl(lwhip_context* c, int atom, bool wait, double* dPops, int32_
 }
 }
 
-extern "C"
+// ---- Ng acceleration: the one host driver of ng_kernel (NgState, lwhip_host.h), for a lone context and for a batch ----------
+namespace lwhip
 {
-int lwhip_ng_configure(lwhip_context* c, int Norder, int Nperiod, int Ndelay)
+NgArgs ng_args(const NgState& s, const int32_t* activeCols)
 {
-    if (!c)
-        return fail(LWHIP_ERR_INVALID, "null context");
+    NgArgs a{};
+    a.columns = s.columns.p;
+    a.atoms = s.atoms.p;
+    a.cols = activeCols;
+    a.history = s.history.p;
+    a.histStride = s.histStride;
+    a.count = s.count();
+    a.ticket = a.count + 2 * s.n;
+    a.change = s.mappedChange ? s.mappedChange : s.out.p;
+    a.accel = s.mappedChange ? (int32_t*)(s.mappedChange + s.change_doubles()) : a.count + s.n;
+    a.Natoms = s.Natoms;
+    a.Norder = s.order;
+    a.Nperiod = s.period;
+    a.Ndelay = s.delay;
+    return a;
+}
+
+hipError_t ng_step(const NgState& s, const int32_t* activeCols, int nActive, hipStream_t stream)
+{
+    return launch_ng(ng_args(s, activeCols), nActive, stream);
+}
+
+// off: the history goes, and every entry point is what it was before Ng was configured
+int ng_off(NgState& s, hipStream_t stream)
+{
+    HIP_TRY(hipStreamSynchronize(stream)); // (nothing may still read what is released)
+    s.on = false;
+    s.order = s.period = s.delay = 0;
+    s.histStride = 0;
+    s.history.release();
+    s.out.release();
+    s.pinned.release();
+    return LWHIP_OK;
+}
+
+int ng_configure(NgState& s, const std::vector<lwhip_context*>& cols, int Norder, int Nperiod, int Ndelay, bool lone)
+{
     if (Norder < 0 || Norder > LWHIP_NG_MAX_ORDER || (Norder > 0 && Nperiod < 1))
         return fail(LWHIP_ERR_INVALID, "Ng: 0 <= Norder <= 6 and Nperiod >= 1");
-    HIP_TRY(hipSetDevice(c->device));
-    c->ngOrder = Norder;
-    c->ngPeriod = Nperiod;
-    c->ngDelay = std::max(Ndelay, Nperiod + 2); // Ng.hpp:32
-    c->ngCount = 1;                             // the constructor stores the current solution :34-38
+    lwhip_context* c0 = cols[0];
+    const size_t n = cols.size();
+    // the solved atoms, in the order of the solve (the columns of a batch share them: batch_create checked)
     std::vector<NgAtom> atoms;
     int64_t hist = 0;
-    for (int ia = 0; ia < c->Natom; ++ia)
+    for (int ia = 0; ia < c0->Natom; ++ia)
     {
-        if (c->atoms[ia].detailed)
+        if (c0->atoms[ia].detailed)
             continue;
         NgAtom at{};
-        at.len = c->atoms[ia].Nlevel * c->Ns;
-        at.nOff = (int64_t)c->levelOff[ia] * c->Ns;
+        at.len = c0->atoms[ia].Nlevel * c0->Ns;
+        at.nOff = (int64_t)c0->levelOff[ia] * c0->Ns;
         at.histOff = hist;
         hist += (int64_t)(Norder + 2) * at.len;
         atoms.push_back(at);
     }
-    c->ngAtomsHost = atoms;
-    if (atoms.empty())
-        return LWHIP_OK;
-    HIP_TRY(c->ngAtoms.upload(c->mem, atoms));
-    HIP_TRY(c->ngHistory.alloc(c->mem, (size_t)hist));
-    HIP_TRY(hipMemsetAsync(c->ngHistory.p, 0, (size_t)hist * sizeof(double), c->stream));
-    for (const NgAtom& at : atoms)
-        HIP_TRY(hipMemcpyAsync(c->ngHistory.p + at.histOff, c->n.p + at.nOff, (size_t)at.len * sizeof(double),
-                               hipMemcpyDeviceToDevice, c->stream));
-    c->ngConfigured = true;
+    if ((!lone && Norder == 0 && Nperiod == 0 && Ndelay == 0) || atoms.empty())
+        return ng_off(s, c0->stream);
+    if (lone && c0->changeCount < 2 * atoms.size() + 1) // (sized for every atom, and to spare, at lwhip_create: host_block_init)
+        return fail(LWHIP_ERR_INVALID, "Ng: the context's host block is too small for the change records");
+    if (!s.columns.p)
+    {
+        std::vector<NgCol> cv(n);
+        for (size_t i = 0; i < n; ++i)
+            cv[i] = { cols[i]->n.p, cols[i]->statusDev };
+        HIP_TRY(s.columns.upload(c0->mem, cv));
+        HIP_TRY(s.atoms.alloc(c0->mem, atoms.size(), false));
+    }
+    s.n = (int)n;
+    s.Natoms = (int)atoms.size();
+    const size_t outDoubles = s.change_doubles() + (3 * n * sizeof(int32_t) + sizeof(double) - 1) / sizeof(double);
+    if (s.history.n != n * (size_t)hist || !s.out.p)
+    {
+        // (a repeated call with another order: the last step may still read the buffers replaced.  Past the validation
+        // above only an allocation can fail, and then Ng is off.)
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        s.on = false;
+        s.order = s.period = s.delay = 0;
+        HIP_TRY(s.history.alloc(c0->mem, n * (size_t)hist, false)); // (the seed launch writes every slot)
+        HIP_TRY(s.out.alloc(c0->mem, outDoubles));
+        HIP_TRY(s.pinned.reserve(c0->device, outDoubles * sizeof(double), c0->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(s.atoms.p, atoms.data(), atoms.size() * sizeof(NgAtom), hipMemcpyHostToDevice, c0->stream));
+    s.order = Norder;
+    s.period = Nperiod;
+    s.delay = std::max(Ndelay, Nperiod + 2); // Ng.hpp:32
+    s.histStride = hist;
+    s.mappedChange = lone ? c0->changeDev : nullptr;
+    s.mappedChangeHost = lone ? c0->changeHost : nullptr;
+    s.on = true;
+    // every column's populations into slot 0, the other slots cleared, count = 1 (the constructor stores the current solution,
+    // Ng.hpp:34-38): a repeated configure seeds again
+    HIP_TRY(launch_ng_seed(ng_args(s, nullptr), (int)n, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream)); // (`atoms` goes when this returns)
     return LWHIP_OK;
+}
+
+int ng_fetch(NgState& s, hipStream_t stream)
+{
+    if (!s.mappedChange) // change, count, accel: one copy
+        HIP_TRY(hipMemcpyAsync(s.pinned.host, s.out.p, s.change_doubles() * sizeof(double) + 2 * (size_t)s.n * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return LWHIP_OK;
+}
+
+void ng_changes(const NgState& s, int col, double* dPops, int32_t* dPopsMaxIdx)
+{
+    const double* ch = s.change_host() + (size_t)col * s.Natoms * 2;
+    for (int q = 0; q < s.Natoms; ++q)
+    {
+        if (dPops)
+            dPops[q] = ch[2 * q];
+        if (dPopsMaxIdx)
+            dPopsMaxIdx[q] = (int32_t)ch[2 * q + 1];
+    }
+}
+
+int ng_read_state(NgState& s, int n, hipStream_t stream, int32_t opts[3], int32_t* counts, int32_t* lastAccelerated)
+{
+    if (opts)
+    {
+        opts[0] = s.order;
+        opts[1] = s.period;
+        opts[2] = s.delay;
+    }
+    if (!s.on)
+    {
+        if (counts)
+            std::fill(counts, counts + n, 0);
+        if (lastAccelerated)
+            std::fill(lastAccelerated, lastAccelerated + n, 0);
+        return LWHIP_OK;
+    }
+    if (!counts && !lastAccelerated)
+        return LWHIP_OK;
+    // the device's own words: count [n] and accel [n] lie together behind the change records
+    const size_t off = s.change_doubles() * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(s.pinned.host + off, (const unsigned char*)s.out.p + off, 2 * (size_t)n * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (counts)
+        std::copy(s.count_host(), s.count_host() + n, counts);
+    if (lastAccelerated)
+        std::copy(s.accel_host(), s.accel_host() + n, lastAccelerated);
+    return LWHIP_OK;
+}
+}
+
+extern "C"
+{
+// A lone context is a batch of one column whose change records and accel word the kernel stores into the context's host-mapped
+// block: a step is one launch and one wait, no copy.  (0, 0, 0) is order 0 here: no extrapolation, the changes still tracked.
+int lwhip_ng_configure(lwhip_context* c, int Norder, int Nperiod, int Ndelay)
+{
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, "null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return ng_configure(c->ng, { c }, Norder, Nperiod, Ndelay, true);
 }
 
 int lwhip_ng_accelerate(lwhip_context* c, int32_t* accelerated, double* dPops, int32_t* dPopsMaxIdx)
 {
     if (!c)
         return fail(LWHIP_ERR_INVALID, "null context");
-    if (!c->ngConfigured)
+    if (!c->ng.on)
         return fail(LWHIP_ERR_INVALID, "lwhip_ng_accelerate before lwhip_ng_configure");
-    const int nAt = (int)c->ngAtomsHost.size();
-    if (nAt == 0)
-        return LWHIP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->changeCount < (size_t)2 * nAt)
-        return fail(LWHIP_ERR_INVALID, "Ng: the context's host block is too small for the change records");
-    const int No = c->ngOrder, nslots = No + 2;
-    NgArgs a{};
-    a.atoms = c->ngAtoms.p;
-    a.n = c->n.p;
-    a.history = c->ngHistory.p;
-    a.change = c->changeDev;
-    a.status = c->statusDev;
-    a.Norder = No;
-    a.storeSlot = c->ngCount % nslots; // Ng.hpp:62
-    c->ngCount += 1;
-    a.doAccel = (No > 0 && c->ngCount >= c->ngDelay && ((c->ngCount - c->ngDelay) % c->ngPeriod) == 0) ? 1 : 0;
-    for (int i = 0; i < No + 2; ++i)
-        a.slots[i] = ((c->ngCount - 1 - i) % nslots + nslots) % nslots;
-    a.haveTwo = c->ngCount >= 2 ? 1 : 0;
-    a.oldSlot = ((c->ngCount - 2) % nslots + nslots) % nslots;
     *c->statusHost = 0;
-    HIP_TRY(launch_ng(a, nAt, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(ng_step(c->ng, nullptr, 1, c->stream));
+    const int st = ng_fetch(c->ng, c->stream);
+    if (st != LWHIP_OK)
+        return st;
     if (*c->statusHost == LWHIP_ERR_SINGULAR)
         return fail(LWHIP_ERR_SINGULAR, "Singular Matrix");
-    for (int q = 0; q < nAt; ++q)
-    {
-        if (accelerated)
-            accelerated[q] = a.doAccel;
-        if (dPops)
-            dPops[q] = c->changeHost[2 * q];
-        if (dPopsMaxIdx)
-            dPopsMaxIdx[q] = (int32_t)c->changeHost[2 * q + 1];
-    }
+    if (accelerated)
+        std::fill(accelerated, accelerated + c->ng.Natoms, *c->ng.accel_host());
+    ng_changes(c->ng, 0, dPops, dPopsMaxIdx);
     return LWHIP_OK;
+}
+
+int lwhip_ng_state(lwhip_context* c, int32_t opts[3], int32_t* count, int32_t* lastAccelerated)
+{
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, "null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return ng_read_state(c->ng, 1, c->stream, opts, count, lastAccelerated);
 }
 
 int lwhip_set_djmax_index_mode(lwhip_context* c, int mode)

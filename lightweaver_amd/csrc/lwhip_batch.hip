@@ -108,32 +108,10 @@ static int batch_singular(lwhip_batch* b)
     return LWHIP_OK;
 }
 
-// Ng acceleration of the batch (lwhip_batch_ng_configure): the arguments of batch_ng_kernel / batch_ng_seed_kernel.  The three
-// int32 arrays follow the change records in the one allocation ngOut, so one copy brings back all a call reports.
-static size_t batch_ng_change_doubles(const lwhip_batch* b) { return b->ctxs.size() * (size_t)b->se0.Natoms * 2; }
-static BatchNgArgs batch_ng_args(lwhip_batch* b)
-{
-    const size_t n = b->ctxs.size();
-    BatchNgArgs a{};
-    a.columns = b->ngCols.p;
-    a.atoms = b->ngAtoms.p;
-    a.cols = b->allActive ? nullptr : b->colsAct.p;
-    a.history = b->ngHistory.p;
-    a.histStride = b->ngHistStride;
-    a.change = b->ngOut.p;
-    a.count = (int32_t*)(b->ngOut.p + batch_ng_change_doubles(b));
-    a.accel = a.count + n;
-    a.ticket = a.accel + n;
-    a.Natoms = b->se0.Natoms;
-    a.Norder = b->ngOrder;
-    a.Nperiod = b->ngPeriod;
-    a.Ndelay = b->ngDelay;
-    return a;
-}
 // the Ng step of the active columns, queued behind their solve
 static hipError_t batch_ng_step(lwhip_batch* b)
 {
-    return launch_batch_ng(batch_ng_args(b), (int)b->act.size(), b->ctxs[0]->stream);
+    return ng_step(b->ng, b->allActive ? nullptr : b->colsAct.p, (int)b->act.size(), b->ctxs[0]->stream);
 }
 
 namespace lwhip
@@ -429,7 +407,7 @@ int lwhip_batch_stat_equil(lwhip_batch* b)
         *c->statusHost = 0;
     }
     HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, b->allActive ? b->seList.p : b->seAct.p, (int)b->act.size()));
-    if (b->ngOn)
+    if (b->ng.on)
         HIP_TRY(batch_ng_step(b));
     HIP_TRY(hipStreamSynchronize(c0->stream));
     return batch_singular(b);
@@ -452,7 +430,7 @@ int lwhip_batch_stat_equil_report(lwhip_batch* b, double* dPops, int32_t* dPopsM
         HIP_TRY(b->rec.alloc(c0->mem, (size_t)n * stride));
         HIP_TRY(b->recPinned.reserve(c0->device, (size_t)n * stride * sizeof(double), c0->stream));
     }
-    if (!b->ngOn && !b->change.p)
+    if (!b->ng.on && !b->change.p)
     {
         // the change records of all columns and a second list of solve arguments that aims at them
         b->seBlocks = stat_eq_blocks(c0->Ns, b->seMaxNl);
@@ -481,13 +459,13 @@ int lwhip_batch_stat_equil_report(lwhip_batch* b, double* dPops, int32_t* dPopsM
     ca.rec = b->rec.p;
     ca.cols = b->allActive ? nullptr : b->colsAct.p;
     ca.Natoms = Na;
-    if (b->ngOn)
+    if (b->ng.on)
     {
         // the plain solve, then the Ng step: the reported change is Ng's max_change, taken after any extrapolation
         // (rel_diff_ng_accelerate, Source/LwMiddleLayer.pyx:3318-3346) -- one (value, index) pair per column and atom
         HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, b->allActive ? b->seList.p : b->seAct.p, nAct));
         HIP_TRY(batch_ng_step(b));
-        ca.change = b->ngOut.p;
+        ca.change = b->ng.out.p;
         ca.nBlocks = 1;
     }
     else
@@ -562,107 +540,44 @@ int lwhip_batch_active(lwhip_batch* b, int32_t* columns, int* nActive)
     return LWHIP_OK;
 }
 
+// Ng acceleration of every column: the shared driver (ng_configure ..., lwhip_api.hip) with the batch's n columns.  (0, 0, 0): off.
 int lwhip_batch_ng_configure(lwhip_batch* b, int Norder, int Nperiod, int Ndelay)
 {
     if (!b || b->ctxs.empty())
         return fail(LWHIP_ERR_INVALID, "null batch");
-    if (Norder < 0 || Norder > LWHIP_NG_MAX_ORDER || (Norder > 0 && Nperiod < 1))
-        return fail(LWHIP_ERR_INVALID, "Ng: 0 <= Norder <= 6 and Nperiod >= 1");
     lwhip_context* c0 = b->ctxs[0];
     HIP_TRY(hipSetDevice(c0->device));
-    const size_t n = b->ctxs.size();
-    const int Na = b->se0.Natoms;
-    if ((Norder == 0 && Nperiod == 0 && Ndelay == 0) || Na <= 0)
+    const int st = ng_configure(b->ng, b->ctxs, Norder, Nperiod, Ndelay, false);
+    if (st == LWHIP_OK && b->ng.on && b->ng.Natoms != b->se0.Natoms) // (batch_conv_kernel reads the change records by se0's count)
     {
-        // off: the history goes, and every entry point is what it was before there was Ng for batches
-        HIP_TRY(hipStreamSynchronize(c0->stream)); // (nothing may still read what is released)
-        b->ngOn = false;
-        b->ngOrder = b->ngPeriod = b->ngDelay = 0;
-        b->ngHistStride = 0;
-        b->ngHistory.release();
-        b->ngOut.release();
-        b->ngPinned.release();
-        return LWHIP_OK;
-    }
-    // the solved atoms, in the order of the batch's solve (batch_create checked that the columns share them)
-    std::vector<NgAtom> atoms;
-    int64_t hist = 0;
-    for (int ia = 0; ia < c0->Natom; ++ia)
-    {
-        if (c0->atoms[ia].detailed)
-            continue;
-        NgAtom at{};
-        at.len = c0->atoms[ia].Nlevel * c0->Ns;
-        at.nOff = (int64_t)c0->levelOff[ia] * c0->Ns;
-        at.histOff = hist;
-        hist += (int64_t)(Norder + 2) * at.len;
-        atoms.push_back(at);
-    }
-    if ((int)atoms.size() != Na)
+        (void)ng_off(b->ng, c0->stream);
         return fail(LWHIP_ERR_INVALID, "batch_ng_configure: the solved atoms are not those of the batch's solve");
-    if (!b->ngCols.p)
-    {
-        std::vector<BatchNgCol> cols(n);
-        for (size_t i = 0; i < n; ++i)
-            cols[i] = { b->ctxs[i]->n.p, b->ctxs[i]->statusDev };
-        HIP_TRY(b->ngCols.upload(c0->mem, cols));
-        HIP_TRY(b->ngAtoms.alloc(c0->mem, atoms.size(), false));
     }
-    const size_t outDoubles = batch_ng_change_doubles(b) + (3 * n * sizeof(int32_t) + sizeof(double) - 1) / sizeof(double);
-    if (b->ngHistory.n != n * (size_t)hist || !b->ngOut.p)
-    {
-        // (a repeated call with another order: the last step may still read the buffers replaced.  Past the validation
-        // above only an allocation can fail, and then Ng is off.)
-        HIP_TRY(hipStreamSynchronize(c0->stream));
-        b->ngOn = false;
-        b->ngOrder = b->ngPeriod = b->ngDelay = 0;
-        HIP_TRY(b->ngHistory.alloc(c0->mem, n * (size_t)hist, false)); // (the seed launch writes every slot)
-        HIP_TRY(b->ngOut.alloc(c0->mem, outDoubles));
-        HIP_TRY(b->ngPinned.reserve(c0->device, outDoubles * sizeof(double), c0->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(b->ngAtoms.p, atoms.data(), atoms.size() * sizeof(NgAtom), hipMemcpyHostToDevice, c0->stream));
-    b->ngOrder = Norder;
-    b->ngPeriod = Nperiod;
-    b->ngDelay = std::max(Ndelay, Nperiod + 2); // Ng.hpp:32
-    b->ngHistStride = hist;
-    b->ngOn = true;
-    HIP_TRY(launch_batch_ng_seed(batch_ng_args(b), (int)n, c0->stream));
-    HIP_TRY(hipStreamSynchronize(c0->stream)); // (`atoms` goes when this returns)
-    return LWHIP_OK;
+    return st;
 }
 
 int lwhip_batch_ng_accelerate(lwhip_batch* b, int32_t* accelerated, double* dPops, int32_t* dPopsMaxIdx)
 {
     if (!b || b->ctxs.empty())
         return fail(LWHIP_ERR_INVALID, "null batch");
-    if (!b->ngOn)
+    if (!b->ng.on)
         return fail(LWHIP_ERR_INVALID, "lwhip_batch_ng_accelerate before lwhip_batch_ng_configure");
     lwhip_context* c0 = b->ctxs[0];
     HIP_TRY(hipSetDevice(c0->device));
-    const size_t n = b->ctxs.size();
-    const int Na = b->se0.Natoms;
+    const int Na = b->ng.Natoms;
     for (const int32_t i : b->act)
         *b->ctxs[i]->statusHost = 0;
     HIP_TRY(batch_ng_step(b));
-    const size_t bytes = batch_ng_change_doubles(b) * sizeof(double) + 2 * n * sizeof(int32_t); // change, count, accel
-    HIP_TRY(hipMemcpyAsync(b->ngPinned.host, b->ngOut.p, bytes, hipMemcpyDeviceToHost, c0->stream));
-    HIP_TRY(hipStreamSynchronize(c0->stream));
-    const int st = batch_singular(b);
+    int st = ng_fetch(b->ng, c0->stream);
+    if (st == LWHIP_OK)
+        st = batch_singular(b);
     if (st != LWHIP_OK)
         return st;
-    const double* ch = b->ngPinned.as<double>();
-    const int32_t* acc = (const int32_t*)(ch + batch_ng_change_doubles(b)) + n;
     for (const int32_t i : b->act) // (rows of inactive columns stay as the caller filled them)
     {
         if (accelerated)
-            accelerated[i] = acc[i];
-        for (int q = 0; q < Na; ++q)
-        {
-            if (dPops)
-                dPops[(size_t)i * Na + q] = ch[((size_t)i * Na + q) * 2];
-            if (dPopsMaxIdx)
-                dPopsMaxIdx[(size_t)i * Na + q] = (int32_t)ch[((size_t)i * Na + q) * 2 + 1];
-        }
+            accelerated[i] = b->ng.accel_host()[i];
+        ng_changes(b->ng, i, dPops ? dPops + (size_t)i * Na : nullptr, dPopsMaxIdx ? dPopsMaxIdx + (size_t)i * Na : nullptr);
     }
     return LWHIP_OK;
 }
@@ -671,35 +586,7 @@ int lwhip_batch_ng_state(lwhip_batch* b, int32_t opts[3], int32_t* counts, int32
 {
     if (!b || b->ctxs.empty())
         return fail(LWHIP_ERR_INVALID, "null batch");
-    const size_t n = b->ctxs.size();
-    if (opts)
-    {
-        opts[0] = b->ngOrder;
-        opts[1] = b->ngPeriod;
-        opts[2] = b->ngDelay;
-    }
-    if (!b->ngOn)
-    {
-        if (counts)
-            std::fill(counts, counts + n, 0);
-        if (lastAccelerated)
-            std::fill(lastAccelerated, lastAccelerated + n, 0);
-        return LWHIP_OK;
-    }
-    if (!counts && !lastAccelerated)
-        return LWHIP_OK;
-    // the device's own words: count [n] and accel [n] lie together behind the change records
-    lwhip_context* c0 = b->ctxs[0];
-    HIP_TRY(hipSetDevice(c0->device));
-    const size_t off = batch_ng_change_doubles(b) * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(b->ngPinned.host + off, (const unsigned char*)b->ngOut.p + off, 2 * n * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, c0->stream));
-    HIP_TRY(hipStreamSynchronize(c0->stream));
-    const int32_t* cnt = (const int32_t*)(b->ngPinned.host + off);
-    if (counts)
-        std::copy(cnt, cnt + n, counts);
-    if (lastAccelerated)
-        std::copy(cnt + n, cnt + 2 * n, lastAccelerated);
-    return LWHIP_OK;
+    HIP_TRY(hipSetDevice(b->ctxs[0]->device));
+    return ng_read_state(b->ng, (int)b->ctxs.size(), b->ctxs[0]->stream, opts, counts, lastAccelerated);
 }
 }

@@ -406,6 +406,43 @@ struct Geom2dDev
 };
 // `g`'s tables into `d`, queued on m's stream: g's arrays must stay until that stream has been waited for
 int geom2d_upload(DevMem& m, const lwhip_grid2d& g, Geom2dDev& d);
+
+// Ng acceleration of the populations of n columns (ng_kernel, lwhip_pops.hip), every column's history and call count on the
+// device: a batch owns one for its n columns, a lone context one for itself -- a batch of one.  Off: all empty.
+struct NgState
+{
+    bool on = false;
+    int order = 0, period = 0, delay = 0; // (delay after the max rule, Ng.hpp:32)
+    int64_t histStride = 0;               // doubles of history per column
+    int n = 0, Natoms = 0;                // columns; solved atoms of each
+    DevBuf<NgCol> columns;                // [n] every column's n pool and status word
+    DevBuf<NgAtom> atoms;                 // [Natoms] the solved atoms, offsets inside one column
+    DevBuf<double> history;               // [n][Natoms][order + 2][Nlevel * Ns]
+    DevBuf<double> out;                   // change [n][Natoms][2], then int32 count [n], accel [n], ticket [n]: one copy
+    PinnedBlock pinned;                   // ... lands here (change, count, accel)
+    // A lone context has the kernel store change and accel into its host-mapped block instead (no copy per step); else null
+    double* mappedChange = nullptr;       // device address of the block's change records, the accel word behind them
+    const double* mappedChangeHost = nullptr;
+    size_t change_doubles() const { return (size_t)n * Natoms * 2; }
+    int32_t* count() const { return (int32_t*)(out.p + change_doubles()); } // (device)
+    // where the host reads what ng_fetch brought (or the kernel stored)
+    const double* change_host() const { return mappedChange ? mappedChangeHost : pinned.as<double>(); }
+    const int32_t* count_host() const { return (const int32_t*)(pinned.as<double>() + change_doubles()); }
+    const int32_t* accel_host() const { return mappedChange ? (const int32_t*)(mappedChangeHost + change_doubles()) : count_host() + n; }
+};
+// cols: the columns (structurally identical; one stream and device: cols[0]'s).  lone -- the one place the two owners differ:
+// cols is one context, whose host-mapped block takes change and accel (see NgState) and for which (0, 0, 0) is order 0 (no
+// extrapolation, changes tracked); for a batch (0, 0, 0) turns Ng off.  No solved atom: off, LWHIP_OK.
+int ng_configure(NgState& s, const std::vector<lwhip_context*>& cols, int Norder, int Nperiod, int Ndelay, bool lone);
+int ng_off(NgState& s, hipStream_t stream);
+NgArgs ng_args(const NgState& s, const int32_t* activeCols);
+// the Ng step of nActive columns (activeCols: their numbers on the device, or null: the first nActive), queued on `stream`
+hipError_t ng_step(const NgState& s, const int32_t* activeCols, int nActive, hipStream_t stream);
+// after a step: waits for `stream` with every column's change and accel at change_host() / accel_host() (mapped: no copy)
+int ng_fetch(NgState& s, hipStream_t stream);
+void ng_changes(const NgState& s, int col, double* dPops, int32_t* dPopsMaxIdx); // ... column col's [Natoms] out of them
+// lwhip_ng_state / lwhip_batch_ng_state: the options in effect and the device's own count and accel words ([n] each; off: zeros)
+int ng_read_state(NgState& s, int n, hipStream_t stream, int32_t opts[3], int32_t* counts, int32_t* lastAccelerated);
 }
 
 struct lwhip_context;
@@ -552,11 +589,7 @@ struct lwhip_context
     std::vector<std::unique_ptr<DevBuf<double>>> gII; // per transition: cached PRD weights (lazily)
     std::vector<char> gIIValid;
     DevBuf<NrAtom> nrAtoms, statEqAtoms;
-    DevBuf<NgAtom> ngAtoms;
-    DevBuf<double> ngHistory;
-    std::vector<NgAtom> ngAtomsHost;
-    int ngOrder = 0, ngPeriod = 0, ngDelay = 0, ngCount = 0;
-    bool ngConfigured = false;
+    NgState ng; // lwhip_ng_configure: this context as a batch of one column
     int statEqKey = -2;
     int32_t* statusHost = nullptr;
     int32_t* statusDev = nullptr;
@@ -662,7 +695,7 @@ struct lwhip_context
         // released while its stream still runs)
         if (stream)
             (void)hipStreamSynchronize(stream);
-        for (PinnedBlock* b : { &stage, &gatherPinned, &prdPinned, &prdPinnedPipe, &fpPinned, &lsDbg })
+        for (PinnedBlock* b : { &stage, &gatherPinned, &prdPinned, &prdPinnedPipe, &fpPinned, &lsDbg, &ng.pinned })
             b->release(); // (before the stream they were used on goes back to its pool)
         stokes_batch_release(stokesFs);
         rays_release(rays);
@@ -781,15 +814,7 @@ struct lwhip_batch
     DevBuf<double> rec;                        // [n][2 + 2 Natoms]: dJMax, idx, then (dPops, idx) per atom
     PinnedBlock recPinned;
     std::vector<int32_t> recCols;              // the columns the last report solved (whose rows of recPinned are its)
-    // lwhip_batch_ng_configure: Ng acceleration of every column, all state on the device (batch_ng_kernel); off: all empty
-    bool ngOn = false;
-    int ngOrder = 0, ngPeriod = 0, ngDelay = 0; // (ngDelay after the max rule, Ng.hpp:32)
-    int64_t ngHistStride = 0;                  // doubles of history per column
-    DevBuf<BatchNgCol> ngCols;                 // [n] every column's n pool and status word
-    DevBuf<NgAtom> ngAtoms;                    // [Natoms] the solved atoms, offsets inside one column
-    DevBuf<double> ngHistory;                  // [n][Natoms][Norder + 2][Nlevel * Ns]
-    DevBuf<double> ngOut;                      // change [n][Natoms][2], then int32 count [n], accel [n], ticket [n]: one copy
-    PinnedBlock ngPinned;                      // ... lands here (change, count, accel)
+    NgState ng;                                // lwhip_batch_ng_configure: Ng acceleration of every column
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments
     DevBuf<PolLineArgs> polList;     // every column's polarised lines, as polHost (lwhip_batch_compute_polarised_profiles)

@@ -773,41 +773,31 @@ struct NgAtom
     int64_t histOff;    // offset of its history [Norder + 2][len]
 };
 enum { LWHIP_NG_MAX_ORDER = 6 };
-struct NgArgs
-{
-    const NgAtom* atoms;
-    double* n;
-    double* history;
-    double* change;         // host-mapped [nAtoms][2]
-    int32_t* status;
-    int32_t Norder, storeSlot, oldSlot, doAccel, haveTwo;
-    int32_t slots[LWHIP_NG_MAX_ORDER + 2]; // slots of count-1, count-2, ... count-Norder-2
-};
-hipError_t launch_ng(const NgArgs& a, int nAtoms, hipStream_t stream);
-// column batches: the Ng step of every active column in one launch, one workgroup per (active column, solved atom).  All
-// per-column state is on the device: the kernel derives the store slot, the accelerate decision and the slot list from
-// count[col] and the three options, so a call uploads nothing per column.
-struct BatchNgCol
+// The Ng step of every active column in one launch, one workgroup per (active column, solved atom); a lone context is one
+// column.  All per-column state is on the device: the kernel derives the store slot, the accelerate decision and the slot list
+// from count[col] and the three options, so a call uploads nothing per column.
+struct NgCol
 {
     double* n;          // the column's n pool (NgAtom::nOff counts from here)
     int32_t* status;    // its status word (LWHIP_ERR_SINGULAR)
 };
-struct BatchNgArgs
+struct NgArgs
 {
-    const BatchNgCol* columns; // [n], by ORIGINAL column number
+    const NgCol* columns;      // [n], by ORIGINAL column number
     const NgAtom* atoms;       // [Natoms]; histOff counts inside one column's history
     const int32_t* cols;       // [nActive] original column numbers, or null: block x is column x
     double* history;           // [n][Natoms][Norder + 2][len]
     int64_t histStride;        // doubles per column
     int32_t* count;            // [n] Ng::count of every column
-    int32_t* accel;            // [n] whether the column's last step extrapolated
+    int32_t* accel;            // [n] whether the column's last step extrapolated (a lone context: a host-mapped word)
     int32_t* ticket;           // [n] workgroups of the column that have finished this launch (0 between launches)
-    double* change;            // [n][Natoms][2]: max_change (value, index) -- batch_conv_kernel's input with nBlocks = 1
+    double* change;            // [n][Natoms][2]: max_change (value, index) -- batch_conv_kernel's input with nBlocks = 1; a lone
+                               // context: the change records of its host-mapped block
     int32_t Natoms, Norder, Nperiod, Ndelay;
 };
-size_t batch_ng_lds_bytes(int Norder);
-hipError_t launch_batch_ng(const BatchNgArgs& a, int nActive, hipStream_t stream);
-hipError_t launch_batch_ng_seed(const BatchNgArgs& a, int n, hipStream_t stream); // slot 0 <- n, count <- 1, for ALL columns
+size_t ng_lds_bytes(int Norder);
+hipError_t launch_ng(const NgArgs& a, int nActive, hipStream_t stream);
+hipError_t launch_ng_seed(const NgArgs& a, int n, hipStream_t stream); // slot 0 <- n, count <- 1, for ALL columns
 hipError_t launch_nr_post(const NrArgs& a, hipStream_t stream);
 hipError_t launch_time_dep(int Nlevel, int Ns, int k0, int k1, double* n, const double* nOld, const double* Gamma, double dt,
                            int* status, hipStream_t stream);

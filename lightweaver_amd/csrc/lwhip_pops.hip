@@ -645,152 +645,38 @@ hipError_t launch_nr_post(const NrArgs& a, hipStream_t stream)
     return hipGetLastError();
 }
 
-// ---- Ng acceleration of one atom's populations: Ng::accelerate + Ng::max_change (Source/Ng.hpp:52-156) ------
-// One workgroup per atom (the vectors are Nlevel x Nspace ~ 500 long).  The weighted dot products that form
-// the Norder x Norder system are accumulated by ONE thread in the reference's order: the system can be
-// ill conditioned, and a few microseconds every Nperiod iterations buy bit-identical coefficients.
-__global__ void __launch_bounds__(256) ng_kernel(const NgArgs a)
-{
-    dbg_poison_lds();
-    extern __shared__ double lds[];
-    const NgAtom at = a.atoms[blockIdx.x];
-    const int L = at.len, No = a.Norder;
-    double* n = a.n + (size_t)at.nOff;
-    double* prev = a.history + (size_t)at.histOff;
-    auto slot = [&](int s) { return prev + (size_t)s * L; };
-    // store the new solution :62-65
-    for (int k = threadIdx.x; k < L; k += blockDim.x)
-        slot(a.storeSlot)[k] = n[k];
-    __syncthreads();
-    if (a.doAccel)
-    {
-        // slots of count-1-i (ip) and count-2-i (ipp), i = 0 .. Norder, precomputed on the host in a.slots
-        double* bco = lds;                       // [No]
-        double* ws = lds + 64;                   // solver workspace of thread 0
-        if (threadIdx.x == 0)
-        {
-            const SolveWs w(ws, No, 1, 0);
-            auto Delta = [&](int i, int k) { return slot(a.slots[i])[k] - slot(a.slots[i + 1])[k]; };
-            for (int j = 0; j < No; ++j)
-            {
-                double bj = 0.0;
-                for (int k = 0; k < L; ++k)
-                    bj += (1.0 / fabs(n[k])) * Delta(0, k) * (Delta(0, k) - Delta(j + 1, k));
-                w.b[j] = bj;
-                for (int i = 0; i < No; ++i)
-                {
-                    double aij = 0.0;
-                    for (int k = 0; k < L; ++k)
-                        aij += (1.0 / fabs(n[k])) * (Delta(j + 1, k) - Delta(0, k)) * (Delta(i + 1, k) - Delta(0, k));
-                    w.A[i * No + j] = aij;
-                }
-            }
-            const bool ok = d_solve_lin_eq(No, w);
-            for (int i = 0; i < No; ++i)
-                bco[i] = ok ? (double)w.b[i] : 0.0;
-            if (!ok)
-                atomicExch(a.status, LWHIP_ERR_SINGULAR);
-        }
-        __syncthreads();
-        // sol += sum_i b_i (previous(count-i-2) - previous(count-1)), then previous(count-1) = sol  :104-113
-        double* p0 = slot(a.slots[0]);
-        for (int k = threadIdx.x; k < L; k += blockDim.x)
-        {
-            double v = n[k];
-            const double p0k = p0[k];
-            for (int i = 0; i < No; ++i)
-                v += bco[i] * (slot(a.slots[i + 1])[k] - p0k);
-            n[k] = v;
-        }
-        __syncthreads();
-        for (int k = threadIdx.x; k < L; k += blockDim.x)
-            p0[k] = n[k];
-        __syncthreads();
-    }
-    // max_change :138-156 between the last two stored solutions
-    double best = 0.0;
-    int bestIdx = 0x7fffffff;
-    if (a.haveTwo)
-    {
-        const double* old = slot(a.oldSlot);
-        const double* cur = slot(a.storeSlot);
-        for (int k = threadIdx.x; k < L; k += blockDim.x)
-        {
-            const double c = cur[k];
-            if (c != 0.0)
-            {
-                const double change = fabs((c - old[k]) / c);
-                if (change > best)
-                {
-                    best = change;
-                    bestIdx = k;
-                }
-            }
-        }
-    }
-    __shared__ double sV[256];
-    __shared__ int sI[256];
-    sV[threadIdx.x] = best;
-    sI[threadIdx.x] = bestIdx;
-    __syncthreads();
-    for (unsigned s2 = blockDim.x / 2; s2 > 0; s2 >>= 1)
-    {
-        if (threadIdx.x < s2)
-        {
-            const double v = sV[threadIdx.x + s2];
-            const int i = sI[threadIdx.x + s2];
-            if (v > sV[threadIdx.x] || (v == sV[threadIdx.x] && i < sI[threadIdx.x]))
-            {
-                sV[threadIdx.x] = v;
-                sI[threadIdx.x] = i;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-    {
-        a.change[2 * blockIdx.x] = sV[0];
-        a.change[2 * blockIdx.x + 1] = sV[0] > 0.0 ? (double)sI[0] : 0.0;
-    }
-}
-
-hipError_t launch_ng(const NgArgs& a, int nAtoms, hipStream_t stream)
-{
-    const size_t lds = (64 + solve_ws_doubles(a.Norder > 0 ? a.Norder : 1)) * sizeof(double);
-    LWHIP_LAUNCH(ng_kernel, dim3(nAtoms), dim3(256), lds, stream, a);
-    return hipGetLastError();
-}
-
-// ---- column batches: Ng::accelerate + Ng::max_change of every active column in ONE launch -----------------------------------
+// ---- Ng acceleration of the populations: Ng::accelerate + Ng::max_change (Source/Ng.hpp:52-156) of every active column in ONE
+// launch.  A lone context is a batch of one column (lwhip_ng_configure); lwhip_batch_ng_configure brings n. ------------------
 // One workgroup per (active column, solved atom); the column is picked through the compacted list as in batch_conv_kernel.
-// What ng_kernel is handed by the host per call -- store slot, accelerate decision, slot list -- is derived here from the
-// column's own count[col] and the three options, so columns on different schedules (one was inactive for some calls) share the
-// launch and nothing per column is uploaded.
-// The No + No^2 weighted sums keep the reference's order without being one thread's work: lane e < No + No^2 owns b(j) or
-// A(i, j) and adds its terms for k = 0 .. L-1 in sequence; the workgroup stages weight(k) = 1 / |n[k]| and the No + 1 rows
-// Delta(i, k) for BNG_CHUNK values of k at a time through LDS (coalesced loads by all lanes; each Delta formed once -- one
-// subtraction, the same bits as ng_kernel's repeated ones).  The term expressions and the `+=` are ng_kernel's, contraction is
-// off in this file, and so the coefficients -- and everything after them -- have ng_kernel's bits.  Rows are BNG_CHUNK + 1
+// All per-column state is on the device: the store slot, the accelerate decision and the slots of the earlier solutions are
+// derived from the column's own count[col] and the three options, so columns on different schedules (one was inactive for some
+// calls) share the launch and a call uploads nothing.
+// The system of Norder x Norder weighted dot products can be ill conditioned, so every one of its No + No^2 sums is formed in
+// the reference's order -- yet not all by a single lane: lane e < No + No^2 owns b(j) or A(i, j) and adds its terms for
+// k = 0 .. L-1 in sequence; the workgroup stages weight(k) = 1 / |n[k]| and the No + 1 rows Delta(i, k) for NG_CHUNK values of k
+// at a time through LDS (coalesced loads by all lanes; each Delta is one subtraction, formed once).  Contraction is off in this
+// file: a term is two roundings of the products and the `+=` one more, as the reference's loop has them.  Rows are NG_CHUNK + 1
 // doubles apart: the lanes of a sum read different rows at the same k, which would otherwise all sit in one bank pair.
 // count[col] is read by every workgroup of the column and written once, by the workgroup that finishes last (a ticket per
-// column): no workgroup can see the new count in the launch that made it.
-enum { BNG_CHUNK = 64, BNG_ROW = BNG_CHUNK + 1, BNG_THREADS = 256 };
-size_t batch_ng_lds_bytes(int Norder)
+// column): no workgroup can see the new count in the launch that made it.  With one solved atom the first workgroup is the last.
+// tests/golden/ng_step_bits.json holds what a step leaves in n and reports, bit for bit.
+enum { NG_CHUNK = 64, NG_ROW = NG_CHUNK + 1, NG_THREADS = 256 };
+size_t ng_lds_bytes(int Norder)
 {
     const int No = Norder > 0 ? Norder : 1;
-    return (8 + (size_t)(No + 2) * BNG_ROW + solve_ws_doubles(No)) * sizeof(double);
+    return (8 + (size_t)(No + 2) * NG_ROW + solve_ws_doubles(No)) * sizeof(double);
 }
 
-__global__ void __launch_bounds__(BNG_THREADS) batch_ng_kernel(const BatchNgArgs a)
+__global__ void __launch_bounds__(NG_THREADS) ng_kernel(const NgArgs a)
 {
     dbg_poison_lds();
     extern __shared__ double lds[];
     __shared__ int sSlot[LWHIP_NG_MAX_ORDER + 2];
-    __shared__ double sV[BNG_THREADS / 64];
-    __shared__ int sI[BNG_THREADS / 64];
+    __shared__ double sV[NG_THREADS / 64];
+    __shared__ int sI[NG_THREADS / 64];
     const int col = a.cols ? a.cols[blockIdx.x] : (int)blockIdx.x;
     const NgAtom at = a.atoms[blockIdx.y];
-    const BatchNgCol cc = a.columns[col];
+    const NgCol cc = a.columns[col];
     const int L = at.len, No = a.Norder, nslots = No + 2;
     double* n = cc.n + (size_t)at.nOff;
     double* prev = a.history + (size_t)col * a.histStride + (size_t)at.histOff;
@@ -802,32 +688,32 @@ __global__ void __launch_bounds__(BNG_THREADS) batch_ng_kernel(const BatchNgArgs
     const bool doAccel = No > 0 && count >= a.Ndelay && ((count - a.Ndelay) % a.Nperiod) == 0;
     if (threadIdx.x < nslots) // slots of count-1, count-2, ... count-Norder-2
         sSlot[threadIdx.x] = ((count - 1 - (int)threadIdx.x) % nslots + nslots) % nslots;
-    for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+    for (int k = threadIdx.x; k < L; k += NG_THREADS)
         slot(storeSlot)[k] = n[k];
     __syncthreads();
     if (doAccel)
     {
         double* bco = lds;               // [No]
-        double* rows = lds + 8;          // [No + 2][BNG_ROW]: weight, Delta(0) .. Delta(No)
-        const SolveWs w(rows + (size_t)(No + 2) * BNG_ROW, No, 1, 0); // the solving lane's workspace
+        double* rows = lds + 8;          // [No + 2][NG_ROW]: weight, Delta(0) .. Delta(No)
+        const SolveWs w(rows + (size_t)(No + 2) * NG_ROW, No, 1, 0); // the solving lane's workspace
         const int e = threadIdx.x, nSums = No + No * No;
         // lane e: b(j) for e < No, else A(i, j) -- rows of Delta(j + 1) and Delta(i + 1)
         const int j = e < No ? e : (e - No) / No, i = e < No ? 0 : (e - No) % No;
         const double* rW = rows;
-        const double* rD0 = rows + BNG_ROW;
-        const double* rDj = rows + (size_t)(j + 2) * BNG_ROW;
-        const double* rDi = rows + (size_t)(i + 2) * BNG_ROW;
+        const double* rD0 = rows + NG_ROW;
+        const double* rDj = rows + (size_t)(j + 2) * NG_ROW;
+        const double* rDi = rows + (size_t)(i + 2) * NG_ROW;
         double acc = 0.0;
-        for (int k0 = 0; k0 < L; k0 += BNG_CHUNK)
+        for (int k0 = 0; k0 < L; k0 += NG_CHUNK)
         {
-            const int m = min((int)BNG_CHUNK, L - k0);
-            for (int q = threadIdx.x; q < nslots * BNG_CHUNK; q += BNG_THREADS)
+            const int m = min((int)NG_CHUNK, L - k0);
+            for (int q = threadIdx.x; q < nslots * NG_CHUNK; q += NG_THREADS)
             {
-                const int r = q / BNG_CHUNK, kk = q % BNG_CHUNK;
+                const int r = q / NG_CHUNK, kk = q % NG_CHUNK;
                 if (kk < m)
                 {
                     const int k = k0 + kk;
-                    rows[r * BNG_ROW + kk] = r == 0 ? 1.0 / fabs(n[k]) : slot(sSlot[r - 1])[k] - slot(sSlot[r])[k];
+                    rows[r * NG_ROW + kk] = r == 0 ? 1.0 / fabs(n[k]) : slot(sSlot[r - 1])[k] - slot(sSlot[r])[k];
                 }
             }
             __syncthreads();
@@ -855,7 +741,7 @@ __global__ void __launch_bounds__(BNG_THREADS) batch_ng_kernel(const BatchNgArgs
         __syncthreads();
         // sol += sum_i b_i (previous(count-i-2) - previous(count-1)), then previous(count-1) = sol  :104-113
         double* p0 = slot(sSlot[0]);
-        for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+        for (int k = threadIdx.x; k < L; k += NG_THREADS)
         {
             double v = n[k];
             const double p0k = p0[k];
@@ -864,7 +750,7 @@ __global__ void __launch_bounds__(BNG_THREADS) batch_ng_kernel(const BatchNgArgs
             n[k] = v;
         }
         __syncthreads();
-        for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+        for (int k = threadIdx.x; k < L; k += NG_THREADS)
             p0[k] = n[k];
         __syncthreads();
     }
@@ -874,7 +760,7 @@ __global__ void __launch_bounds__(BNG_THREADS) batch_ng_kernel(const BatchNgArgs
     {
         const double* old = slot(sSlot[1]);
         const double* cur = slot(storeSlot);
-        for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+        for (int k = threadIdx.x; k < L; k += NG_THREADS)
         {
             const double c = cur[k];
             if (c != 0.0)
@@ -907,7 +793,7 @@ __global__ void __launch_bounds__(BNG_THREADS) batch_ng_kernel(const BatchNgArgs
     __syncthreads(); // (also: every lane's read of count[col] lies before the ticket below)
     if (threadIdx.x == 0)
     {
-        for (int q = 1; q < BNG_THREADS / 64; ++q)
+        for (int q = 1; q < NG_THREADS / 64; ++q)
             if (sV[q] > best || (sV[q] == best && sI[q] < bestIdx))
             {
                 best = sV[q];
@@ -927,18 +813,18 @@ __global__ void __launch_bounds__(BNG_THREADS) batch_ng_kernel(const BatchNgArgs
     }
 }
 
-// lwhip_batch_ng_configure: every column's current populations into slot 0, the other slots cleared, count = 1 -- one launch,
+// ng_configure: every column's current populations into slot 0, the other slots cleared, count = 1 -- one launch,
 // one workgroup per (column, solved atom), ALL columns
-__global__ void __launch_bounds__(BNG_THREADS) batch_ng_seed_kernel(const BatchNgArgs a)
+__global__ void __launch_bounds__(NG_THREADS) ng_seed_kernel(const NgArgs a)
 {
     const int col = blockIdx.x;
     const NgAtom at = a.atoms[blockIdx.y];
     const double* n = a.columns[col].n + (size_t)at.nOff;
     double* prev = a.history + (size_t)col * a.histStride + (size_t)at.histOff;
     const int L = at.len;
-    for (int k = threadIdx.x; k < L; k += BNG_THREADS)
+    for (int k = threadIdx.x; k < L; k += NG_THREADS)
         prev[k] = n[k];
-    for (size_t k = (size_t)L + threadIdx.x; k < (size_t)(a.Norder + 2) * L; k += BNG_THREADS)
+    for (size_t k = (size_t)L + threadIdx.x; k < (size_t)(a.Norder + 2) * L; k += NG_THREADS)
         prev[k] = 0.0;
     if (blockIdx.y == 0 && threadIdx.x == 0)
     {
@@ -948,19 +834,19 @@ __global__ void __launch_bounds__(BNG_THREADS) batch_ng_seed_kernel(const BatchN
     }
 }
 
-hipError_t launch_batch_ng(const BatchNgArgs& a, int nActive, hipStream_t stream)
+hipError_t launch_ng(const NgArgs& a, int nActive, hipStream_t stream)
 {
     if (nActive < 1 || a.Natoms < 1 || a.Norder < 0 || a.Norder > LWHIP_NG_MAX_ORDER || (a.Norder > 0 && a.Nperiod < 1))
         return hipErrorInvalidValue;
-    LWHIP_LAUNCH(batch_ng_kernel, dim3(nActive, a.Natoms), dim3(BNG_THREADS), batch_ng_lds_bytes(a.Norder), stream, a);
+    LWHIP_LAUNCH(ng_kernel, dim3(nActive, a.Natoms), dim3(NG_THREADS), ng_lds_bytes(a.Norder), stream, a);
     return hipGetLastError();
 }
 
-hipError_t launch_batch_ng_seed(const BatchNgArgs& a, int n, hipStream_t stream)
+hipError_t launch_ng_seed(const NgArgs& a, int n, hipStream_t stream)
 {
     if (n < 1 || a.Natoms < 1)
         return hipErrorInvalidValue;
-    LWHIP_LAUNCH(batch_ng_seed_kernel, dim3(n, a.Natoms), dim3(BNG_THREADS), 0, stream, a);
+    LWHIP_LAUNCH(ng_seed_kernel, dim3(n, a.Natoms), dim3(NG_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 }

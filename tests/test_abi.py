@@ -66,6 +66,12 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert hip_lib.lwhip_abi_version() == abi.ABI_VERSION
 
 
+def test_ng_state_refuses_a_null_context(hip_lib):
+    opts = (C.c_int32 * 3)()
+    assert hip_lib.lwhip_ng_state(None, opts, None, None) == abi.ERR_INVALID
+    assert b'null context' in hip_lib.lwhip_last_error()
+
+
 def test_no_cpu_fallback_without_gpu(hip_lib):
     """Without a device the product path must fail loudly, never compute on the CPU."""
     if hip_lib.lwhip_device_count() > 0:

@@ -1,41 +1,35 @@
-"""Ng acceleration for column batches (lwhip_batch_ng_configure / _accelerate / _state, batch_ng_kernel;
-ColumnBatch.configure_ng, ng_accelerate, ng_state, iterate_to_convergence(ng=...)): every column of a batch behaves as a lone
-Context with configure_ng does.
+"""Ng acceleration for column batches (lwhip_batch_ng_configure / _accelerate / _state; ColumnBatch.configure_ng, ng_accelerate,
+ng_state, iterate_to_convergence(ng=...)): every column of a batch behaves as a lone Context with configure_ng does -- both run
+ng_kernel, a lone context as a batch of one column.
 
 Columns: the batch tests' perturbed FAL-C columns with dT = 0.1 (with the dT = 0.3 of test_batch_converge.py the oracle's own Ng
 loop ends in "Singular Matrix" for three seeds), H(6) + Ca II(6), 3 rays, NgOptions(2, 3, 5).  On the CPU oracle these stop at
 iterations 26, 26, 23, 32, 29 (plain MALI: 40, 38, 29, 37, 34) and accelerate at 6, 9, 12, ...; a relative 1e-9 perturbation of
 the starting populations moves no stop and the final dJMax / dPops by at most 5.5e-7 / 7.5e-7 relative, so the device's
 1e-10-level differences stay well inside the project's bounds for this comparison (dJMax rel 1e-6, dPops rtol 1e-5, states
-TOL_CONVERGED).  The Ng step itself is compared bit for bit with the lone context's ng_kernel: same operations, same order,
-contraction off."""
+TOL_CONVERGED).  The Ng step itself is held, for the lone context and for the batch, to the bits recorded from lone contexts
+before the two routes shared a kernel (tests/golden/ng_step_bits.json, tools/record_ng_bits.py); the comparison of batch and lone
+context bit for bit now guards the column addressing, the history stride and the compacted list."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+import ng_cases
 from helpers import TOL_CONVERGED, rel_err
 from lightweaver_amd import _abi as abi
 from lightweaver_amd.batch import ColumnBatch
 from lightweaver_amd.context import ExplodingMatrixError
-from lightweaver_amd.harness import models
 from lightweaver_amd.iterate import iterate_ctx_se
 from oracle import bindings
 from test_batch_converge import OracleBatch, same_bits, snapshot
+from ng_cases import SEEDS, Synthetic, column, get, lone_ng, put
 from test_iterate import OracleLoopContext
 
-SEEDS = [100, 101, 102, 103, 107]
 NG = (2, 3, 5)
 JTOL, PTOL, NSCATTER, NMAX = 5e-2, 3e-2, 3, 60
 KW = dict(Nscatter=NSCATTER, NmaxIter=NMAX, JTol=JTOL, popsTol=PTOL)
-
-
-def column(seed, Nspace=None):
-    atmos = models.perturbed(models.falc82(), seed, dT=0.1, dv=2.0e3)
-    if Nspace is not None:
-        atmos = models.resample(atmos, Nspace)
-    return models.build_problem(atmos, [models.H_6(0.3), models.CaII_6(0.3)], Nrays=3)
 
 
 @functools.lru_cache(maxsize=None)
@@ -77,8 +71,20 @@ def plain_converged_by(seed, last):
 
 
 class NgOracleContext(OracleLoopContext):
+    """... with Context.configure_ng / ng_state: the oracle's Ng keeps its count to itself, so the calls are counted here."""
+
     def configure_ng(self, Norder=0, Nperiod=0, Ndelay=0):
         self.ng = [bindings.NgHandle('oracle', Norder, Nperiod, Ndelay, sol=a.n) for a in self.prob.atoms if not a.detailed]
+        self._state = dict(options=(Norder, Nperiod, max(Ndelay, Nperiod + 2)), count=1, lastAccelerated=False)
+
+    def stat_equil(self, deviceResident=False):
+        up = super().stat_equil(deviceResident)
+        self._state['count'] += 1
+        self._state['lastAccelerated'] = bool(up.ngAccelerated)
+        return up
+
+    def ng_state(self):
+        return dict(self._state)
 
 
 class NgOracleBatch(OracleBatch):
@@ -132,68 +138,30 @@ def test_iterate_to_convergence_with_ng_on_oracle_columns():
 
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------------
-POPS_SCALE = (1.0e16, 1.0e10)
-
-
-class Synthetic:
-    """One slowly converging sequence of positive vectors per (column, atom): the linear map of
-    test_oracle_ng_matches_the_reference_struct, its own rng per column, scaled to population size."""
-
-    def __init__(self, probs, seed0=7):
-        self.target, self.x0 = [], []
-        for i, p in enumerate(probs):
-            rng = np.random.default_rng(seed0 + i)
-            t = [1.0 + rng.random(a.n.shape) for a in p.atoms]
-            self.target.append(t)
-            self.x0.append([sc * (tt + 0.4 * rng.uniform(-1.0, 1.0, tt.shape)) for tt, sc in zip(t, POPS_SCALE)])
-
-    def advance(self, i, xs):
-        """The iteration being accelerated, applied to column i's current vectors."""
-        out = []
-        for x, t, sc in zip(xs, self.target[i], POPS_SCALE):
-            d = (x / sc - t).ravel()
-            out.append(sc * (t + (0.9 * d + 0.05 * np.roll(d, 1)).reshape(t.shape)))
-        return out
-
-
-def put(ctx, prob, xs):
-    for a, x in zip(prob.atoms, xs):
-        a.n[...] = x
-    ctx.upload(abi.POPS)
-
-
-def get(ctx, prob):
-    ctx.download(abi.POPS)
-    return [a.n.copy() for a in prob.atoms]
-
-
-def lone_ng(ctx, nAtoms):
-    """lwhip_ng_accelerate of a lone context: (status, accelerated, dPops, indices)."""
-    acc = np.zeros(nAtoms, dtype=np.int32)
-    dP, dI = np.zeros(nAtoms), np.zeros(nAtoms, dtype=np.int32)
-    st = ctx.lib.lwhip_ng_accelerate(ctx._h, acc.ctypes.data_as(abi.i32p), dP.ctypes.data_as(abi.f64p), dI.ctypes.data_as(abi.i32p))
-    return st, bool(acc.any()), dP.tolist(), dI.tolist()
-
-
 class Twins:
     """A fused batch of 3 columns and one lone Context per column, fed the same vectors."""
 
-    def __init__(self, Nspace):
+    def __init__(self, Nspace, problem='HCa', fused=True):
         from lightweaver_amd.context import Context
         seeds = SEEDS[:3]
-        self.probs = [column(s, Nspace) for s in seeds]
-        self.lprobs = [column(s, Nspace) for s in seeds]
-        self.batch = ColumnBatch(self.probs)
-        assert self.batch._batch is not None
+        self.probs = [column(s, Nspace, problem) for s in seeds]
+        self.lprobs = [column(s, Nspace, problem) for s in seeds]
+        self.batch = ColumnBatch(self.probs, fused=fused)
+        assert (self.batch._batch is not None) == fused
         self.lones = [Context(p) for p in self.lprobs]
         self.nAtoms = len(self.probs[0].atoms)
+        self.gold, self.stepNo = None, 0
 
     def close(self):
         for c in self.lones:
             c.close()
         self.batch.close()
 
-    def seed(self, syn, opts):
+    def seed(self, syn, opts, gold=None):
+        """gold: the recorded sequence (ng_cases.golden) that the steps from here on are held to, step 1 first."""
+        self.gold, self.stepNo = gold, 0
+        if gold is not None:
+            ng_cases.check_inputs(gold, syn)
         for i in range(3):
             put(self.batch.contexts[i], self.probs[i], syn.x0[i])
             put(self.lones[i], self.lprobs[i], syn.x0[i])
@@ -202,8 +170,9 @@ class Twins:
         return [[x.copy() for x in syn.x0[i]] for i in range(3)]
 
     def step(self, syn, xs, cols=(0, 1, 2), oracle=None, worst=None):
-        """Advance the sequences of `cols`, upload, one Ng step on batch and lone contexts; everything equal bit for bit.
-        Returns the new vectors (the batch's n)."""
+        """Advance the sequences of `cols`, upload, one Ng step on batch and lone contexts; everything equal bit for bit, and
+        (seeded with a recorded sequence) both equal to the recorded bits of this step.  Returns the new vectors (the batch's n)."""
+        self.stepNo += 1
         for i in cols:
             xs[i] = syn.advance(i, xs[i])
             put(self.batch.contexts[i], self.probs[i], xs[i])
@@ -216,6 +185,9 @@ class Twins:
             nb, nl = get(self.batch.contexts[i], self.probs[i]), get(self.lones[i], self.lprobs[i])
             assert all(np.array_equal(a, b) for a, b in zip(nb, nl)), i
             assert ups[i].ngAccelerated == acc and ups[i].dPops == dP and ups[i].dPopsMaxIdx == dI, (i, ups[i], acc, dP, dI)
+            if self.gold is not None:
+                ng_cases.check_step(self.gold, i, self.stepNo, 'lone', nl, acc, dP, dI)
+                ng_cases.check_step(self.gold, i, self.stepNo, 'batch', nb, ups[i].ngAccelerated, ups[i].dPops, ups[i].dPopsMaxIdx)
             if oracle is not None:
                 for q, g in enumerate(oracle[i]):
                     xo = np.ascontiguousarray(xs[i][q]).copy()
@@ -235,14 +207,17 @@ def test_ng_step_matches_the_lone_context_bit_for_bit(gpu, Nspace):
     (6, 4, 2) extrapolates first at count 6 = Ndelay, below Norder + 2 = 8: Ng::accelerate then asks storage_index for counts
     -1 and -2, which in the reference (Ng.hpp:47-50, `cnt % (Norder + 2)` of a negative int) and in the oracle's restatement
     index BEFORE the history -- an out-of-bounds read (the oracle answered "singular" from it when this was tried; nothing
-    defines that).  The device wraps such a count onto slots that still hold the zeros of configure, in ng_kernel and in
-    batch_ng_kernel alike, so the bit-for-bit comparison with the lone context stands for that set; the oracle is compared
-    wherever it is defined (Ndelay >= Norder + 2), and (6, 4, 8) is added so that a 42-sum system meets it too."""
+    defines that).  The device wraps such a count onto slots that still hold the zeros of configure, so the comparison with
+    the recorded bits and with the lone context stands for that set; the oracle is compared wherever it is defined
+    (Ndelay >= Norder + 2), and (6, 4, 8) is added so that a 42-sum system meets it too.
+    Lone context and batch column run the same ng_kernel: their equality guards the column addressing, the history stride and
+    the compacted list, and the arithmetic is held -- both of them -- to tests/golden/ng_step_bits.json, recorded from lone
+    contexts when they still had a kernel of their own (one thread forming every sum)."""
     tw = Twins(Nspace)
     try:
-        for opts in ((1, 1, 0), (2, 3, 5), (6, 4, 2), (6, 4, 8)):
-            syn = Synthetic(tw.probs, seed0=7 + opts[0])
-            xs = tw.seed(syn, opts)
+        for opts in ng_cases.OPTIONS:
+            syn = ng_cases.sequence_inputs(tw.probs, opts)
+            xs = tw.seed(syn, opts, gold=ng_cases.golden('HCa', Nspace, opts))
             eff = (opts[0], opts[1], max(opts[2], opts[1] + 2))
             assert tw.batch.ng_state()['options'] == eff
             oracle = None
@@ -289,6 +264,107 @@ def test_each_column_keeps_its_own_ng_schedule(gpu):
         assert [s[1] for s in seen] == [True, False, False, True, False, False]
     finally:
         tw.close()
+
+
+@pytest.mark.gpu
+def test_one_solved_atom_matches_the_recorded_bits(gpu):
+    """H alone: each column has ONE workgroup, the first to take the column's ticket and the last -- it must still write the
+    count back (and only after its own read).  Lone contexts and a fused batch of 3 against the recorded steps."""
+    opts = (2, 3, 5)
+    tw = Twins(13, problem='H')
+    try:
+        assert tw.nAtoms == 1
+        syn = ng_cases.sequence_inputs(tw.probs, opts)
+        xs = tw.seed(syn, opts, gold=ng_cases.golden('H', 13, opts))
+        for stepNo in range(1, ng_cases.NSTEPS + 1):
+            xs = tw.step(syn, xs)
+            assert tw.batch.ng_state()['counts'] == [stepNo + 1] * 3
+            assert [c.ng_state()['count'] for c in tw.lones] == [stepNo + 1] * 3
+    finally:
+        tw.close()
+
+
+@pytest.mark.gpu
+def test_a_repeated_configure_seeds_again(gpu):
+    """(2, 3, 5), three steps, then (1, 1, 0) on the SAME context -- a smaller history, allocated anew -- fed the (1, 1, 0)
+    sequence from its x0: the recorded (1, 1, 0) steps, one by one.  Nothing of the first configuration's history or count
+    may survive."""
+    from lightweaver_amd.context import Context
+    prob = column(SEEDS[0], 13)
+    with Context(prob) as ctx:
+        first = ng_cases.sequence_inputs([prob], (2, 3, 5))
+        put(ctx, prob, first.x0[0])
+        ctx.configure_ng(2, 3, 5)
+        xs = first.x0[0]
+        for _ in range(3):
+            xs = first.advance(0, xs)
+            put(ctx, prob, xs)
+            assert lone_ng(ctx, 2)[0] == abi.OK
+            xs = get(ctx, prob)
+        assert ctx.ng_state() == dict(options=(2, 3, 5), count=4, lastAccelerated=False)
+        opts = (1, 1, 0)
+        syn, gold = ng_cases.sequence_inputs([prob], opts), ng_cases.golden('HCa', 13, opts)
+        ng_cases.check_inputs(gold[:1], syn)
+        put(ctx, prob, syn.x0[0])
+        ctx.configure_ng(*opts)
+        assert ctx.ng_state() == dict(options=(1, 1, 3), count=1, lastAccelerated=False)
+        xs = syn.x0[0]
+        for stepNo in range(1, ng_cases.NSTEPS + 1):
+            put(ctx, prob, syn.advance(0, xs))
+            st, acc, dP, dI = lone_ng(ctx, 2)
+            assert st == abi.OK
+            xs = get(ctx, prob)
+            ng_cases.check_step(gold, 0, stepNo, 'reconfigured lone', xs, acc, dP, dI)
+
+
+@pytest.mark.gpu
+def test_ng_state_is_the_devices_word_for_lone_contexts_and_unfused_batches(gpu):
+    from lightweaver_amd.context import Context
+    prob = column(SEEDS[0], 13)
+    syn = Synthetic([prob])
+    with Context(prob) as ctx:
+        assert ctx.ng_state() == dict(options=None, count=0, lastAccelerated=False)
+        put(ctx, prob, syn.x0[0])
+        ctx.configure_ng(*NG)
+        assert ctx.ng_state() == dict(options=NG, count=1, lastAccelerated=False)
+        xs = syn.x0[0]
+        for k in range(1, 9):
+            put(ctx, prob, syn.advance(0, xs))
+            st, acc, _, _ = lone_ng(ctx, 2)
+            assert st == abi.OK
+            xs = get(ctx, prob)
+            # (2, 3, 5): counts 5, 8, ... extrapolate
+            assert ctx.ng_state() == dict(options=NG, count=k + 1, lastAccelerated=(k + 1) in (5, 8)) and acc == ((k + 1) in (5, 8))
+        ctx.configure_ng(0, 0, 0)      # a lone context: order 0, the changes still tracked
+        assert ctx.ng_state() == dict(options=(0, 0, 2), count=1, lastAccelerated=False)
+    # the scenario of test_each_column_keeps_its_own_ng_schedule on a fused and on an unfused batch: the same state throughout
+    probs = [[column(s, 32) for s in SEEDS[:3]] for _ in range(2)]
+    syn = Synthetic(probs[0])
+    with ColumnBatch(probs[0]) as fused, ColumnBatch(probs[1], fused=False) as unfused:
+        assert fused._batch is not None and unfused._batch is None
+        assert unfused.ng_state() == fused.ng_state() == dict(options=None, counts=[0] * 3, lastAccelerated=[False] * 3)
+        xs = [[x.copy() for x in syn.x0[i]] for i in range(3)]
+        for b, pp in zip((fused, unfused), probs):
+            for i in range(3):
+                put(b.contexts[i], pp[i], xs[i])
+            b.configure_ng(*NG)
+        assert unfused.ng_state() == fused.ng_state() == dict(options=NG, counts=[1] * 3, lastAccelerated=[False] * 3)
+        for stepNo in range(1, 13):
+            cols = (0, 2) if 4 <= stepNo <= 6 else (0, 1, 2)
+            for b in (fused, unfused):
+                b.set_active(list(cols) if len(cols) < 3 else None)
+            for i in cols:
+                xs[i] = syn.advance(i, xs[i])
+            for b, pp in zip((fused, unfused), probs):
+                for i in cols:
+                    put(b.contexts[i], pp[i], xs[i])
+            uf, uu = fused.ng_accelerate(), unfused.ng_accelerate()
+            assert uf == uu
+            for i in cols:
+                xs[i] = get(fused.contexts[i], probs[0][i])
+                assert all(np.array_equal(a, b) for a, b in zip(xs[i], get(unfused.contexts[i], probs[1][i])))
+            assert unfused.ng_state() == fused.ng_state(), stepNo
+        assert unfused.ng_state()['counts'] == [13, 10, 13]
 
 
 @pytest.mark.gpu
