@@ -1307,19 +1307,8 @@ int lwhip_check_status(lwhip_context* c)
 
 namespace lwhip
 {
-int stat_equil_impl(lwhip_context* c, int atom, bool wait, double* dPops, int32_t* dPopsMaxIdx)
+int solved_atoms(const lwhip_context* c, int atom, std::vector<NrAtom>& atoms)
 {
-    if (!c)
-        return fail(LWHIP_ERR_INVALID, "null context");
-    HIP_TRY(hipSetDevice(c->device));
-    {
-        int stp = flush_prefill(c);
-        if (stp != LWHIP_OK)
-            return stp;
-    }
-    // one launch for all requested atoms; the status word lives in host-mapped pinned memory, so the
-    // call needs no memset kernel and no read-back copy, only the stream synchronisation
-    std::vector<NrAtom> atoms;
     int maxNl = 0;
     for (int ia = 0; ia < c->Natom; ++ia)
     {
@@ -1336,6 +1325,38 @@ int stat_equil_impl(lwhip_context* c, int atom, bool wait, double* dPops, int32_
         atoms.push_back(at);
         maxNl = std::max(maxNl, a.Nlevel);
     }
+    return maxNl;
+}
+
+StatEqArgs stat_eq_args(const lwhip_context* c, int Natoms)
+{
+    StatEqArgs sa{};
+    sa.Ns = c->Ns;
+    sa.k0 = c->kLo;
+    sa.k1 = c->kHi < 0 ? c->Ns : c->kHi;
+    sa.Natoms = Natoms;
+    sa.atoms = c->statEqAtoms.p; // (as uploaded by the caller)
+    sa.n = c->n.p;
+    sa.nTotal = c->nTotal.p;
+    sa.Gamma = c->Gamma.p;
+    sa.status = c->statusDev;
+    return sa;
+}
+
+int stat_equil_impl(lwhip_context* c, int atom, bool wait, double* dPops, int32_t* dPopsMaxIdx)
+{
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, "null context");
+    HIP_TRY(hipSetDevice(c->device));
+    {
+        int stp = flush_prefill(c);
+        if (stp != LWHIP_OK)
+            return stp;
+    }
+    // one launch for all requested atoms; the status word lives in host-mapped pinned memory, so the
+    // call needs no memset kernel and no read-back copy, only the stream synchronisation
+    std::vector<NrAtom> atoms;
+    const int maxNl = solved_atoms(c, atom, atoms);
     if (atoms.empty())
         return LWHIP_OK;
     if (c->statEqKey != atom || c->statEqAtoms.n < atoms.size())
@@ -1345,16 +1366,7 @@ int stat_equil_impl(lwhip_context* c, int atom, bool wait, double* dPops, int32_
     }
     if (wait)
         *c->statusHost = 0; // (the async form accumulates until lwhip_check_status)
-    StatEqArgs sa{};
-    sa.Ns = c->Ns;
-    sa.k0 = c->kLo;
-    sa.k1 = c->kHi < 0 ? c->Ns : c->kHi;
-    sa.Natoms = (int32_t)atoms.size();
-    sa.atoms = c->statEqAtoms.p;
-    sa.n = c->n.p;
-    sa.nTotal = c->nTotal.p;
-    sa.Gamma = c->Gamma.p;
-    sa.status = c->statusDev;
+    StatEqArgs sa = stat_eq_args(c, (int)atoms.size());
     const int nBlocks = stat_eq_blocks(c->Ns, maxNl);
     const bool report = wait && dPops;
     if (report)
@@ -1843,10 +1855,7 @@ static int compute_profiles_impl(lwhip_context* c)
         HIP_TRY(hipMemcpyAsync(c->voigtList.p, list.data(), list.size() * sizeof(VoigtLineArgs), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(launch_voigt_lines(c->voigtList.p, list.data(), (int)list.size(), c->stream));
     }
-    c->deviceProfiles = true;
-    c->profilesStale = false;
-    c->phiSym = c->vlosZero; // (the Voigt arguments of the two directions differ by the sign of the line-of-sight velocity alone)
-    c->phiIso = c->vlosZero; // (... and those of two angles by the velocity's projection alone)
+    profiles_made_on_device(c);
     return retile_profiles(c);
 }
 

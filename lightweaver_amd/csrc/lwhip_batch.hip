@@ -21,30 +21,12 @@ static int batch_compute_profiles(lwhip_batch* b, bool all)
     }
     if (todo.empty())
         return LWHIP_OK;
-    lwhip_context* c0 = b->ctxs[0];
-    if (!list.empty())
-    {
-        if (b->voigtList.n < list.size())
-        {
-            HIP_TRY(hipStreamSynchronize(c0->stream)); // nothing may still read the buffer about to be replaced
-            HIP_TRY(b->voigtList.alloc(c0->mem, list.size()));
-        }
-        HIP_TRY(hipMemcpyAsync(b->voigtList.p, list.data(), list.size() * sizeof(VoigtLineArgs), hipMemcpyHostToDevice, c0->stream));
-        // the launch geometry allows 65 535 entries per grid dimension
-        for (size_t off = 0; off < list.size(); off += 32768)
-        {
-            const int cnt = (int)std::min<size_t>(32768, list.size() - off);
-            HIP_TRY(launch_voigt_lines(b->voigtList.p + off, list.data() + off, cnt, c0->stream));
-        }
-    }
+    const int st = launch_list(b->ctxs[0], b->voigtList, list, true, launch_voigt_lines);
+    if (st != LWHIP_OK)
+        return st;
     // ... and their tile-blocked copies, one grid slice per column
     for (lwhip_context* c : todo)
-    {
-        c->deviceProfiles = true;
-        c->profilesStale = false;
-        c->phiSym = c->vlosZero;
-        c->phiIso = c->vlosZero;
-    }
+        profiles_made_on_device(c);
     return batch_retile(b, todo);
 }
 
@@ -58,38 +40,31 @@ static bool batch_plain_ok(const lwhip_batch* b, const TileDyn& dyn)
     return true;
 }
 
-// the compacted argument lists of a proper subset of the columns (lwhip_batch_set_active): position p is column act[p].  The
-// buffers are made once, for n columns; the copies are ordered on the batch's stream behind the launches that read the last set.
-// (The apply blocks follow in the next lwhip_batch_formal_sol_gamma_matrices: aValid is off.)
-template <class T> static hipError_t upload_compact(lwhip_batch* b, DevBuf<T>& dev, std::vector<T>& host, const std::vector<T>& full)
+// the argument lists of the active set (lwhip_batch_set_active; all columns: lwhip_batch_create) go to the device, ordered on the
+// batch's stream behind the launches that read the last set.  (The apply blocks follow in the next
+// lwhip_batch_formal_sol_gamma_matrices: aValid is off.)
+static int batch_refresh_lists(lwhip_batch* b)
 {
     lwhip_context* c0 = b->ctxs[0];
-    if (!dev.p)
-    {
-        const hipError_t e = dev.alloc(c0->mem, full.size(), false);
-        if (e != hipSuccess)
-            return e;
-    }
-    host.resize(b->act.size());
-    for (size_t p = 0; p < b->act.size(); ++p)
-        host[p] = full[b->act[p]];
-    return hipMemcpyAsync(dev.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, c0->stream);
-}
-static int batch_upload_active(lwhip_batch* b)
-{
-    lwhip_context* c0 = b->ctxs[0];
-    HIP_TRY(upload_compact(b, b->apAct, b->apActHost, b->apHost));
-    HIP_TRY(upload_compact(b, b->rAct, b->rActHost, b->rHost));
-    HIP_TRY(upload_compact(b, b->seAct, b->seActHost, b->seHost));
-    if (b->change.p)
-        HIP_TRY(upload_compact(b, b->seRepAct, b->seRepActHost, b->seRepHost));
-    if (!b->aAct.p)
-        HIP_TRY(b->aAct.alloc(c0->mem, b->ctxs.size()));
-    b->aActHost.resize(b->act.size());
-    if (!b->colsAct.p)
-        HIP_TRY(b->colsAct.alloc(c0->mem, b->ctxs.size(), false));
+    HIP_TRY(b->ap.refresh(b->act, c0->stream));
+    HIP_TRY(b->r.refresh(b->act, c0->stream));
+    HIP_TRY(b->se.refresh(b->act, c0->stream));
+    HIP_TRY(b->seRep.refresh(b->act, c0->stream));
     HIP_TRY(hipMemcpyAsync(b->colsAct.p, b->act.data(), b->act.size() * sizeof(int32_t), hipMemcpyHostToDevice, c0->stream));
-    HIP_TRY(hipStreamSynchronize(c0->stream)); // (the host lists may change with the next set; a retirement is rare)
+    HIP_TRY(hipStreamSynchronize(c0->stream)); // (what the copies read changes with the next set; a change of set is rare)
+    return LWHIP_OK;
+}
+
+// what batch_conv_kernel and ng_kernel get to find a list position's column: nothing when every column is active
+static const int32_t* batch_cols(const lwhip_batch* b) { return b->allActive ? nullptr : b->colsAct.p; }
+
+// every entry point's opening: the batch is there, and its device is the current one
+static int batch_enter(lwhip_batch* b, const char* what, lwhip_context*& c0)
+{
+    if (!b || b->ctxs.empty())
+        return fail(LWHIP_ERR_INVALID, what);
+    c0 = b->ctxs[0];
+    HIP_TRY(hipSetDevice(c0->device));
     return LWHIP_OK;
 }
 
@@ -111,14 +86,67 @@ static int batch_singular(lwhip_batch* b)
 // the Ng step of the active columns, queued behind their solve
 static hipError_t batch_ng_step(lwhip_batch* b)
 {
-    return ng_step(b->ng, b->allActive ? nullptr : b->colsAct.p, (int)b->act.size(), b->ctxs[0]->stream);
+    return ng_step(b->ng, batch_cols(b), (int)b->act.size(), b->ctxs[0]->stream);
+}
+
+// stat_equil of the active columns in one launch, their Ng step behind it when Ng is on, and one stream wait.  report: the
+// columns' changes -- with Ng its max_change, taken after any extrapolation (rel_diff_ng_accelerate,
+// Source/LwMiddleLayer.pyx:3318-3346), one (value, index) pair per column and atom; else what the solve writes when its arguments
+// aim at `change` (seRep) -- become one record per column (batch_conv_kernel), which one copy brings back.
+static int batch_solve(lwhip_batch* b, bool report, const char* what, double* dPops, int32_t* dPopsMaxIdx)
+{
+    lwhip_context* c0 = nullptr;
+    if (const int st = batch_enter(b, what, c0); st != LWHIP_OK)
+        return st;
+    const int Na = b->se0.Natoms, nAct = (int)b->act.size();
+    if (Na <= 0)
+        return LWHIP_OK;
+    for (const int32_t i : b->act)
+    {
+        lwhip_context* c = b->ctxs[i];
+        const int stp = flush_prefill(c);
+        if (stp != LWHIP_OK)
+            return stp;
+        *c->statusHost = 0;
+    }
+    const bool ownChange = report && !b->ng.on;
+    HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, ownChange ? b->seRep.dev.p : b->se.dev.p, nAct));
+    if (b->ng.on)
+        HIP_TRY(batch_ng_step(b));
+    const size_t stride = 2 + 2 * (size_t)Na;
+    if (report)
+    {
+        BatchConvArgs ca{};
+        ca.tail = b->tail.p;
+        ca.rec = b->rec.p;
+        ca.cols = batch_cols(b);
+        ca.Natoms = Na;
+        ca.change = ownChange ? b->change.p : b->ng.out.p;
+        ca.nBlocks = ownChange ? b->seBlocks : 1;
+        HIP_TRY(launch_batch_conv(ca, nAct, c0->stream));
+        HIP_TRY(hipMemcpyAsync(b->recPinned.host, b->rec.p, b->ctxs.size() * stride * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    if (report)
+        b->recCols = b->act;
+    const int st = batch_singular(b);
+    if (st != LWHIP_OK || !report)
+        return st;
+    const double* rec = b->recPinned.as<double>();
+    for (const int32_t i : b->act)
+        for (int q = 0; q < Na; ++q)
+        {
+            dPops[(size_t)i * Na + q] = rec[i * stride + 2 + 2 * q];
+            if (dPopsMaxIdx)
+                dPopsMaxIdx[(size_t)i * Na + q] = (int32_t)rec[i * stride + 3 + 2 * q];
+        }
+    return LWHIP_OK;
 }
 
 namespace lwhip
 {
 int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols)
 {
-    lwhip_context* c0 = b->ctxs[0];
     std::vector<RetileArgs> rl;
     for (lwhip_context* c : cols)
     {
@@ -126,19 +154,7 @@ int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols)
         if (retile_args(c, r))
             rl.push_back(r);
     }
-    if (!rl.empty())
-    {
-        if (b->retileList.n < rl.size())
-        {
-            HIP_TRY(hipStreamSynchronize(c0->stream));
-            HIP_TRY(b->retileList.alloc(c0->mem, rl.size()));
-        }
-        HIP_TRY(hipMemcpyAsync(b->retileList.p, rl.data(), rl.size() * sizeof(RetileArgs), hipMemcpyHostToDevice, c0->stream));
-        for (size_t off = 0; off < rl.size(); off += 32768)
-            HIP_TRY(launch_retile_list(b->retileList.p + off, rl.data() + off, (int)std::min<size_t>(32768, rl.size() - off),
-                                       c0->stream));
-    }
-    return LWHIP_OK;
+    return launch_list(b->ctxs[0], b->retileList, rl, true, launch_retile_list);
 }
 int batch_ensure_profiles(lwhip_batch* b) { return batch_compute_profiles(b, false); }
 }
@@ -186,78 +202,59 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
     auto b = std::make_unique<lwhip_batch>();
     b->ctxs.assign(ctxs, ctxs + n);
     b->ownStreams = before;
-    std::vector<const TileArgs*> ap(n);
-    std::vector<ReduceArgs> rl(n);
+    HIP_TRY(b->ap.alloc(c0->mem, (size_t)n));
+    HIP_TRY(b->r.alloc(c0->mem, (size_t)n));
+    HIP_TRY(b->a.alloc(c0->mem, (size_t)n));
+    HIP_TRY(b->se.alloc(c0->mem, (size_t)n));
+    HIP_TRY(b->seRep.alloc(c0->mem, (size_t)n));
+    HIP_TRY(b->colsAct.alloc(c0->mem, (size_t)n, false));
+    b->act.resize(n);
     HIP_TRY(b->tail.alloc(c0->mem, (size_t)2 * n));
     for (int i = 0; i < n; ++i)
     {
-        ap[i] = ctxs[i]->dtargs.p;
-        rl[i] = make_reduce_args(ctxs[i]);
-        rl[i].batchTail = b->tail.p + 2 * (size_t)i;
-        rl[i].zeroParts = 1;
-        // the columns' stage-1 buffers start clean (the sweep adds into them, stage 2 zeroes what it has summed)
-        if (!ctxs[i]->red8Clean)
-            HIP_TRY(hipMemsetAsync(ctxs[i]->red8.p, 0, ctxs[i]->red8.n * sizeof(double), c0->stream));
-        ctxs[i]->red8Clean = true;
-    }
-    HIP_TRY(b->apList.upload(c0->mem, ap));
-    HIP_TRY(b->rList.upload(c0->mem, rl));
-    b->apHost = ap;
-    b->rHost = rl;
-    b->act.resize(n);
-    for (int i = 0; i < n; ++i)
+        lwhip_context* c = ctxs[i];
         b->act[i] = i;
-    HIP_TRY(b->aList.alloc(c0->mem, (size_t)n));
-    b->aHost.resize(n);
-    {
-        std::vector<StatEqArgs> sl(n);
-        for (int i = 0; i < n; ++i)
+        b->ap.full[i] = c->dtargs.p;
+        b->r.full[i] = make_reduce_args(c);
+        b->r.full[i].batchTail = b->tail.p + 2 * (size_t)i;
+        b->r.full[i].zeroParts = 1;
+        // the columns' stage-1 buffers start clean (the sweep adds into them, stage 2 zeroes what it has summed)
+        if (!c->red8Clean)
+            HIP_TRY(hipMemsetAsync(c->red8.p, 0, c->red8.n * sizeof(double), c0->stream));
+        c->red8Clean = true;
+        // stat_equil of all its solved atoms, at every depth (a batch's solve does not follow lwhip_set_depth_range)
+        std::vector<NrAtom> atoms;
+        const int maxNl = solved_atoms(c, -1, atoms);
+        if (!atoms.empty())
         {
-            lwhip_context* c = ctxs[i];
-            std::vector<NrAtom> atoms;
-            int maxNl = 0;
-            for (int ia = 0; ia < c->Natom; ++ia)
-            {
-                const lwhip_atom& a = c->atoms[ia];
-                if (a.detailed)
-                    continue;
-                NrAtom at{};
-                at.atom = ia;
-                at.Nlevel = a.Nlevel;
-                at.levelOff = c->levelOff[ia];
-                at.gammaOff = c->gammaOff[ia];
-                atoms.push_back(at);
-                maxNl = std::max(maxNl, a.Nlevel);
-            }
-            if (!atoms.empty())
-            {
-                HIP_TRY(c->statEqAtoms.upload(c->mem, atoms));
-                c->statEqKey = -1;
-            }
-            StatEqArgs sa{};
-            sa.Ns = c->Ns;
-            sa.k0 = 0;
-            sa.k1 = c->Ns;
-            sa.Natoms = (int32_t)atoms.size();
-            sa.atoms = c->statEqAtoms.p;
-            sa.n = c->n.p;
-            sa.nTotal = c->nTotal.p;
-            sa.Gamma = c->Gamma.p;
-            sa.status = c->statusDev;
-            sa.change = nullptr;
-            sl[i] = sa;
-            if (i == 0)
-            {
-                b->se0 = sa;
-                b->seMaxNl = maxNl;
-            }
-            else if (sa.Natoms != b->se0.Natoms || maxNl != b->seMaxNl)
-                return fail(LWHIP_ERR_INVALID, "batch_create: the columns must share their active atoms");
+            HIP_TRY(c->statEqAtoms.upload(c->mem, atoms));
+            c->statEqKey = -1;
         }
-        HIP_TRY(b->seList.upload(c0->mem, sl));
-        b->seHost = sl;
+        StatEqArgs& sa = b->se.full[i] = stat_eq_args(c, (int)atoms.size());
+        sa.k0 = 0;
+        sa.k1 = c->Ns;
+        if (i == 0)
+        {
+            b->se0 = sa;
+            b->seMaxNl = maxNl;
+        }
+        else if (sa.Natoms != b->se0.Natoms || maxNl != b->seMaxNl)
+            return fail(LWHIP_ERR_INVALID, "batch_create: the columns must share their active atoms");
     }
+    // the reported solve: the change records of all columns, a second list of solve arguments that aims at them (the plain
+    // solve keeps launching with `se`, whose change is null), and the records the columns' changes become
+    const size_t Na = (size_t)std::max(b->se0.Natoms, 0);
+    b->seBlocks = stat_eq_blocks(c0->Ns, b->seMaxNl);
+    HIP_TRY(b->change.alloc(c0->mem, (size_t)n * Na * b->seBlocks * 2));
+    b->seRep.full = b->se.full;
+    for (int i = 0; i < n; ++i)
+        b->seRep.full[i].change = b->change.p + (size_t)i * Na * b->seBlocks * 2;
+    HIP_TRY(b->rec.alloc(c0->mem, (size_t)n * (2 + 2 * Na)));
+    HIP_TRY(b->recPinned.reserve(c0->device, (size_t)n * (2 + 2 * Na) * sizeof(double), c0->stream));
     HIP_TRY(b->tailPinned.reserve(c0->device, (size_t)2 * n * sizeof(double), c0->stream));
+    const int st = batch_refresh_lists(b.get());
+    if (st != LWHIP_OK)
+        return st;
     *out = b.release();
     return LWHIP_OK;
 }
@@ -284,22 +281,19 @@ void lwhip_batch_destroy(lwhip_batch* b)
 
 int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, double crsw, lwhip_iter_result* results)
 {
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "null batch");
+    lwhip_context* c0 = nullptr;
+    if (const int st = batch_enter(b, "null batch", c0); st != LWHIP_OK)
+        return st;
     const int n = (int)b->ctxs.size();
-    lwhip_context* c0 = b->ctxs[0];
-    HIP_TRY(hipSetDevice(c0->device));
     {
         // columns whose atmosphere was updated: their phi / wphi first, all their lines in one launch pair
         const int stp = batch_ensure_profiles(b);
         if (stp != LWHIP_OK)
             return stp;
     }
-    // the columns this call launches: all of them, or the compacted lists of the active set (lwhip_batch_set_active)
+    // the columns this call launches: the active set (lwhip_batch_set_active), whose entries the lists' device copies hold
     const int nAct = (int)b->act.size();
-    const TileArgs* const* apL = b->allActive ? b->apList.p : b->apAct.p;
-    const ReduceArgs* rL = b->allActive ? b->rList.p : b->rAct.p;
-    const ApplyArgs* aL = b->allActive ? b->aList.p : b->aAct.p;
+    const TileArgs* const* apL = b->ap.dev.p;
     // Gamma <- crsw * C of every column is fused into its slice of the apply launch
     for (const int32_t i : b->act)
     {
@@ -309,19 +303,12 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
         c->prefillCrsw = crsw;
         c->dJPrdClean = false; // (the batch sweep writes every wavelength's dJ)
         c->prefillPending = c->gammaTot > 0 && c->Cmat.p != nullptr;
-        b->aHost[i] = make_apply_args(c);
+        b->a.full[i] = make_apply_args(c);
         c->prefillPending = false;
     }
     if (!b->aValid || b->aCrsw != crsw)
     {
-        if (b->allActive)
-            HIP_TRY(hipMemcpyAsync(b->aList.p, b->aHost.data(), (size_t)n * sizeof(ApplyArgs), hipMemcpyHostToDevice, c0->stream));
-        else
-        {
-            for (int p = 0; p < nAct; ++p)
-                b->aActHost[p] = b->aHost[b->act[p]];
-            HIP_TRY(hipMemcpyAsync(b->aAct.p, b->aActHost.data(), (size_t)nAct * sizeof(ApplyArgs), hipMemcpyHostToDevice, c0->stream));
-        }
+        HIP_TRY(b->a.refresh(b->act, c0->stream));
         b->aValid = true;
         b->aCrsw = crsw;
     }
@@ -347,10 +334,10 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
     {
         ReduceArgs r0 = make_reduce_args(c0);
         r0.zeroParts = 1;
-        HIP_TRY(launch_reduce_sum(r0, c0->stream, rL, nAct));
+        HIP_TRY(launch_reduce_sum(r0, c0->stream, b->r.dev.p, nAct));
     }
     if (c0->Natom > 0)
-        HIP_TRY(launch_apply(b->aHost[b->act[0]], c0->stream, aL, nAct));
+        HIP_TRY(launch_apply(b->a.full[b->act[0]], c0->stream, b->a.dev.p, nAct));
     if (results)
     {
         HIP_TRY(hipMemcpyAsync(b->tailPinned.host, b->tail.p, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
@@ -367,10 +354,9 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
 
 int lwhip_batch_compute_profiles(lwhip_batch* b)
 {
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "null batch");
-    HIP_TRY(hipSetDevice(b->ctxs[0]->device));
-    return batch_compute_profiles(b, true);
+    lwhip_context* c0 = nullptr;
+    const int st = batch_enter(b, "null batch", c0);
+    return st != LWHIP_OK ? st : batch_compute_profiles(b, true);
 }
 
 int lwhip_batch_sweep_instance(lwhip_batch* b, int32_t out[4])
@@ -390,106 +376,12 @@ int lwhip_batch_sweep_instance(lwhip_batch* b, int32_t out[4])
     return LWHIP_OK;
 }
 
-int lwhip_batch_stat_equil(lwhip_batch* b)
-{
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "null batch");
-    lwhip_context* c0 = b->ctxs[0];
-    HIP_TRY(hipSetDevice(c0->device));
-    if (b->se0.Natoms <= 0)
-        return LWHIP_OK;
-    for (const int32_t i : b->act)
-    {
-        lwhip_context* c = b->ctxs[i];
-        const int stp = flush_prefill(c);
-        if (stp != LWHIP_OK)
-            return stp;
-        *c->statusHost = 0;
-    }
-    HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, b->allActive ? b->seList.p : b->seAct.p, (int)b->act.size()));
-    if (b->ng.on)
-        HIP_TRY(batch_ng_step(b));
-    HIP_TRY(hipStreamSynchronize(c0->stream));
-    return batch_singular(b);
-}
+int lwhip_batch_stat_equil(lwhip_batch* b) { return batch_solve(b, false, "null batch", nullptr, nullptr); }
 
 int lwhip_batch_stat_equil_report(lwhip_batch* b, double* dPops, int32_t* dPopsMaxIdx)
 {
-    if (!b || b->ctxs.empty() || !dPops)
-        return fail(LWHIP_ERR_INVALID, "batch_stat_equil_report: null argument");
-    lwhip_context* c0 = b->ctxs[0];
-    HIP_TRY(hipSetDevice(c0->device));
-    const int Na = b->se0.Natoms;
-    if (Na <= 0)
-        return LWHIP_OK;
-    const int n = (int)b->ctxs.size(), nAct = (int)b->act.size();
-    const size_t stride = 2 + 2 * (size_t)Na;
-    if (!b->rec.p)
-    {
-        // the records the columns' changes become
-        HIP_TRY(b->rec.alloc(c0->mem, (size_t)n * stride));
-        HIP_TRY(b->recPinned.reserve(c0->device, (size_t)n * stride * sizeof(double), c0->stream));
-    }
-    if (!b->ng.on && !b->change.p)
-    {
-        // the change records of all columns and a second list of solve arguments that aims at them
-        b->seBlocks = stat_eq_blocks(c0->Ns, b->seMaxNl);
-        HIP_TRY(b->change.alloc(c0->mem, (size_t)n * Na * b->seBlocks * 2));
-        b->seRepHost = b->seHost;
-        for (int i = 0; i < n; ++i)
-            b->seRepHost[i].change = b->change.p + (size_t)i * Na * b->seBlocks * 2;
-        HIP_TRY(b->seRepList.upload(c0->mem, b->seRepHost));
-        if (!b->allActive)
-        {
-            const int stu = batch_upload_active(b);
-            if (stu != LWHIP_OK)
-                return stu;
-        }
-    }
-    for (const int32_t i : b->act)
-    {
-        lwhip_context* c = b->ctxs[i];
-        const int stp = flush_prefill(c);
-        if (stp != LWHIP_OK)
-            return stp;
-        *c->statusHost = 0;
-    }
-    BatchConvArgs ca{};
-    ca.tail = b->tail.p;
-    ca.rec = b->rec.p;
-    ca.cols = b->allActive ? nullptr : b->colsAct.p;
-    ca.Natoms = Na;
-    if (b->ng.on)
-    {
-        // the plain solve, then the Ng step: the reported change is Ng's max_change, taken after any extrapolation
-        // (rel_diff_ng_accelerate, Source/LwMiddleLayer.pyx:3318-3346) -- one (value, index) pair per column and atom
-        HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, b->allActive ? b->seList.p : b->seAct.p, nAct));
-        HIP_TRY(batch_ng_step(b));
-        ca.change = b->ng.out.p;
-        ca.nBlocks = 1;
-    }
-    else
-    {
-        HIP_TRY(launch_stat_eq(b->se0, b->seMaxNl, c0->stream, b->allActive ? b->seRepList.p : b->seRepAct.p, nAct));
-        ca.change = b->change.p;
-        ca.nBlocks = b->seBlocks;
-    }
-    HIP_TRY(launch_batch_conv(ca, nAct, c0->stream));
-    HIP_TRY(hipMemcpyAsync(b->recPinned.host, b->rec.p, (size_t)n * stride * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
-    HIP_TRY(hipStreamSynchronize(c0->stream));
-    b->recCols = b->act;
-    const int st = batch_singular(b);
-    if (st != LWHIP_OK)
-        return st;
-    const double* rec = b->recPinned.as<double>();
-    for (const int32_t i : b->act)
-        for (int q = 0; q < Na; ++q)
-        {
-            dPops[(size_t)i * Na + q] = rec[i * stride + 2 + 2 * q];
-            if (dPopsMaxIdx)
-                dPopsMaxIdx[(size_t)i * Na + q] = (int32_t)rec[i * stride + 3 + 2 * q];
-        }
-    return LWHIP_OK;
+    const char* what = "batch_stat_equil_report: null argument";
+    return dPops ? batch_solve(b, true, what, dPops, dPopsMaxIdx) : fail(LWHIP_ERR_INVALID, what);
 }
 
 int lwhip_batch_conv_records(lwhip_batch* b, double* records, int* strideOut)
@@ -507,8 +399,9 @@ int lwhip_batch_conv_records(lwhip_batch* b, double* records, int* strideOut)
 
 int lwhip_batch_set_active(lwhip_batch* b, const int32_t* columns, int nActive)
 {
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "null batch");
+    lwhip_context* c0 = nullptr;
+    if (const int st = batch_enter(b, "null batch", c0); st != LWHIP_OK)
+        return st;
     const int n = (int)b->ctxs.size();
     if (nActive < 0 || (nActive > 0 && !columns))
         return fail(LWHIP_ERR_INVALID, "batch_set_active: nActive < 0, or a count without a list");
@@ -516,8 +409,6 @@ int lwhip_batch_set_active(lwhip_batch* b, const int32_t* columns, int nActive)
         if (columns[p] < 0 || columns[p] >= n || (p > 0 && columns[p] <= columns[p - 1]))
             return fail(LWHIP_ERR_INVALID, "batch_set_active: entry " + std::to_string(p) + " (" + std::to_string(columns[p])
                                                + ") is out of range or not above the one before it");
-    lwhip_context* c0 = b->ctxs[0];
-    HIP_TRY(hipSetDevice(c0->device));
     const bool all = nActive == 0 || !columns || nActive == n;
     std::vector<int32_t> act(all ? n : nActive);
     for (int p = 0; p < (int)act.size(); ++p)
@@ -527,7 +418,7 @@ int lwhip_batch_set_active(lwhip_batch* b, const int32_t* columns, int nActive)
     b->act = act;
     b->allActive = all;
     b->aValid = false; // (the device copy of the apply blocks is that of another set)
-    return all ? LWHIP_OK : batch_upload_active(b);
+    return batch_refresh_lists(b);
 }
 
 int lwhip_batch_active(lwhip_batch* b, int32_t* columns, int* nActive)
@@ -543,11 +434,10 @@ int lwhip_batch_active(lwhip_batch* b, int32_t* columns, int* nActive)
 // Ng acceleration of every column: the shared driver (ng_configure ..., lwhip_api.hip) with the batch's n columns.  (0, 0, 0): off.
 int lwhip_batch_ng_configure(lwhip_batch* b, int Norder, int Nperiod, int Ndelay)
 {
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "null batch");
-    lwhip_context* c0 = b->ctxs[0];
-    HIP_TRY(hipSetDevice(c0->device));
-    const int st = ng_configure(b->ng, b->ctxs, Norder, Nperiod, Ndelay, false);
+    lwhip_context* c0 = nullptr;
+    int st = batch_enter(b, "null batch", c0);
+    if (st == LWHIP_OK)
+        st = ng_configure(b->ng, b->ctxs, Norder, Nperiod, Ndelay, false);
     if (st == LWHIP_OK && b->ng.on && b->ng.Natoms != b->se0.Natoms) // (batch_conv_kernel reads the change records by se0's count)
     {
         (void)ng_off(b->ng, c0->stream);
@@ -558,17 +448,17 @@ int lwhip_batch_ng_configure(lwhip_batch* b, int Norder, int Nperiod, int Ndelay
 
 int lwhip_batch_ng_accelerate(lwhip_batch* b, int32_t* accelerated, double* dPops, int32_t* dPopsMaxIdx)
 {
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "null batch");
+    lwhip_context* c0 = nullptr;
+    int st = batch_enter(b, "null batch", c0);
+    if (st != LWHIP_OK)
+        return st;
     if (!b->ng.on)
         return fail(LWHIP_ERR_INVALID, "lwhip_batch_ng_accelerate before lwhip_batch_ng_configure");
-    lwhip_context* c0 = b->ctxs[0];
-    HIP_TRY(hipSetDevice(c0->device));
     const int Na = b->ng.Natoms;
     for (const int32_t i : b->act)
         *b->ctxs[i]->statusHost = 0;
     HIP_TRY(batch_ng_step(b));
-    int st = ng_fetch(b->ng, c0->stream);
+    st = ng_fetch(b->ng, c0->stream);
     if (st == LWHIP_OK)
         st = batch_singular(b);
     if (st != LWHIP_OK)
@@ -584,9 +474,8 @@ int lwhip_batch_ng_accelerate(lwhip_batch* b, int32_t* accelerated, double* dPop
 
 int lwhip_batch_ng_state(lwhip_batch* b, int32_t opts[3], int32_t* counts, int32_t* lastAccelerated)
 {
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "null batch");
-    HIP_TRY(hipSetDevice(b->ctxs[0]->device));
-    return ng_read_state(b->ng, (int)b->ctxs.size(), b->ctxs[0]->stream, opts, counts, lastAccelerated);
+    lwhip_context* c0 = nullptr;
+    const int st = batch_enter(b, "null batch", c0);
+    return st != LWHIP_OK ? st : ng_read_state(b->ng, (int)b->ctxs.size(), c0->stream, opts, counts, lastAccelerated);
 }
 }

@@ -774,46 +774,89 @@ ApplyArgs make_apply_args(lwhip_context* c);
 int ensure_profiles(lwhip_context* c);
 int voigt_line_list(lwhip_context* c, std::vector<VoigtLineArgs>& out);
 int stat_equil_impl(lwhip_context* c, int atom, bool wait, double* dPops = nullptr, int32_t* dPopsMaxIdx = nullptr);
+int solved_atoms(const lwhip_context* c, int atom, std::vector<NrAtom>& atoms); // atom -1: all that are not detailed; returns maxNl
+StatEqArgs stat_eq_args(const lwhip_context* c, int Natoms);                    // ... and their solve over the context's depth range
+// the context's phi / wphi were just made on the device from (aDamp, vBroad, vlosMu): the Voigt arguments of the two directions of
+// an angle differ by the sign of the line-of-sight velocity alone, those of two angles by its projection alone
+inline void profiles_made_on_device(lwhip_context* c)
+{
+    c->deviceProfiles = true;
+    c->profilesStale = false;
+    c->phiSym = c->vlosZero;
+    c->phiIso = c->vlosZero;
+}
+// A batch's list of argument blocks goes to `dev` (copy; grown first if need be, once nothing can still read the buffer that is
+// replaced) and is launched in pieces: the launch geometry allows 65 535 entries per grid dimension.
+template <class T>
+int launch_list(lwhip_context* c0, DevBuf<T>& dev, const std::vector<T>& list, bool copy,
+                hipError_t (*launch)(const T*, const T*, int, hipStream_t))
+{
+    if (list.empty())
+        return LWHIP_OK;
+    if (copy && dev.n < list.size())
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        HIP_TRY(dev.alloc(c0->mem, list.size(), false));
+    }
+    if (copy)
+        HIP_TRY(hipMemcpyAsync(dev.p, list.data(), list.size() * sizeof(T), hipMemcpyHostToDevice, c0->stream));
+    for (size_t off = 0; off < list.size(); off += 32768)
+        HIP_TRY(launch(dev.p + off, list.data() + off, (int)std::min<size_t>(32768, list.size() - off), c0->stream));
+    return LWHIP_OK;
+}
 // lwhip_api2d.hip
 int run_2d(lwhip_context* c, int lambdaIterate, int mode = 0);
 }
 
 // ---- 1.5D column batches: one iteration of n structurally identical contexts in one set of launches (lwhip_batch.hip;
 // their full-Stokes calls: lwhip_stokes_batch.hip, lwhip_stokes_fs.hip) ----------
+// One per-column argument list of a batch.  Every batched kernel picks its column by list position, so the entries of the active
+// columns alone (lwhip_batch_set_active), position p = column act[p], are all it needs to run a smaller batch -- and all
+// columns are the set act = 0 .. n-1.
+template <class T> struct ColList
+{
+    std::vector<T> full;   // every column's entry
+    DevBuf<T> dev;         // made once, for all columns: the entries of the active ones, in the order of act
+    std::vector<T> staged; // ... as the queued copy reads them
+    hipError_t alloc(DevMem& mem, size_t n) // (lwhip_batch_create; every entry a launch reads is copied there first)
+    {
+        full.resize(n);
+        return dev.alloc(mem, n, false);
+    }
+    hipError_t refresh(const std::vector<int32_t>& act, hipStream_t stream)
+    {
+        staged.resize(act.size());
+        for (size_t p = 0; p < act.size(); ++p)
+            staged[p] = full[act[p]];
+        return hipMemcpyAsync(dev.p, staged.data(), staged.size() * sizeof(T), hipMemcpyHostToDevice, stream);
+    }
+};
+
 struct lwhip_batch
 {
     std::vector<lwhip_context*> ctxs;
     std::vector<hipStream_t> ownStreams; // what the columns ran on before they joined the batch
-    DevBuf<const TileArgs*> apList;
-    DevBuf<ReduceArgs> rList;
-    DevBuf<ApplyArgs> aList;
-    DevBuf<double> tail;       // [n][2] (dJMax, idx) of every column
-    PinnedBlock tailPinned;
-    std::vector<ApplyArgs> aHost;
-    double aCrsw = 0.0;        // what the device copy of the apply blocks was built with
+    // The active set (lwhip_batch_set_active) and the argument lists of its columns: refreshed together whenever the set
+    // changes (batch_refresh_lists), except the apply blocks, which the next iteration rebuilds and uploads (aValid is off).
+    std::vector<int32_t> act;            // the active columns, increasing (0 .. n-1 when all are)
+    bool allActive = true;               // (then batch_conv_kernel / ng_kernel get no column list: batch_cols)
+    DevBuf<int32_t> colsAct;             // act on the device
+    ColList<const TileArgs*> ap;
+    ColList<ReduceArgs> r;
+    ColList<ApplyArgs> a;
+    ColList<StatEqArgs> se, seRep;       // stat_equil of all solved atoms of every column; seRep: change -> `change` below
+    double aCrsw = 0.0;                  // what the device copy of the apply blocks was built with
     bool aValid = false;
-    DevBuf<StatEqArgs> seList; // stat_equil of all active atoms of every column
     StatEqArgs se0{};
     int seMaxNl = 0;
-    // The active set (lwhip_batch_set_active): the lists above stay those of ALL columns; a proper subset gets compacted
-    // copies (position p = column act[p]), which is all a batched kernel needs to run a smaller batch.
-    bool allActive = true;
-    std::vector<int32_t> act;                  // the active columns, increasing (0 .. n-1 when all are)
-    std::vector<const TileArgs*> apHost, apActHost;
-    std::vector<ReduceArgs> rHost, rActHost;
-    std::vector<StatEqArgs> seHost, seRepHost, seActHost, seRepActHost; // (seRep*: change -> this batch's change buffer)
-    std::vector<ApplyArgs> aActHost;
-    DevBuf<const TileArgs*> apAct;
-    DevBuf<ReduceArgs> rAct;
-    DevBuf<ApplyArgs> aAct;
-    DevBuf<StatEqArgs> seAct, seRepList, seRepAct;
-    DevBuf<int32_t> colsAct;                   // act on the device (batch_conv_kernel)
-    // lwhip_batch_stat_equil_report (made by the first call)
-    int seBlocks = 0;                          // solve blocks per atom and column
-    DevBuf<double> change;                     // [n][Natoms][seBlocks][2], what stat_eq_body writes per column
-    DevBuf<double> rec;                        // [n][2 + 2 Natoms]: dJMax, idx, then (dPops, idx) per atom
+    DevBuf<double> tail;                 // [n][2] (dJMax, idx) of every column
+    PinnedBlock tailPinned;
+    // lwhip_batch_stat_equil_report
+    int seBlocks = 0;                    // solve blocks per atom and column
+    DevBuf<double> change;               // [n][Natoms][seBlocks][2], what stat_eq_body writes per column
+    DevBuf<double> rec;                  // [n][2 + 2 Natoms]: dJMax, idx, then (dPops, idx) per atom
     PinnedBlock recPinned;
-    std::vector<int32_t> recCols;              // the columns the last report solved (whose rows of recPinned are its)
+    std::vector<int32_t> recCols;        // the columns the last report solved (whose rows of recPinned are its)
     NgState ng;                                // lwhip_batch_ng_configure: Ng acceleration of every column
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments

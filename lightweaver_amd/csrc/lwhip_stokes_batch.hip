@@ -63,20 +63,15 @@ int lwhip_batch_compute_polarised_profiles(lwhip_batch* b)
     for (lwhip_context* c : b->ctxs)
         list.insert(list.end(), c->stokes.argsHost.begin(), c->stokes.argsHost.end());
     // (uploaded again only when a column's blocks changed; the host copy is the source of the queued copy)
-    if (b->polHost.size() != list.size() || std::memcmp(b->polHost.data(), list.data(), list.size() * sizeof(PolLineArgs)) != 0)
+    const bool changed = b->polHost.size() != list.size() || std::memcmp(b->polHost.data(), list.data(), list.size() * sizeof(PolLineArgs)) != 0;
+    if (changed)
     {
         HIP_TRY(hipStreamSynchronize(c0->stream)); // nothing may still read the blocks about to be replaced
         b->polHost.swap(list);
-        if (b->polList.n < b->polHost.size())
-            HIP_TRY(b->polList.alloc(c0->mem, b->polHost.size(), false));
-        HIP_TRY(hipMemcpyAsync(b->polList.p, b->polHost.data(), b->polHost.size() * sizeof(PolLineArgs), hipMemcpyHostToDevice,
-                               c0->stream));
     }
-    const std::vector<PolLineArgs>& pl = b->polHost;
-    // the launch geometry allows 65 535 entries per grid dimension (as batch_compute_profiles)
-    for (size_t off = 0; off < pl.size(); off += 32768)
-        HIP_TRY(launch_polarised_profiles(b->polList.p + off, pl.data() + off, (int)std::min<size_t>(32768, pl.size() - off),
-                                          c0->stream));
+    const int stl = launch_list(c0, b->polList, b->polHost, changed, launch_polarised_profiles);
+    if (stl != LWHIP_OK)
+        return stl;
     for (lwhip_context* c : b->ctxs)
     {
         c->stokes.polOnDevice = true;

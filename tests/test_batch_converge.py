@@ -335,3 +335,201 @@ def test_set_active_refusals_leave_the_set(gpu):
         assert ra[0] == ra[2] == (-7.0, -7) and ra[1][0] > 0.0 and ra[3][0] > 0.0
         assert lib.lwhip_batch_set_active(h, None, 0) == abi.OK and active() == [0, 1, 2, 3]
         assert all(r[0] > 0.0 for r in raw_fs(batch))
+
+
+# ---- the active set as one list per kind: grown, shrunk and restored with iterations in between ---------------------------------
+def raw_report(batch, fill=-7.0):
+    """lwhip_batch_stat_equil_report called directly, the caller's arrays pre-filled: (dPops, indices), one row per column."""
+    lib = batch.contexts[0].lib
+    n, nAt = len(batch.contexts), sum(1 for a in batch.problems[0].atoms if not a.detailed)
+    dP, dI = np.full((n, nAt), fill), np.full((n, nAt), -7, dtype=np.int32)
+    assert lib.lwhip_batch_stat_equil_report(batch._batch, dP.ctypes.data_as(abi.f64p), dI.ctypes.data_as(abi.i32p)) == abi.OK
+    return dP, dI
+
+
+def lone_column(seed):
+    """A lone Context on a twin of the column, its profiles made on the device as the batch's are."""
+    from lightweaver_amd.context import Context
+    p = column(seed)
+    ctx = Context(p)
+    ctx.compute_profiles(deviceResident=True)
+    return p, ctx
+
+
+def close_to_lone(tag, got, want, idxGot, idxWant):
+    """Batch column against lone context, the bounds of test_reported_solve_matches_oracle_and_lone_context: the same index,
+    the value to rtol 1e-9."""
+    print(tag, 'batch', got, idxGot, 'lone', want, idxWant)
+    assert list(np.atleast_1d(idxGot)) == list(np.atleast_1d(idxWant)), tag
+    assert np.allclose(got, want, rtol=1e-9, atol=0.0), tag
+
+
+@pytest.mark.gpu
+def test_an_active_set_walk_matches_fresh_batches(gpu):
+    """all -> [1, 3] -> [0, 1, 3, 4] -> all -> [2] -> all, one raw iteration and one reported solve at every stop: the lists
+    are refreshed to a smaller set, to a larger one and to the full one with work in between.  Every column is held to a lone
+    Context driven through the same calls; an inactive column keeps its bits and its entries of the pre-filled results."""
+    walk = [None, [1, 3], [0, 1, 3, 4], None, [2], None]
+    probs = [column(s) for s in SEEDS]
+    lones = [lone_column(s) for s in SEEDS]
+    try:
+        with ColumnBatch(probs) as batch:
+            assert batch._batch is not None
+            for stop, cols in enumerate(walk):
+                batch.download()
+                before = [snapshot(p) for p in probs]
+                batch.set_active(cols)
+                act = list(range(len(SEEDS))) if cols is None else cols
+                assert batch.active == act
+                rJ = raw_fs(batch)
+                dP, dI = raw_report(batch)
+                batch.download()
+                for i, (p, (q, ctx)) in enumerate(zip(probs, lones)):
+                    if i not in act:
+                        assert same_bits(before[i], snapshot(p)), (stop, i)
+                        assert rJ[i] == (-7.0, -7) and np.all(dP[i] == -7.0) and np.all(dI[i] == -7), (stop, i)
+                        continue
+                    Ju = ctx.formal_sol_gamma_matrices(deviceResident=True)
+                    Pu = ctx.stat_equil(deviceResident=True)
+                    ctx.download(abi.ALL_OUTPUTS | abi.POPS)
+                    tag = 'stop %d column %d' % (stop, i)
+                    close_to_lone(tag + ' dJMax', rJ[i][0], Ju.dJMax, rJ[i][1], Ju.dJMaxIdx)
+                    close_to_lone(tag + ' dPops', dP[i], Pu.dPops, dI[i], Pu.dPopsMaxIdx)
+                    errs = rel_err(p.J, q.J), rel_err(p.I, q.I)
+                    print(tag, 'J, I rel', errs)
+                    assert max(errs) <= 1e-9, tag
+                    assert not same_bits(before[i], snapshot(p), keys=('J',)), tag
+    finally:
+        for _, ctx in lones:
+            ctx.close()
+
+
+@pytest.mark.gpu
+def test_apply_blocks_follow_crsw_on_a_subset(gpu):
+    """The device copy of the apply blocks (aValid / aCrsw) across a change of crsw and a change of set: [1, 3] active, one raw
+    iteration with crsw and one with half of it, then all columns with that half again -- the same crsw, but another set's
+    blocks.  Gamma of every column that ran against a fresh twin batch given the same calls, to the bound of its atomics
+    (test_result_of_a_column_does_not_depend_on_the_active_set: 1e-11)."""
+    from test_hip_parity import compare_problems
+    pa, pb = [column(s) for s in SEEDS], [column(s) for s in SEEDS]
+
+    def fs(batch, crsw):
+        lib = batch.contexts[0].lib
+        assert lib.lwhip_batch_formal_sol_gamma_matrices(batch._batch, 0, crsw, None) == abi.OK
+        batch.download()
+
+    def lone_fs(pc, cw):
+        pc[1].crsw = cw
+        pc[1].formal_sol_gamma_matrices(deviceResident=True)
+        pc[1].download(abi.ALL_OUTPUTS)
+        return pc[0]
+
+    lones = {i: lone_column(SEEDS[i]) for i in (0, 1)}
+    try:
+        with ColumnBatch(pa) as A, ColumnBatch(pb) as B:
+            crsw = A.contexts[0].crsw
+            for cols, cw in (([1, 3], crsw), ([1, 3], 0.5 * crsw), (None, 0.5 * crsw)):
+                for batch in (A, B):
+                    batch.set_active(cols)
+                    fs(batch, cw)
+                ran = list(range(len(SEEDS))) if cols is None else cols
+                for i in ran:
+                    worst = compare_problems(pa[i], pb[i], tol=1e-11, what=('Gamma',))
+                    print('set', cols, 'crsw', cw, 'column', i, worst)
+                # ... and crsw did arrive (twins would agree on a stale block too): lone Contexts given the same crsw, to the
+                # walk's bound for a batch column against a lone context -- a block of the other crsw is off by half of C
+                for i in lones:
+                    if i in ran:
+                        worst = compare_problems(pa[i], lone_fs(lones[i], cw), tol=1e-9, what=('Gamma',))
+                        print('column', i, 'against its lone context', worst)
+    finally:
+        for _, ctx in lones.values():
+            ctx.close()
+
+
+@functools.lru_cache(maxsize=None)
+def lone_first_report(seed, ng):
+    """A lone Context's reported solve after NSCATTER + 1 iterations (ng: configured just before it), computed once: dPops,
+    indices, ngAccelerated."""
+    p, ctx = lone_column(seed)
+    with ctx:
+        for it in range(NSCATTER + 1):
+            ctx.formal_sol_gamma_matrices(deviceResident=True)
+        if ng is not None:
+            ctx.configure_ng(*ng)
+        up = ctx.stat_equil(deviceResident=True)
+    return tuple(up.dPops), tuple(up.dPopsMaxIdx), bool(up.ngAccelerated)
+
+
+ORDERS = [(first, ng) for first in ('all', 'subset') for ng in (None, (2, 3, 5))]
+
+
+@functools.lru_cache(maxsize=None)
+def first_report_order(first, ng):
+    """One order of first reports on a fresh batch, computed once: all columns or [0, 2] active; with ng the first report is
+    made with Ng configured, which is switched off again before the next.  Every report starts from the same populations
+    (put back in between) and the Gamma of NSCATTER + 1 iterations.  Returns the active set, {column: (dPops, indices,
+    ngAccelerated)} of the Ng-on report (None without ng), of the Ng-off report of that set and of a last one of all columns,
+    and the Ng call counts after the Ng-on report."""
+    from ng_cases import put
+    ncol = len(SEEDS)
+    act = list(range(ncol)) if first == 'all' else [0, 2]
+    probs = [column(s) for s in SEEDS]
+
+    def report(batch, n0, active):
+        for i in active:
+            put(batch.contexts[i], probs[i], n0[i])
+        ups = batch.stat_equil(report=True)
+        assert [u is not None for u in ups] == [i in active for i in range(ncol)]
+        return {i: (list(ups[i].dPops), list(ups[i].dPopsMaxIdx), bool(ups[i].ngAccelerated)) for i in active}
+
+    with ColumnBatch(probs) as batch:
+        assert batch._batch is not None
+        for it in range(NSCATTER + 1):
+            batch.formal_sol_gamma_matrices(sync_host=False)
+        batch.download(abi.POPS)
+        n0 = [[a.n.copy() for a in p.atoms] for p in probs]
+        batch.set_active(act)
+        on = counts = None
+        if ng is not None:
+            batch.configure_ng(*ng)
+            on = report(batch, n0, act)
+            counts = batch.ng_state()['counts']
+            batch.configure_ng(0, 0, 0)
+        off = report(batch, n0, act)
+        batch.set_active(None)
+        full = report(batch, n0, list(range(ncol)))
+    return dict(act=act, on=on, counts=counts, off=off, full=full)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('first,ng', ORDERS)
+def test_first_report_in_any_order(gpu, first, ng):
+    """The change records are made with the batch, so the first report finds the same state whatever came before it
+    (first_report_order: the four orders the lazily made records used to distinguish).  The Ng-off reports agree between this
+    order and each of the other three, and with a lone Context, within the bounds of the walk above.  With Ng on the report
+    agrees with a lone Context that was given configure_ng at the same point -- one recording step, not extrapolated -- within
+    those bounds too (the bound of test_ng_on_changes_nothing_but_ng).  Not bit for bit, as test_batch_ng.py's Twins compare
+    an Ng step from uploaded populations: here the solve in front of the step reads a Gamma that the fused batch sums by
+    atomics, which no lone context reproduces to the last bit."""
+    got = first_report_order(first, ng)
+    act = got['act']
+    if ng is not None:
+        assert got['counts'] == [2 if i in act else 1 for i in range(len(SEEDS))]
+        for i in act:
+            dP, dI, acc = lone_first_report(SEEDS[i], ng)
+            close_to_lone('Ng on, column %d' % i, got['on'][i][0], dP, got['on'][i][1], dI)
+            assert got['on'][i][2] == acc and not acc
+    for i, s in enumerate(SEEDS):
+        dP, dI, _ = lone_first_report(s, None)
+        close_to_lone('all columns at the end, column %d' % i, got['full'][i][0], dP, got['full'][i][1], dI)
+        assert not got['full'][i][2]
+        if i in act:
+            close_to_lone('Ng off, column %d' % i, got['off'][i][0], dP, got['off'][i][1], dI)
+            assert not got['off'][i][2]
+    for other in ORDERS:
+        if other == (first, ng):
+            continue
+        theirs = first_report_order(*other)['off']
+        for i in sorted(set(got['off']) & set(theirs)):
+            close_to_lone('column %d against the order %s' % (i, other), got['off'][i][0], theirs[i][0], got['off'][i][1], theirs[i][1])
