@@ -917,6 +917,13 @@ int lwhip_layout_1d(lwhip_context* ctx, int32_t out[10]);
  * lwhip_batch_sweep_instance: the same of a column batch's one sweep launch, plain only if every column's would be (out[1] = 0). */
 int lwhip_sweep_instance(lwhip_context* ctx, int32_t out[4]);
 int lwhip_batch_sweep_instance(lwhip_batch* batch, int32_t out[4]);
+/* A fingerprint of what lwhip_create planned for this context; launches nothing, copies nothing:
+ *   out[0]          folds the element count and content fingerprint of every structure-table buffer, in the order the
+ *                   library lists them (a context made with lwhip_create_like reports its owner's words)
+ *   out[1]          folds the scalars of the plan (sweep kind, D / LR / R, tile, chunk and slot counts, splits, totals)
+ * Equal words: the same tables and the same launch layout.  They depend on the problem's structure, the options, the
+ * environment's layout knobs and the device's compute-unit count.  LWHIP_ERR_INVALID for a null argument. */
+int lwhip_tables_signature(lwhip_context* ctx, uint64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -793,6 +793,13 @@ class Context:
         _check(self.lib, self.lib.lwhip_sweep_instance(self._h, out), 'lwhip_sweep_instance')
         return {'main': bool(out[0]), 'prdRates': bool(out[1]), 'lanes': bool(out[2]), 'switch': bool(out[3])}
 
+    def tables_signature(self):
+        """Two 64-bit words (include/lwhip.h: lwhip_tables_signature): a fold of the size and content fingerprint of every
+        structure-table buffer, and a fold of the plan's scalars.  Equal words: the same tables and launch layout."""
+        out = (C.c_uint64 * 2)()
+        _check(self.lib, self.lib.lwhip_tables_signature(self._h, out), 'lwhip_tables_signature')
+        return int(out[0]), int(out[1])
+
     def algorithmic_bytes(self):
         b = C.c_double()
         _check(self.lib, self.lib.lwhip_algorithmic_bytes(self._h, C.byref(b)), 'lwhip_algorithmic_bytes')

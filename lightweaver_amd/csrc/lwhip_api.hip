@@ -736,47 +736,17 @@ static int create_impl(const lwhip_problem* prob, const lwhip_options* opts, lwh
 
     DevBuf<double>::alloc_seq() = 0; // (diagnosis: allocations are numbered per context)
     auto c = new lwhip_context();
-    c->prob = *prob;
-    c->atoms.assign(prob->atoms, prob->atoms + prob->Natom);
-    c->device = opts ? opts->device : 0;
-    c->batchHint = opts ? (opts->flags & 0xffff) : 0;
-    c->prdDetailed = opts && (opts->flags & LWHIP_OPT_PRD_DETAILED);
-    c->hprd = opts ? opts->hprd : nullptr;
-    c->deterministic = ((opts && (opts->flags & LWHIP_OPT_DETERMINISTIC)) || env_int("LWHIP_DETERMINISTIC", 0) == 1)
-                       && (!opts || (opts->flags & 0xffff) <= 1);
-    if (c->device < 0 || c->device >= ndev)
+    if (opts && (opts->device < 0 || opts->device >= ndev))
     {
         delete c;
         return fail(LWHIP_ERR_INVALID, "lwhip_create: bad device ordinal");
     }
-    c->laStart = 0;
-    c->laEnd = prob->Nlambda;
-    if (opts && !(opts->laStart == 0 && opts->laEnd == 0))
+    st = context_init_host(c, prob, opts);
+    if (st != LWHIP_OK)
     {
-        c->laStart = opts->laStart;
-        c->laEnd = opts->laEnd;
-        if (c->laStart < 0 || c->laEnd > prob->Nlambda || c->laEnd <= c->laStart)
-        {
-            delete c;
-            return fail(LWHIP_ERR_INVALID, "lwhip_create: bad wavelength shard");
-        }
+        delete c;
+        return st;
     }
-    if (opts && opts->worldSize > 1)
-    {
-        c->worldSize = opts->worldSize;
-        c->worldRank = opts->worldRank;
-        if (c->worldRank < 0 || c->worldRank >= c->worldSize)
-        {
-            delete c;
-            return fail(LWHIP_ERR_INVALID, "lwhip_create: bad worldRank");
-        }
-    }
-    c->is2d = prob->grid2d != nullptr;
-    c->Nx = c->is2d ? prob->grid2d->Nx : 1;
-    c->Nla = c->laEnd - c->laStart;
-    c->Ns = prob->Nspace;
-    c->Nrays = prob->Nrays;
-    c->Natom = prob->Natom;
 
     // (declared before `bail`: the gathered upload, if one opens below, is closed while the context's stream is still its own)
     DevArena arena;

@@ -3,7 +3,8 @@
 // cross file boundaries.
 //
 //     lwhip_api.hip      create / destroy, one iteration (sweep -> reduce -> [all-reduce by the caller] -> apply), populations
-//     lwhip_tables.hip   validation of the descriptor and the per-wavelength activity tables of the sweeps (build_tables)
+//     lwhip_tables.hip   validation of the descriptor; the structure tables of the sweeps in two halves: plan_tables (device-free:
+//                        TableKnobs + compute-unit count -> TablePlan + HostTables) and upload_tables; build_tables drives them
 //     lwhip_state.hip    device allocations, kernel argument blocks, the sweep's launch sequence, upload / download
 //     lwhip_api2d.hip    the 2D iteration's launch sequence, the 2D primitives
 //     lwhip_batch.hip    1.5D column batches
@@ -26,7 +27,6 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -327,6 +327,133 @@ inline std::vector<LineEval> line_eval_records(const std::vector<HostTrans>& tra
     }
     return ev;
 }
+
+// ---- the structure tables (lwhip_tables.hip) ----------------------------------------------------------------------------------
+// The environment's knobs that shape the tables, read once per lwhip_create (read_table_knobs).  The layout knobs are honoured
+// only under LWHIP_DEBUG; the defaults below are what a production process gets.
+struct TableKnobs
+{
+    struct OptInt // a knob whose default is computed where it is used
+    {
+        bool set = false;
+        int v = 0;
+        int value_or(int dflt) const { return set ? v : dflt; }
+    };
+    bool createTiming = false; // LWHIP_CREATE_TIMING: where the host time of the tables goes (stderr)
+    bool verbose = false;      // LWHIP_VERBOSE: tile and finish-program histograms (stderr)
+    bool sweepGiven = false, sweepLanes = false, sweepMarch = false; // LWHIP_SWEEP=lanes|march forces a sweep
+    int tileGeneric = 0;       // LWHIP_TILE_GENERIC > 0: every tile through the guarded generic march (test hook)
+    int laneGeneric = 1;       // LWHIP_LANE_GENERIC=0: no generic kind in the lane sweep (such problems take the march)
+    int tileL = 16;            // LWHIP_TILE_L: most wavelengths of a march tile
+    OptInt tileLH, tileL1;     // LWHIP_TILE_LH / LWHIP_TILE_L1: ... of a tile with two or more slots / with one
+    int lWaves = 4, tWaves = 2; // LWHIP_LWAVES / LWHIP_TWAVES: wavefronts per workgroup of the lane sweep / the march
+    int tileFuse = 1;          // LWHIP_TILE_FUSE=0: the march's post-pass as a launch of its own
+    int laneSplit = 0;         // LWHIP_LANE_SPLIT=1|2|4: wavefronts a tile's rays are split over
+    OptInt laneCut;            // LWHIP_LANE_CUT: chunks of the lane sweep's tail cut in two
+    int depthSplit = -1;       // LWHIP_DEPTH_SPLIT=1|2|4: wavefronts a direction's depth points are split over on the march
+    int detNoWait = 0;         // LWHIP_DET_NOWAIT: fixed-order mode without its waits (measurement only, bit mask)
+    int finFast = 1;           // LWHIP_FIN_FAST=0: the finish's general form for every tile
+};
+
+// What build_tables decides, as scalars: THE declaration list (type, name, initial value).  lwhip_context derives from
+// TablePlan, so a reader says c->laneSweep; plan_tables fills one, upload_tables copies it into the context, and
+// lwhip_tables_signature folds the fields in this order.
+#define LWHIP_TABLE_PLAN(X)                                                                                                     \
+    X(int64_t, gammaTot, 0) X(int64_t, phiTot, 0) X(int64_t, rhoTot, 0) X(int64_t, parTot, 0) /* doubles of the pools */      \
+    X(int64_t, rowsTot, 0)     /* rows of the continuum-row buffer (march, 2D) */                                              \
+    X(int64_t, rowsTileTot, 0) X(int64_t, momTot, 0) X(int64_t, phiTTot, 0) /* doubles of the tiles' rows / moments / phi */  \
+    X(int, NlevTot, 0) X(int, Ntrans, 0) X(int, Nline, 0) X(int, Ncont, 0)                                                    \
+    X(int, maxL, 0) X(int, maxC, 0) X(int, maxM, 0) X(int, maxP, 0) /* most lines / continua / mixed / pure at one wavelength */ \
+    X(int, nContLa, 0)         /* wavelengths with a continuum */                                                              \
+    X(bool, tiled, false)      /* 1D: tiles of structurally identical wavelengths */                                          \
+    X(bool, laneSweep, false)  /* the depth-across-lanes sweep (lwhip_lanesweep.hip), else the ray-column march */            \
+    X(bool, deterministic, false) /* LWHIP_OPT_DETERMINISTIC as asked for; the plan turns it off on the march */              \
+    X(int, laneD, 0) X(int, laneLR, 0) X(int, laneR, 0) /* lane sweep: points per lane, lanes per ray, wavelengths per wavefront */ \
+    X(int, tileL, 12)          /* most wavelengths of a tile */                                                                \
+    X(int, tileCap, 0)         /* > 0: the guarded generic march, up to this many lines / mixed continua per tile */          \
+    X(int, tileWaves, 4)       /* wavefronts per workgroup */                                                                  \
+    X(bool, tileFuse, false)   /* march: the workgroup = one tile, finished by the post-pass inside the sweep launch */       \
+    X(int, depthSplit, 1)      /* march on deep columns: wavefronts a direction's depth points are split over */              \
+    X(int, laneSplit, 1) X(int, laneSplitPrd, 1) /* lane sweep: wavefronts a tile's rays are split over; ... in the PRD rates pass */ \
+    X(int, nTiles, 0) X(int, nTilesPrd, 0) X(int, nTileChunks, 0) X(int, nTileChunksPrd, 0) X(int, nPostChunks, 0)            \
+    X(int, nPostChunksPrd, 0)                                                                                                  \
+    X(int, maxSlotsTile, 0) X(int, maxCTTile, 1) X(int, maxCTPost, 1) /* most slots of a tile; accumulator slots per workgroup */ \
+    X(int, preCols, 0)         /* most level-sum columns a tile's rows need (LDS columns of the pre-pass) */                   \
+    X(bool, chunkOrderOn, false) X(bool, chunkSplitOn, false) /* lane sweep: chunkOrder / chunkSplit are in use */            \
+    X(int, nGenTiles, 0) X(int, momA, 0) /* lane sweep: tiles of the generic kind, moment-scratch rows of their wavefronts */
+struct TablePlan
+{
+#define X(type, name, init) type name = init;
+    LWHIP_TABLE_PLAN(X)
+#undef X
+};
+
+// The device buffers of the structure tables: THE declaration list (element type, name), in upload order.  lwhip_context
+// derives from TableBufs; a context made with lwhip_create_like borrows each from its owner where the bytes agree
+// (upload_tables), and lwhip_tables_signature folds size and content fingerprint of each in this order.
+#define LWHIP_TABLE_BUFS(X)                                                                                                     \
+    X(int32_t, detOff) X(int32_t, detEnt) X(int32_t, detOffPrd) X(int32_t, detEntPrd) /* fixed-order mode: (workgroup, slot) lists */ \
+    X(double, lineWave) X(double, lineWlam) X(double, par)                                                                     \
+    X(DevTrans, dtrans) X(DevLaHeader, laHdr) X(DevSlot, slots) X(int32_t, slotTrD)                                            \
+    X(DevProgram, progs) X(DevProgRow, progRows) X(DevProgEnt, progEnts)                                                       \
+    X(int32_t, contLa) X(int32_t, rayAll) X(int32_t, rayUp)                                                                    \
+    X(DevContRec, contRec) X(DevPostProg, postProg)                                                                            \
+    X(DevTile, tiles) X(DevTileSlot, tslots) X(DevTileSlot, tslotsPrd) X(DevTileCopy, tcopies) X(int32_t, tileRemap)           \
+    X(int32_t, chunkTile)                                                                                                      \
+    X(int32_t, chunkOrder) /* lane sweep: dispatch order of the workgroups' chunks */                                          \
+    X(int32_t, chunkSplit) /* ... per chunk, the wavefronts its tiles' rays are split over (the launch's tail) */              \
+    /* lane sweep: the flat per-workgroup / per-tile records of a task's setup and finish (lwhip_internal.h) */               \
+    X(DevLaneWg, laneWg)                                                                                                       \
+    X(uint8_t, laneFeedG)  /* generic tiles: continuum -> slot feed bytes */                                                   \
+    X(DevLaneTile, laneTiles) X(DevLaneTile, laneTilesPrd) X(DevLaneWg, laneWgPrd)                                             \
+    X(DevLaneRay, laneRays) X(DevLaneFin, laneFin) X(double, laneFinPar)                                                       \
+    X(int32_t, chunkTilePrd) X(int32_t, tileListPrd) X(int32_t, tileSlotTr) X(int32_t, tileSlotTrPrd)                          \
+    X(int32_t, postChunkTile) X(int32_t, postChunkTilePrd) X(int32_t, postSlotTr) X(int32_t, postCs)                           \
+    X(int32_t, transLi) X(int32_t, transLj) X(int32_t, atomNlevel) X(int32_t, atomDetailed) X(int32_t, atomTrOffD)
+struct TableBufs
+{
+#define X(type, name) DevBuf<type> name;
+    LWHIP_TABLE_BUFS(X)
+#undef X
+};
+
+// Everything plan_tables hands upload_tables beside the plan: the bytes of every table, the host vectors the context keeps, and
+// the sizes of the few allocations.  A vector left empty is a table this context does not have.
+struct HostTables
+{
+#define X(type, name) std::vector<type> name;
+    LWHIP_TABLE_BUFS(X) // (one per buffer of TableBufs, as it is uploaded)
+#undef X
+    // what the context keeps on the host (lwhip_context's members of the same names)
+    std::vector<HostTrans> trans;
+    std::vector<int> levelOff, atomTrOff;
+    std::vector<int64_t> gammaOff;
+    std::vector<int> hLa2prdHost, hLa2hHost;
+    std::vector<int64_t> hRhoOffHost;
+    // hybrid PRD: never borrowed (the coefficients follow the atmosphere)
+    std::vector<lwhip_rho_coeff> hRho;
+    std::vector<int32_t> hLa2h;
+    std::vector<int64_t> hJOff;
+    std::vector<lwhip_j_coeff> hJCoef;
+    // elements of the allocations (0: none)
+    size_t JRestCount = 0, detSlabCount = 0, detPartCount = 0, momScratchCount = 0;
+    // between the stages of the plan only
+    std::vector<int> laneCsPure;    // lane sweep: accumulator slot of every pure continuum inside its workgroup chunk
+    std::vector<char> ppWide;       // per tile: the finish program's words are in the wide encoding
+    std::vector<uint32_t> turnPure; // fixed-order mode: per (tile, continuum) the task's turn at the continuum's slot
+};
+
+// the fold of structure_signature, for lwhip_tables_signature's two words
+struct SigFold
+{
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+    void mix(uint64_t v)
+    {
+        h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
+        h *= 0xFF51AFD7ED558CCDull;
+        h ^= h >> 33;
+    }
+};
 }
 using namespace lwhip;
 
@@ -463,41 +590,26 @@ void fingerprint_J_fold(lwhip_context* c, const void* p);
 void peer_apply_args(lwhip_context* c, struct ApplyArgs& a);
 }
 
-struct lwhip_context
+// (TablePlan, TableBufs: what build_tables decided and put on the device -- one declaration list each, above)
+struct lwhip_context : lwhip::TablePlan, lwhip::TableBufs
 {
     lwhip_problem prob;             // copy of the descriptor (host pointers borrowed)
     std::vector<lwhip_atom> atoms;
-    std::vector<HostTrans> trans;   // global transition list, reference order
+    std::vector<HostTrans> trans;   // global transition list, reference order (these vectors: copies of the HostTables')
     std::vector<int> levelOff, atomTrOff;
     std::vector<int64_t> gammaOff;
     int device = 0;
     int worldSize = 1, worldRank = 0;
     int laStart = 0, laEnd = 0, Nla = 0;
-    int Ns = 0, Nrays = 0, Natom = 0, NlevTot = 0, Ntrans = 0, Nline = 0, Ncont = 0;
-    int maxL = 0, maxC = 0;
-    int maxM = 0, maxP = 0; // most mixed / pure continua at one wavelength
+    int Ns = 0, Nrays = 0, Natom = 0;
     bool is2d = false;            // x-periodic 2D geometry (prob.grid2d): batched pipeline of lwhip_2d.hip
     int Nx = 1, batch2d = 1;
     std::vector<DevLaHeader> hdrHost;
     std::vector<int32_t> contLaHost;
-    // the ray-column sweep (lwhip_raymarch.hip): tiles of structurally identical wavelengths
-    bool tiled = false;
-    int tileL = 12, nTiles = 0, nTileChunks = 0, nTileChunksPrd = 0, nPostChunks = 0, nPostChunksPrd = 0, nTilesPrd = 0;
-    bool tileFuse = false; // the sweep's workgroup = one tile, finished by the post-pass inside the sweep launch
-    int depthSplit = 1;    // the march on deep columns: a direction's depth points split over this many wavefronts (lwhip_raymarch.hip)
-    // depth-across-lanes sweep (lwhip_lanesweep.hip): D points per lane, LR lanes per ray, R wavelengths per wavefront
-    bool laneSweep = false;
-    bool chunkOrderOn = false, chunkSplitOn = false;
-    int laneSplitPrd = 1;          // ... in the PRD rates pass (its tile list is shorter)
-    int laneSplit = 1;             // lane sweep: wavefronts a tile's rays are split over (1, 2, 4)
-    int laneD = 0, laneLR = 0, laneR = 0;
-    DevBuf<DevPostProg> postProg;
     DevBuf<double> geoT;
     // hybrid PRD (lwhip_options.hprd): the tables of configure_hprd_coeffs on the device
-    // deterministic mode (LWHIP_OPT_DETERMINISTIC): per-workgroup slabs + the (workgroup, slot) lists of every transition
-    bool deterministic = false;
+    // deterministic mode (LWHIP_OPT_DETERMINISTIC): per-workgroup slabs (the (workgroup, slot) lists of every transition: TableBufs)
     DevBuf<double> detSlab, detPart; // (detPart: partial sums of the fixed-shape reduction, lwhip_lanesweep.hip)
-    DevBuf<int32_t> detOff, detEnt, detOffPrd, detEntPrd;
     const lwhip_hprd* hprd = nullptr;
     std::vector<int> hLa2prdHost, hLa2hHost;     // global wavelength -> row of JRest / ordinal among hPrdIdxs, or -1
     std::vector<int64_t> hRhoOffHost;             // per transition: offset of its rho-coefficient block, or -1
@@ -508,44 +620,22 @@ struct lwhip_context
     DevBuf<double> JRest;
     PinnedBlock lsDbg;           // LWHIP_LS_TIMING: phase clocks of the last sweep, [nTiles][8] (mapped)
     DevBuf<double> depArena; // lane sweep: n | wphi | ratio | geoT in one allocation (one buffer resource in the kernel)
-    int tileWaves = 4, maxSlotsTile = 0, maxCTTile = 1, maxCTPost = 1, tileCap = 0, ktStride = 4;
-    int64_t rowsTileTot = 0, momTot = 0, phiTTot = 0;
-    int preCols = 0;              // most level-sum columns a tile's rows need (LDS columns of the pre-pass)
-    DevBuf<DevTile> tiles;
-    DevBuf<DevTileSlot> tslots, tslotsPrd;
-    DevBuf<DevTileCopy> tcopies;
-    DevBuf<int32_t> tileRemap;
-    DevBuf<DevContRec> contRec;
-    DevBuf<int32_t> chunkOrder;   // lane sweep: dispatch order of the workgroups' chunks
-    // lane sweep: the flat per-workgroup / per-tile records of a task's setup and finish (lwhip_internal.h)
-    DevBuf<DevLaneWg> laneWg, laneWgPrd;
-    DevBuf<DevLaneTile> laneTiles, laneTilesPrd;
-    DevBuf<DevLaneRay> laneRays;
-    DevBuf<DevLaneFin> laneFin;
-    DevBuf<double> laneFinPar, bcPlanck;
-    DevBuf<uint8_t> laneFeedG;    // generic tiles of the lane sweep: continuum -> slot feed bytes
-    int nGenTiles = 0;
-    DevBuf<double> momScratch;    // ... and the moment scratch of their wavefronts (TileArgs::momS)
-    int momA = 0;
-    DevBuf<int32_t> chunkSplit;   // lane sweep: per chunk, the wavefronts its tiles' rays are split over (the launch's tail)
-    DevBuf<int32_t> chunkTile, chunkTilePrd, tileListPrd, tileSlotTr, tileSlotTrPrd, postChunkTile, postChunkTilePrd, postSlotTr,
-        postCs;
+    int ktStride = 4;
+    DevBuf<double> bcPlanck;
+    DevBuf<double> momScratch;    // the moment scratch of the generic tiles' wavefronts (TileArgs::momS)
     DevBuf<double> geo, kt, rowsTile, momTile, phiT;
     DevBuf<TileArgs> dtargs, dtargsPrd;
     TileArgs htargs{}, htargsPrd{};
-    int64_t rowsTot = 0;
-    int nContLa = 0;
-    int64_t gammaTot = 0, phiTot = 0, rhoTot = 0, parTot = 0;
     DevMem mem;                   // allocations, fills and uploads: all on the context's stream
     hipStream_t& stream = mem.stream;
     hipStream_t ownStream = nullptr;
     bool ownStreamShared = false;
 
     DevBuf<double> height, temperature, muz, wmu, wavelength, lowerBcData, upperBcData;
-    DevBuf<int32_t> rayAll, rayUp, lowerIdx, upperIdx;
+    DevBuf<int32_t> lowerIdx, upperIdx;
     DevBuf<double> bgChi, bgEta, bgSca, J, I, depthChi, depthEta, depthI;
-    DevBuf<double> n, nTotal, ratio, wphi, phi, rho, par, Gamma, Cmat, Rij, Rji;
-    DevBuf<double> vlosMu, vBroad, aDamp, Qelast, lineWave, lineWlam;
+    DevBuf<double> n, nTotal, ratio, wphi, phi, rho, Gamma, Cmat, Rij, Rji;
+    DevBuf<double> vlosMu, vBroad, aDamp, Qelast;
     DevBuf<double> prdChange, rowsBuf, popScratch, prdJt, prdJ;
     DevBuf<PrdLineArgs> prdArgsDev;   // argument blocks of the PRD lines of a sub-iteration (one launch for all lines)
     std::vector<PrdLineArgs> prdArgsHost; // what the device copy holds
@@ -573,7 +663,6 @@ struct lwhip_context
     double* zDownHost = nullptr;       // their host arrays [Nlambda, Nrays, Nx]
     double* zUpHost = nullptr;
     DevBuf<int32_t> xIdxLow, xIdxUp;   // [Nrays, 2]
-    DevBuf<int32_t> slotTrD;
     DevBuf<double> b2lc; // [batch2d][NlongChar][3]
     // lwhip_create_like: the structure tables (lwhip_tables.hip) are borrowed from a context of the same structure, which
     // counts its borrowers and cannot be destroyed before them
@@ -597,7 +686,6 @@ struct lwhip_context
     double* changeDev = nullptr;
     size_t changeCount = 0;
     DevBuf<int32_t> transType;
-    DevBuf<int32_t> contLa;
     DevBuf<int32_t> prdChangeIdx;
     PinnedBlock prdPinned;
     // pipelined sub-iterations of lwhip_redistribute_prd (one device, 1D, lane sweep): the launches of up to PRD_PIPE_DEPTH
@@ -620,19 +708,12 @@ struct lwhip_context
     PinnedBlock prdPinnedPipe;
     int prdPipeIter = 0;     // > 0: the sub-iteration the calls of lwhip_prd_partial / _finalise belong to
     double prdPipeTol = 0.0;
-    DevBuf<DevTrans> dtrans;
-    DevBuf<DevLaHeader> laHdr;
-    DevBuf<DevSlot> slots;
-    DevBuf<DevProgram> progs;
-    DevBuf<DevProgRow> progRows;
-    DevBuf<DevProgEnt> progEnts;
     DevBuf<ContArgs> dargs;      // 2D: argument block of the continuum-row kernel
     ContArgs hargs{};
     bool atomicParts = false;     // the pending iteration's parts were accumulated by atomics
     bool red8Clean = false;       // red8 holds zeros (only the atomic path leaves it so)
     int* zeroCheck = nullptr;     // LWHIP_CHECK_ZERO=1 (diagnosis): host-mapped count of non-zero words found in red8 at sweep entry
     int* zeroCheckDev = nullptr;  // (windows of hostBlock; null unless the knob is set)
-    DevBuf<int32_t> atomTrOffD, atomNlevel, atomDetailed, transLi, transLj;
     DevBuf<int64_t> atomGammaOff;
     DevBuf<double> red, red8, dJ;
     std::vector<double> gatherHost;
@@ -755,8 +836,14 @@ inline double trans_wlambda(const lwhip_transition& t, int lt)
 
 // lwhip_tables.hip
 int validate(const lwhip_problem* p, std::string& why);
-int build_tables(lwhip_context* c);
 uint64_t structure_signature(const lwhip_context* c);
+// the context's host fields from the descriptor and the options (no device needed); refuses a bad shard or rank
+int context_init_host(lwhip_context* c, const lwhip_problem* prob, const lwhip_options* opts);
+TableKnobs read_table_knobs();
+int plan_tables(const lwhip_context& c, const TableKnobs& k, int numCU, TablePlan& p, HostTables& ht); // device-free
+int upload_tables(lwhip_context* c, const TablePlan& p, const HostTables& ht);
+int build_tables(lwhip_context* c); // knobs, compute-unit count, plan, upload
+uint64_t plan_signature(const TablePlan& p); // lwhip_tables_signature's second word
 // lwhip_state.hip
 int alloc_state(lwhip_context* c);
 int build_sweep_args(lwhip_context* c);
