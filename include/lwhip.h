@@ -605,11 +605,41 @@ int lwhip_batch_compute_profiles(lwhip_batch* batch);
  *    decision and its coefficients come from its own count and history alone;
  *  - with all columns active the launches and copies of the three entry points are what they were before there was an
  *    active set; and with Ng off they are what they were before there was Ng for batches.
- * Out of scope for batches: PRD sub-iterations, time-dependent and charge-conserving updates. */
+ * The time-dependent and charge-conserving updates of a batch (lwhip_batch_time_dep_update, lwhip_batch_nr_post_update, below)
+ * follow the active set under the same invariants.  Out of scope for batches: PRD sub-iterations. */
 int lwhip_batch_stat_equil_report(lwhip_batch* batch, double* dPops /* [n][Natoms] */, int32_t* dPopsMaxIdx /* [n][Natoms] or NULL */);
 int lwhip_batch_conv_records(lwhip_batch* batch, double* records /* [n][2 + 2 Natoms] */, int* stride /* or NULL */);
 int lwhip_batch_set_active(lwhip_batch* batch, const int32_t* columns, int nActive);
 int lwhip_batch_active(lwhip_batch* batch, int32_t* columns /* [n] or NULL */, int* nActive);
+
+/* Population updates for column batches: lwhip_time_dep_update of every solved atom, and lwhip_nr_post_update, of every ACTIVE
+ * column in one launch each, at every depth point (a batch does not follow lwhip_set_depth_range), with the per-column change
+ * of what was updated: per column and atom max |(new - old) / new| over the populations with new != 0 and the flattened
+ * [level, depth] index of its first occurrence, (0, 0) where nothing changed (LwContext.rel_diff_pops: what the reference's
+ * time_dep_update / nr_post_update report).  A call stages everything it sends -- the active columns' argument blocks, then
+ * their arrays -- in one pinned block; on the batch's stream it is one copy up, the update launch, batch_conv_kernel, one copy
+ * back (the records; for the Newton-Raphson step also ne) and one stream wait.  The records also become those
+ * lwhip_batch_conv_records returns (dJMax as the last formal solution left it).  Neither call runs the batch's Ng step or
+ * changes its counts and histories.  A column's result does not depend on which other columns are active; a retired column's n
+ * and the caller's ne array of it are not touched; dPops / dPopsMaxIdx rows are indexed by the ORIGINAL column number, rows of
+ * inactive columns untouched.
+ *
+ * lwhip_batch_time_dep_update: nOld [n] host pointers, one per column (entries of inactive columns are ignored): the solved
+ * atoms' [Nlevel, Nspace] blocks back to back in atom order; dt [n]; dPops / dPopsMaxIdx [n][Natoms] or NULL.
+ * lwhip_batch_nr_post_update: perColumn [n], the lwhip_nr_args of lwhip_nr_post_update, one per column (entries of inactive
+ * columns are ignored); ne of every active column is updated in place on return.  dPops / dPopsMaxIdx [n][Natoms] or NULL,
+ * Natoms the number of SOLVED atoms: the entries of the listed atoms are written, those of solved atoms the call does not list
+ * are left untouched (their places in the conv records hold 0).
+ * A singular system at a depth point leaves that point's n (and ne) as they were and the call returns LWHIP_ERR_SINGULAR with
+ * dPops / dPopsMaxIdx untouched; the other points and columns are updated (ne of every active column is still written).
+ * Refused before anything is queued, outputs untouched -- LWHIP_ERR_INVALID: a null batch; a null nOld, dt or perColumn; for an
+ * active column a null nOld[i], or null atoms, stages, ne or backgroundNe (or a null entry of stages, nPrev, dC); a listed atom
+ * that is detailed, out of range or has no C; a column whose Natoms, atom list or presence of dC / nPrev differs from the
+ * first active column's (the message names the column).  LWHIP_ERR_UNSUPPORTED: more than 63 coupled levels. */
+int lwhip_batch_time_dep_update(lwhip_batch* batch, const double* const* nOld, const double* dt,
+                                double* dPops, int32_t* dPopsMaxIdx);
+int lwhip_batch_nr_post_update(lwhip_batch* batch, const lwhip_nr_args* perColumn,
+                               double* dPops, int32_t* dPopsMaxIdx);
 
 /* Ng acceleration for column batches: every column behaves as a lone context with lwhip_ng_configure would (struct Ng,
  * Source/Ng.hpp:16-156, driven as LwContext.stat_equil drives it), with its own history and its own call count, both on the

@@ -262,6 +262,8 @@ SYMBOLS = [
     ('lwhip_batch_conv_records', C.c_int, [C.c_void_p, f64p, C.POINTER(C.c_int)]),
     ('lwhip_batch_set_active', C.c_int, [C.c_void_p, i32p, C.c_int]),
     ('lwhip_batch_active', C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_int)]),
+    ('lwhip_batch_time_dep_update', C.c_int, [C.c_void_p, C.POINTER(f64p), f64p, f64p, i32p]),
+    ('lwhip_batch_nr_post_update', C.c_int, [C.c_void_p, C.POINTER(lwhip_nr_args), f64p, i32p]),
     ('lwhip_batch_ng_configure', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ('lwhip_batch_ng_accelerate', C.c_int, [C.c_void_p, i32p, f64p, i32p]),
     ('lwhip_batch_ng_state', C.c_int, [C.c_void_p, i32p, i32p, i32p]),

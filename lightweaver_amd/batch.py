@@ -32,8 +32,48 @@ def columns_of_rank(ncolumns: int, world: int, rank: int) -> List[int]:
     return list(range(rank, ncolumns, world))
 
 
+def pack_time_dep(problems, active, prevTimePops):
+    """What lwhip_batch_time_dep_update takes as nOld: per ACTIVE column one contiguous array holding the [Nlevel, Nspace]
+    blocks of its solved atoms back to back in atom order (prevTimePops[i]: one array per solved atom of column i), and
+    NULL for the others.  Returns (the [n] pointer array, the arrays it points to, None for inactive columns)."""
+    import ctypes as C
+    import numpy as np
+    n = len(problems)
+    keep = [None] * n
+    ptrs = (abi.f64p * n)()
+    for i in active:
+        solved = [a for a in problems[i].atoms if not a.detailed]
+        prev = prevTimePops[i]
+        if prev is None or len(prev) != len(solved):
+            raise ValueError('time_dep_update: column %d needs one array per solved atom' % i)
+        blocks = []
+        for a, p in zip(solved, prev):
+            p = np.asarray(p, dtype=np.float64)
+            if p.shape != (a.Nlevel, problems[i].Nspace):
+                raise ValueError('time_dep_update: column %d: prevTimePops of %s must be [Nlevel, Nspace]' % (i, a.name))
+            blocks.append(p.reshape(-1))
+        keep[i] = np.ascontiguousarray(np.concatenate(blocks)) if blocks else np.zeros(1)
+        ptrs[i] = keep[i].ctypes.data_as(abi.f64p)
+    return ptrs, keep
+
+
+def pack_nr_args(n, active, atoms, stages, backgroundNe, ne, dC=None, nPrev=None, dt=0.0, crsw=1.0):
+    """What lwhip_batch_nr_post_update takes as perColumn: [n] lwhip_nr_args, those of the ACTIVE columns filled by
+    _abi.make_nr_args (shared `atoms` and `stages`; backgroundNe, ne, dC, nPrev one entry per column; crsw a scalar or one
+    value per column), the others zeroed.  Returns (the array, what it points to)."""
+    arr = (abi.lwhip_nr_args * n)()
+    keep = [None] * n
+    per = lambda a, i: None if a is None else a[i]  # noqa: E731
+    for i in active:
+        cr = crsw[i] if isinstance(crsw, (list, tuple)) else crsw
+        args, k = abi.make_nr_args(atoms, stages, backgroundNe[i], ne[i], dC=per(dC, i), nPrev=per(nPrev, i), dt=dt, crsw=cr)
+        arr[i] = args
+        keep[i] = (args, k)
+    return arr, keep
+
+
 class ColumnBatch:
-    _ng = None          # (Norder, Nperiod, Ndelay) in effect, Ndelay after the max rule -- configure_ng; None: no Ng acceleration
+    _ng = None         # (Norder, Nperiod, Ndelay) in effect, Ndelay after the max rule -- configure_ng; None: no Ng acceleration
 
     def __init__(self, problems: Sequence[Problem], device: int = 0, stream: Optional[int] = None,
                  device_profiles: bool = True, streams: Optional[Sequence[int]] = None, fused: bool = True):
@@ -304,6 +344,85 @@ class ColumnBatch:
             ups[i] = IterationUpdate(updatedPops=True, dPops=dPops[i, :nAct].tolist(), dPopsMaxIdx=dIdx[i, :nAct].tolist(),
                                      ngAccelerated=bool(acc[i]))
         return ups
+
+    # -- time-dependent and charge-conserving updates: every active column in one launch -------------------------------------
+    def _solved(self):
+        return [ia for ia, a in enumerate(self.problems[0].atoms) if not a.detailed]
+
+    def _pops_reports(self, atoms, run):
+        """One IterationUpdate per column (None for inactive ones) from run(dPops [n, Nsolved], dIdx [n, Nsolved]), which
+        fills the rows of the active columns; `atoms`: the atoms the call updated, whose entries are reported."""
+        import numpy as np
+        from .context import IterationUpdate
+        n, solved = len(self.contexts), self._solved()
+        dPops = np.zeros((n, max(len(solved), 1)))
+        dIdx = np.zeros((n, max(len(solved), 1)), dtype=np.int32)
+        run(dPops, dIdx)
+        pos = [solved.index(ia) for ia in atoms]
+        ups = [None] * n
+        for i in self.active:
+            ups[i] = IterationUpdate(updatedPops=True, dPops=[float(dPops[i, q]) for q in pos],
+                                     dPopsMaxIdx=[int(dIdx[i, q]) for q in pos])
+        return ups
+
+    def _unfused_pops(self, atoms, update):
+        """The per-column route of time_dep_update / nr_post_update: update(i, context) on every active column's own Context,
+        reported by _rel_diff_pops of downloads taken before and after."""
+        import numpy as np
+        ups = [None] * len(self.contexts)
+        for i in self.active:
+            c = self.contexts[i]
+            c.download(abi.POPS)
+            before = [np.array(c.prob.atoms[ia].n, dtype=np.float64, copy=True) for ia in atoms]
+            update(i, c)
+            c.download(abi.POPS)
+            ups[i] = c._rel_diff_pops(atoms, before)
+        return ups
+
+    def time_dep_update(self, dt, prevTimePops):
+        """Context.time_dep_update(dt, prevTimePops[i], deviceResident=True) of every active column: dt a scalar or one value
+        per column, prevTimePops[i] the list of [Nlevel, Nspace] arrays of column i's solved atoms (entries of inactive
+        columns may be None).  Fused: lwhip_batch_time_dep_update -- one launch for all columns and atoms, the columns' changes
+        combined on the device.  Returns one IterationUpdate(updatedPops=True, dPops, dPopsMaxIdx) per column (rel_diff_pops of
+        the reference: the change against the populations before the call), None for an inactive column."""
+        import numpy as np
+        n = len(self.contexts)
+        if self._active is not None and not self._active:
+            return [None] * n
+        dts = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, dtype=np.float64), (n,)))
+        solved = self._solved()
+        if self._batch is None:
+            return self._unfused_pops(solved, lambda i, c: c.time_dep_update(float(dts[i]), prevTimePops[i], deviceResident=True))
+        if not solved:
+            return self._pops_reports([], lambda dP, dI: None)
+        ptrs, keep = pack_time_dep(self.problems, self.active, prevTimePops)
+        lib = self.contexts[0].lib
+        return self._pops_reports(solved, lambda dP, dI: _check(
+            lib, lib.lwhip_batch_time_dep_update(self._batch, ptrs, dts.ctypes.data_as(abi.f64p), dP.ctypes.data_as(abi.f64p),
+                                                 dI.ctypes.data_as(abi.i32p)), 'lwhip_batch_time_dep_update'))
+
+    def nr_post_update(self, stages, backgroundNe, ne, dC=None, nPrev=None, dt=0.0, atoms=None):
+        """Context.nr_post_update(..., deviceResident=True) of every active column: `stages` and `atoms` are shared,
+        backgroundNe, ne, dC and nPrev are lists with one entry per column (those of inactive columns may be None); ne[i] is
+        updated in place.  Fused: lwhip_batch_nr_post_update.  Returns one IterationUpdate(updatedPops=True, dPops,
+        dPopsMaxIdx) per column with one entry per listed atom, None for an inactive column."""
+        n = len(self.contexts)
+        if self._active is not None and not self._active:
+            return [None] * n
+        if atoms is None:
+            atoms = self._solved()
+        atoms = [int(ia) for ia in atoms]
+        per = lambda a, i: None if a is None else a[i]  # noqa: E731
+        if self._batch is None:
+            return self._unfused_pops(atoms, lambda i, c: c.nr_post_update(stages, backgroundNe[i], ne[i], dC=per(dC, i),
+                                                                           nPrev=per(nPrev, i), dt=dt, atoms=atoms,
+                                                                           deviceResident=True))
+        arr, keep = pack_nr_args(n, self.active, atoms, stages, backgroundNe, ne, dC=dC, nPrev=nPrev, dt=dt,
+                                 crsw=[c.crsw for c in self.contexts])
+        lib = self.contexts[0].lib
+        return self._pops_reports(atoms, lambda dP, dI: _check(
+            lib, lib.lwhip_batch_nr_post_update(self._batch, arr, dP.ctypes.data_as(abi.f64p), dI.ctypes.data_as(abi.i32p)),
+            'lwhip_batch_nr_post_update'))
 
     # -- the active set: the columns formal_sol_gamma_matrices and stat_equil advance ---------------------------------------
     @property

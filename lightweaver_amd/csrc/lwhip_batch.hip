@@ -143,6 +143,35 @@ static int batch_solve(lwhip_batch* b, bool report, const char* what, double* dP
     return LWHIP_OK;
 }
 
+// lwhip_batch_time_dep_update / lwhip_batch_nr_post_update: room for what a call sends, in the pinned stage and on the device
+// (both regrown, after a stream wait, when a request is larger; a call ends with a stream wait, so the stage is free here)
+static int pop_stage(lwhip_batch* b, size_t bytes, unsigned char*& stage)
+{
+    lwhip_context* c0 = b->ctxs[0];
+    if (b->popIn.n < bytes)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        HIP_TRY(b->popIn.alloc(c0->mem, bytes, false));
+    }
+    HIP_TRY(b->popStage.reserve(c0->device, bytes, c0->stream));
+    stage = b->popStage.host;
+    return LWHIP_OK;
+}
+
+// ... and what comes before their launch: every active column's pending Gamma pre-fill, its status word cleared
+static int pop_begin(lwhip_batch* b)
+{
+    for (const int32_t i : b->act)
+    {
+        lwhip_context* c = b->ctxs[i];
+        const int stp = flush_prefill(c);
+        if (stp != LWHIP_OK)
+            return stp;
+        *c->statusHost = 0;
+    }
+    return LWHIP_OK;
+}
+
 namespace lwhip
 {
 int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols)
@@ -269,6 +298,7 @@ void lwhip_batch_destroy(lwhip_batch* b)
         (void)hipSetDevice(b->ctxs[0]->device);
         (void)hipStreamSynchronize(b->ctxs[0]->stream);
         b->tailPinned.release();
+        b->popStage.release();
         stokes_batch_release(b->stokes);
         b->stokes = nullptr;
         rays_release(b->rays);
@@ -382,6 +412,262 @@ int lwhip_batch_stat_equil_report(lwhip_batch* b, double* dPops, int32_t* dPopsM
 {
     const char* what = "batch_stat_equil_report: null argument";
     return dPops ? batch_solve(b, true, what, dPops, dPopsMaxIdx) : fail(LWHIP_ERR_INVALID, what);
+}
+
+int lwhip_batch_time_dep_update(lwhip_batch* b, const double* const* nOld, const double* dt, double* dPops, int32_t* dPopsMaxIdx)
+{
+    lwhip_context* c0 = nullptr;
+    if (const int st = batch_enter(b, "batch_time_dep_update: null batch", c0); st != LWHIP_OK)
+        return st;
+    if (!nOld || !dt)
+        return fail(LWHIP_ERR_INVALID, "batch_time_dep_update: null argument");
+    const int Na = b->se0.Natoms, nAct = (int)b->act.size();
+    if (Na <= 0)
+        return LWHIP_OK;
+    for (const int32_t i : b->act)
+        if (!nOld[i])
+            return fail(LWHIP_ERR_INVALID, "batch_time_dep_update: column " + std::to_string(i) + " has no nOld");
+    const size_t Ns = (size_t)c0->Ns;
+    size_t rows = 0; // of nOld, per column: the solved atoms' levels
+    for (int ia = 0; ia < c0->Natom; ++ia)
+        if (!c0->atoms[ia].detailed)
+            rows += (size_t)c0->atoms[ia].Nlevel;
+    const size_t per = rows * Ns, oldOff = (size_t)nAct * sizeof(TimeDepArgs);
+    unsigned char* stage = nullptr;
+    if (const int st = pop_stage(b, oldOff + (size_t)nAct * per * sizeof(double), stage); st != LWHIP_OK)
+        return st;
+    TimeDepArgs* args = (TimeDepArgs*)stage;
+    for (int p = 0; p < nAct; ++p)
+    {
+        const int32_t i = b->act[p];
+        lwhip_context* c = b->ctxs[i];
+        TimeDepArgs& a = args[p];
+        a.Ns = c->Ns;
+        a.Natoms = Na;
+        a.atoms = b->se.full[i].atoms;
+        a.n = c->n.p;
+        a.Gamma = c->Gamma.p;
+        a.nOld = (const double*)(b->popIn.p + oldOff) + (size_t)p * per;
+        a.dt = dt[i];
+        a.status = c->statusDev;
+        a.change = b->change.p + (size_t)i * Na * b->seBlocks * 2;
+        std::memcpy(stage + oldOff + (size_t)p * per * sizeof(double), nOld[i], per * sizeof(double));
+    }
+    if (const int st = pop_begin(b); st != LWHIP_OK)
+        return st;
+    HIP_TRY(hipMemcpyAsync(b->popIn.p, stage, oldOff + (size_t)nAct * per * sizeof(double), hipMemcpyHostToDevice, c0->stream));
+    HIP_TRY(launch_time_dep_list((const TimeDepArgs*)b->popIn.p, c0->Ns, Na, b->seMaxNl, nAct, c0->stream));
+    BatchConvArgs ca{};
+    ca.tail = b->tail.p;
+    ca.rec = b->rec.p;
+    ca.cols = batch_cols(b);
+    ca.Natoms = Na;
+    ca.change = b->change.p;
+    ca.nBlocks = b->seBlocks;
+    HIP_TRY(launch_batch_conv(ca, nAct, c0->stream));
+    const size_t stride = 2 + 2 * (size_t)Na;
+    HIP_TRY(hipMemcpyAsync(b->recPinned.host, b->rec.p, b->ctxs.size() * stride * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    b->recCols = b->act;
+    if (const int st = batch_singular(b); st != LWHIP_OK)
+        return st;
+    const double* rec = b->recPinned.as<double>();
+    for (const int32_t i : b->act)
+        for (int q = 0; q < Na; ++q)
+        {
+            if (dPops)
+                dPops[(size_t)i * Na + q] = rec[i * stride + 2 + 2 * q];
+            if (dPopsMaxIdx)
+                dPopsMaxIdx[(size_t)i * Na + q] = (int32_t)rec[i * stride + 3 + 2 * q];
+        }
+    return LWHIP_OK;
+}
+
+int lwhip_batch_nr_post_update(lwhip_batch* b, const lwhip_nr_args* perColumn, double* dPops, int32_t* dPopsMaxIdx)
+{
+    lwhip_context* c0 = nullptr;
+    if (const int st = batch_enter(b, "batch_nr_post_update: null batch", c0); st != LWHIP_OK)
+        return st;
+    if (!perColumn)
+        return fail(LWHIP_ERR_INVALID, "batch_nr_post_update: null argument");
+    const int Na = b->se0.Natoms, nAct = (int)b->act.size(), n = (int)b->ctxs.size();
+    const size_t Ns = (size_t)c0->Ns;
+    // ---- every refusal, before anything is queued: the first active column's list, then every column against it ----
+    const lwhip_nr_args& f = perColumn[b->act[0]];
+    const std::string what = "batch_nr_post_update: column ";
+    if (!f.atoms || f.Natoms <= 0)
+        return fail(LWHIP_ERR_INVALID, what + std::to_string(b->act[0]) + " lists no atoms");
+    const int Nl = f.Natoms;
+    std::vector<NrAtom> atoms(Nl);
+    std::vector<int32_t> slots(Nl);
+    int eq = 0;
+    int64_t dcRows = 0;
+    for (int q = 0; q < Nl; ++q)
+    {
+        const int ia = f.atoms[q];
+        if (ia < 0 || ia >= c0->Natom || c0->atoms[ia].detailed)
+            return fail(LWHIP_ERR_INVALID, "batch_nr_post_update: not an active atom");
+        NrAtom& at = atoms[q];
+        at.atom = ia;
+        at.Nlevel = c0->atoms[ia].Nlevel;
+        at.levelOff = c0->levelOff[ia];
+        at.eqOff = eq;
+        at.trBegin = c0->atomTrOff[ia];
+        at.trEnd = c0->atomTrOff[ia + 1];
+        at.gammaOff = c0->gammaOff[ia];
+        at.dcOff = dcRows;
+        eq += at.Nlevel;
+        dcRows += (int64_t)at.Nlevel * at.Nlevel;
+        slots[q] = 0; // its position among the solved atoms
+        for (int ib = 0; ib < ia; ++ib)
+            slots[q] += c0->atoms[ib].detailed ? 0 : 1;
+    }
+    const bool timeDep = f.nPrev != nullptr, fdC = f.dC != nullptr;
+    for (const int32_t i : b->act)
+    {
+        const lwhip_nr_args& g = perColumn[i];
+        const lwhip_context* c = b->ctxs[i];
+        const std::string col = what + std::to_string(i);
+        if (!g.atoms || !g.stages || !g.ne || !g.backgroundNe)
+            return fail(LWHIP_ERR_INVALID, col + ": null atoms, stages, ne or backgroundNe");
+        if (g.Natoms != Nl || !std::equal(g.atoms, g.atoms + Nl, f.atoms) || (g.nPrev != nullptr) != timeDep || (g.dC != nullptr) != fdC)
+            return fail(LWHIP_ERR_INVALID, col + " differs from the first active column in its atom list or in the presence of dC / nPrev");
+        for (int q = 0; q < Nl; ++q)
+        {
+            const NrAtom& at = atoms[q];
+            if (!c->atoms[at.atom].C)
+                return fail(LWHIP_ERR_INVALID, col + ": nr_post_update needs the collisional rates C of every listed atom");
+            if (c->atoms[at.atom].Nlevel != at.Nlevel || c->levelOff[at.atom] != at.levelOff || c->gammaOff[at.atom] != at.gammaOff
+                || c->atomTrOff[at.atom] != at.trBegin || c->atomTrOff[at.atom + 1] != at.trEnd)
+                return fail(LWHIP_ERR_INVALID, col + ": the listed atoms are not laid out as the first column's");
+            if (!g.stages[q] || (timeDep && !g.nPrev[q]) || (fdC && !g.dC[q]))
+                return fail(LWHIP_ERR_INVALID, col + ": null stages, nPrev or dC of a listed atom");
+        }
+    }
+    const int Neqn = eq + 1;
+    if (Neqn > 64)
+        return fail(LWHIP_ERR_UNSUPPORTED, "batch_nr_post_update: more than 63 coupled levels");
+    // ---- the call's block: argument blocks | atoms | slots | stages | records | ne | backgroundNe | nPrev | dC ----
+    const size_t stride = 2 + 2 * (size_t)Na, D = sizeof(double);
+    const size_t atomsOff = (size_t)nAct * sizeof(NrListArgs);
+    const size_t slotsOff = atomsOff + (size_t)Nl * sizeof(NrAtom);
+    const size_t stagesOff = slotsOff + (((size_t)Nl * sizeof(int32_t) + 7) & ~(size_t)7);
+    const size_t recOff = stagesOff + (size_t)nAct * eq * D;
+    const size_t neOff = recOff + (size_t)n * stride * D;
+    const size_t bgOff = neOff + (size_t)nAct * Ns * D;
+    const size_t prevOff = bgOff + (size_t)nAct * Ns * D;
+    const size_t dcOff = prevOff + (timeDep ? (size_t)nAct * eq * Ns * D : 0);
+    const size_t total = dcOff + (fdC ? (size_t)nAct * dcRows * Ns * D : 0);
+    unsigned char* stage = nullptr;
+    if (const int st = pop_stage(b, total, stage); st != LWHIP_OK)
+        return st;
+    // the change records: one set of pairs per column, solved atom and block; the slots of atoms not listed stay zero
+    const int nrBlocks = nr_post_blocks(c0->Ns, Neqn);
+    if (b->nrBlocks != nrBlocks || !b->nrChange.p)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        HIP_TRY(b->nrChange.alloc_zero(c0->mem, (size_t)n * Na * nrBlocks * 2));
+        b->nrBlocks = nrBlocks;
+        b->nrListed = slots;
+    }
+    if (c0->transType.n < (size_t)std::max(c0->Ntrans, 1))
+    {
+        std::vector<int32_t> tt((size_t)std::max(c0->Ntrans, 1), 0);
+        for (int tr = 0; tr < c0->Ntrans; ++tr)
+            tt[tr] = c0->trans[tr].t.type;
+        HIP_TRY(c0->transType.upload(c0->mem, tt));
+    }
+    unsigned char* dev = b->popIn.p;
+    std::memcpy(stage + atomsOff, atoms.data(), (size_t)Nl * sizeof(NrAtom));
+    std::memcpy(stage + slotsOff, slots.data(), (size_t)Nl * sizeof(int32_t));
+    NrListArgs* args = (NrListArgs*)stage;
+    for (int p = 0; p < nAct; ++p)
+    {
+        const int32_t i = b->act[p];
+        lwhip_context* c = b->ctxs[i];
+        const lwhip_nr_args& g = perColumn[i];
+        double* hStages = (double*)(stage + stagesOff) + (size_t)p * eq;
+        double* hPrev = (double*)(stage + prevOff) + (size_t)p * eq * Ns;
+        double* hDC = (double*)(stage + dcOff) + (size_t)p * dcRows * Ns;
+        for (int q = 0; q < Nl; ++q)
+        {
+            const NrAtom& at = atoms[q];
+            std::memcpy(hStages + at.eqOff, g.stages[q], (size_t)at.Nlevel * D);
+            if (timeDep)
+                std::memcpy(hPrev + (size_t)at.eqOff * Ns, g.nPrev[q], (size_t)at.Nlevel * Ns * D);
+            if (fdC)
+                std::memcpy(hDC + (size_t)at.dcOff * Ns, g.dC[q], (size_t)at.Nlevel * at.Nlevel * Ns * D);
+        }
+        std::memcpy(stage + neOff + (size_t)p * Ns * D, g.ne, Ns * D);
+        std::memcpy(stage + bgOff + (size_t)p * Ns * D, g.backgroundNe, Ns * D);
+        NrListArgs& l = args[p];
+        NrArgs& a = l.a;
+        a = NrArgs{};
+        a.Ns = (int32_t)Ns;
+        a.Natoms = Nl;
+        a.Neqn = Neqn;
+        a.timeDep = timeDep ? 1 : 0;
+        a.atoms = (const NrAtom*)(dev + atomsOff);
+        a.Gamma = c->Gamma.p;
+        a.Cmat = c->Cmat.p;
+        a.n = c->n.p;
+        a.nTotal = c->nTotal.p;
+        a.stages = (const double*)(dev + stagesOff) + (size_t)p * eq;
+        a.nPrev = timeDep ? (const double*)(dev + prevOff) + (size_t)p * eq * Ns : nullptr;
+        a.dC = fdC ? (const double*)(dev + dcOff) + (size_t)p * dcRows * Ns : nullptr;
+        a.backgroundNe = (const double*)(dev + bgOff) + (size_t)p * Ns;
+        a.ne = (double*)(dev + neOff) + (size_t)p * Ns;
+        a.transType = c0->transType.p;
+        a.transLi = c->transLi.p;
+        a.transLj = c->transLj.p;
+        a.dt = g.dt;
+        a.crsw = g.crsw;
+        a.status = c->statusDev;
+        a.k0 = 0;
+        a.k1 = (int32_t)Ns;
+        l.change = b->nrChange.p + (size_t)i * Na * nrBlocks * 2;
+        l.slots = (const int32_t*)(dev + slotsOff);
+    }
+    if (const int st = pop_begin(b); st != LWHIP_OK)
+        return st;
+    if (b->nrListed != slots) // (rare: another atom list than the last call's -- what it left in other slots goes)
+    {
+        HIP_TRY(hipMemsetAsync(b->nrChange.p, 0, b->nrChange.n * sizeof(double), c0->stream));
+        b->nrListed = slots;
+    }
+    HIP_TRY(hipMemcpyAsync(dev, stage, total, hipMemcpyHostToDevice, c0->stream));
+    HIP_TRY(launch_nr_post(args[0].a, c0->stream, (const NrListArgs*)dev, nAct));
+    BatchConvArgs ca{};
+    ca.tail = b->tail.p;
+    ca.rec = (double*)(dev + recOff);
+    ca.cols = batch_cols(b);
+    ca.Natoms = Na;
+    ca.change = b->nrChange.p;
+    ca.nBlocks = nrBlocks;
+    HIP_TRY(launch_batch_conv(ca, nAct, c0->stream));
+    // records and ne lie together: one copy back, one wait
+    HIP_TRY(hipMemcpyAsync(stage + recOff, dev + recOff, bgOff - recOff, hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    const double* rec = (const double*)(stage + recOff);
+    double* recOut = b->recPinned.as<double>();
+    for (int p = 0; p < nAct; ++p)
+    {
+        const int32_t i = b->act[p];
+        std::memcpy(perColumn[i].ne, stage + neOff + (size_t)p * Ns * D, Ns * D);
+        std::memcpy(recOut + i * stride, rec + i * stride, stride * D);
+    }
+    b->recCols = b->act;
+    if (const int st = batch_singular(b); st != LWHIP_OK)
+        return st;
+    for (const int32_t i : b->act)
+        for (int q = 0; q < Nl; ++q)
+        {
+            if (dPops)
+                dPops[(size_t)i * Na + slots[q]] = rec[i * stride + 2 + 2 * slots[q]];
+            if (dPopsMaxIdx)
+                dPopsMaxIdx[(size_t)i * Na + slots[q]] = (int32_t)rec[i * stride + 3 + 2 * slots[q]];
+        }
+    return LWHIP_OK;
 }
 
 int lwhip_batch_conv_records(lwhip_batch* b, double* records, int* strideOut)

@@ -944,6 +944,13 @@ struct lwhip_batch
     DevBuf<double> rec;                  // [n][2 + 2 Natoms]: dJMax, idx, then (dPops, idx) per atom
     PinnedBlock recPinned;
     std::vector<int32_t> recCols;        // the columns the last report solved (whose rows of recPinned are its)
+    // lwhip_batch_time_dep_update / lwhip_batch_nr_post_update: everything a call sends -- the active columns' argument blocks
+    // in list order, then their arrays -- is staged in ONE pinned block and goes up in one copy
+    PinnedBlock popStage;
+    DevBuf<unsigned char> popIn;         // ... its landing place, laid out as the stage
+    int nrBlocks = 0;                    // Newton-Raphson blocks per column (the block size follows Neqn, not seMaxNl)
+    DevBuf<double> nrChange;             // [n][Natoms][nrBlocks][2]; zero in the slots of solved atoms the call does not list
+    std::vector<int32_t> nrListed;       // the atom list those zeros are right for
     NgState ng;                                // lwhip_batch_ng_configure: Ng acceleration of every column
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments

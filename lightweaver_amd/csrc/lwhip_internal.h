@@ -798,9 +798,31 @@ struct NgArgs
 size_t ng_lds_bytes(int Norder);
 hipError_t launch_ng(const NgArgs& a, int nActive, hipStream_t stream);
 hipError_t launch_ng_seed(const NgArgs& a, int n, hipStream_t stream); // slot 0 <- n, count <- 1, for ALL columns
-hipError_t launch_nr_post(const NrArgs& a, hipStream_t stream);
+// column batches: one column's Newton-Raphson step -- its NrArgs, and where it reports the change of what it updates
+struct NrListArgs
+{
+    NrArgs a;
+    double* change;         // the column's [slots][nr_post_blocks][2] pairs (value, flattened [level, depth] index)
+    const int32_t* slots;   // [a.Natoms]: listed atom q reports into slot slots[q], its position among the solved atoms
+};
+// list / nBatch: column batches -- a device array of per-column argument blocks, one grid slice per column (a: any one of them)
+hipError_t launch_nr_post(const NrArgs& a, hipStream_t stream, const NrListArgs* list = nullptr, int nBatch = 0);
+int nr_post_blocks(int Ns, int Neqn);   // blocks per column (the block size follows Neqn)
 hipError_t launch_time_dep(int Nlevel, int Ns, int k0, int k1, double* n, const double* nOld, const double* Gamma, double dt,
                            int* status, hipStream_t stream);
+// column batches: the time-dependent update of every solved atom of one column, at every depth
+struct TimeDepArgs
+{
+    int32_t Ns, Natoms;
+    const NrAtom* atoms;    // the solved atoms (Nlevel, levelOff, gammaOff used), as StatEqArgs::atoms
+    double* n;              // pool
+    const double* Gamma;    // pool
+    const double* nOld;     // the solved atoms' [Nlevel, Ns] blocks back to back in atom order
+    double dt;
+    int32_t* status;        // host-mapped, as StatEqArgs::status
+    double* change;         // the column's [Natoms][stat_eq_blocks][2] pairs, or null
+};
+hipError_t launch_time_dep_list(const TimeDepArgs* list, int Ns, int Natoms, int maxNlevel, int nBatch, hipStream_t stream);
 
 // launch helpers implemented in lwhip_kernels.hip
 // list / nBatch: column batches -- a device array of per-column argument blocks, one grid slice per column

@@ -432,8 +432,13 @@ hipError_t launch_batch_conv(const BatchConvArgs& a, int nActive, hipStream_t st
 }
 
 // ---- time_dependent_update_impl: Source/UpdatePopulations.cpp:120-151 --------------------------------------
+// The per-point code below is shared by the lone kernels and the column-batch ones.  The batched kernels report the change of
+// what they update (report_change: a barrier), so nothing in these bodies returns early: a thread outside the depth range, or
+// whose system is singular, skips its work by predicate and contributes best = 0, bestIdx = 0x7fffffff; every thread of a block
+// reaches every barrier.  `old` is read just before n is overwritten: no second copy of the populations.
 template <int N>
-DEVINL bool time_dep_point_reg(double* n, const double* nOld, const double* Gamma, const double dt, const int Ns, const int k)
+DEVINL bool time_dep_point_reg(double* n, const double* nOld, const double* Gamma, const double dt, const int Ns, const int k,
+                               double& best, int& bestIdx)
 {
     double A[N][N], b[N];
 #pragma unroll
@@ -451,48 +456,100 @@ DEVINL bool time_dep_point_reg(double* n, const double* nOld, const double* Gamm
         return false;
 #pragma unroll
     for (int i = 0; i < N; ++i)
-        n[(size_t)i * Ns + k] = b[i];
+    {
+        const double cur = b[i];
+        const double old = n[(size_t)i * Ns + k];
+        n[(size_t)i * Ns + k] = cur;
+        if (cur != 0.0)
+        {
+            const double change = fabs((cur - old) / cur);
+            if (change > best)
+            {
+                best = change;
+                bestIdx = i * Ns + k;
+            }
+        }
+    }
     return true;
 }
 
-__global__ void __launch_bounds__(64) time_dep_kernel(int N, int Ns, int k0, int k1, double* n, const double* nOld, const double* Gamma,
-                                double dt, int* status)
+// one atom of N levels: n, nOld, Gamma are the atom's own; change: its [gridDim.x][2] pairs, or null (then no barrier is met)
+DEVINL void time_dep_body(const int N, const int Ns, const int k0, const int k1, double* n, const double* nOld, const double* Gamma,
+                          const double dt, int* status, double* change)
 {
-    dbg_poison_lds();
     extern __shared__ double lds[];
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < k0 || k >= k1)
-        return;
-    if (N >= 2 && N <= SOLVE_REG_MAXN)
+    const bool inRange = k >= k0 && k < k1;
+    double best = 0.0;
+    int bestIdx = 0x7fffffff;
+    if (inRange && N >= 2 && N <= SOLVE_REG_MAXN)
     {
         bool ok = true;
         switch (N)
         {
-        case 2: ok = time_dep_point_reg<2>(n, nOld, Gamma, dt, Ns, k); break;
-        case 3: ok = time_dep_point_reg<3>(n, nOld, Gamma, dt, Ns, k); break;
-        case 4: ok = time_dep_point_reg<4>(n, nOld, Gamma, dt, Ns, k); break;
-        case 5: ok = time_dep_point_reg<5>(n, nOld, Gamma, dt, Ns, k); break;
-        default: ok = time_dep_point_reg<6>(n, nOld, Gamma, dt, Ns, k); break;
+        case 2: ok = time_dep_point_reg<2>(n, nOld, Gamma, dt, Ns, k, best, bestIdx); break;
+        case 3: ok = time_dep_point_reg<3>(n, nOld, Gamma, dt, Ns, k, best, bestIdx); break;
+        case 4: ok = time_dep_point_reg<4>(n, nOld, Gamma, dt, Ns, k, best, bestIdx); break;
+        case 5: ok = time_dep_point_reg<5>(n, nOld, Gamma, dt, Ns, k, best, bestIdx); break;
+        default: ok = time_dep_point_reg<6>(n, nOld, Gamma, dt, Ns, k, best, bestIdx); break;
         }
         if (!ok)
             atomicExch(status, LWHIP_ERR_SINGULAR);
-        return;
     }
-    const SolveWs w(lds, N, blockDim.x, threadIdx.x);
-    for (int i = 0; i < N; ++i)
+    else if (inRange)
     {
-        w.b[i] = nOld[(size_t)i * Ns + k];
-        for (int j = 0; j < N; ++j)
-            w.A[i * N + j] = -Gamma[((size_t)i * N + j) * Ns + k] * dt;
-        w.A[i * N + i] = 1.0 - Gamma[((size_t)i * N + i) * Ns + k] * dt;
+        const SolveWs w(lds, N, blockDim.x, threadIdx.x);
+        for (int i = 0; i < N; ++i)
+        {
+            w.b[i] = nOld[(size_t)i * Ns + k];
+            for (int j = 0; j < N; ++j)
+                w.A[i * N + j] = -Gamma[((size_t)i * N + j) * Ns + k] * dt;
+            w.A[i * N + i] = 1.0 - Gamma[((size_t)i * N + i) * Ns + k] * dt;
+        }
+        if (!d_solve_lin_eq(N, w))
+            atomicExch(status, LWHIP_ERR_SINGULAR);
+        else
+        {
+            for (int i = 0; i < N; ++i)
+            {
+                const double cur = w.b[i];
+                const double old = n[(size_t)i * Ns + k];
+                n[(size_t)i * Ns + k] = cur;
+                if (cur != 0.0)
+                {
+                    const double change1 = fabs((cur - old) / cur);
+                    if (change1 > best)
+                    {
+                        best = change1;
+                        bestIdx = i * Ns + k;
+                    }
+                }
+            }
+        }
     }
-    if (!d_solve_lin_eq(N, w))
+    report_change(best, bestIdx, change);
+}
+
+// BATCH: column batches -- blockIdx.z picks the column's argument block (read through the constant address space), blockIdx.y
+// the solved atom, so all solved atoms of all active columns go in one launch; every depth point is solved.  The atom's rows
+// of nOld follow those of the atoms before it.  The lone form is launched once per atom.
+template <bool BATCH>
+__global__ void __launch_bounds__(64) time_dep_kernel(int N, int Ns, int k0, int k1, double* n, const double* nOld, const double* Gamma,
+                                                      double dt, int* status, const TimeDepArgs* __restrict__ list)
+{
+    dbg_poison_lds();
+    if constexpr (BATCH)
     {
-        atomicExch(status, LWHIP_ERR_SINGULAR);
-        return;
+        const TimeDepArgs a = ld_c(CTAB(TimeDepArgs, list) + blockIdx.z);
+        int rows = 0;
+        for (int q = 0; q < (int)blockIdx.y; ++q)
+            rows += a.atoms[q].Nlevel;
+        const NrAtom at = a.atoms[blockIdx.y];
+        time_dep_body(at.Nlevel, a.Ns, 0, a.Ns, a.n + (size_t)at.levelOff * a.Ns, a.nOld + (size_t)rows * a.Ns, a.Gamma + at.gammaOff, a.dt,
+                      a.status, a.change ? a.change + (size_t)blockIdx.y * 2 * gridDim.x : nullptr);
     }
-    for (int i = 0; i < N; ++i)
-        n[(size_t)i * Ns + k] = w.b[i];
+    else
+        time_dep_body(N, Ns, k0, k1, n, nOld, Gamma, dt, status, nullptr);
 }
 
 hipError_t launch_time_dep(int Nlevel, int Ns, int k0, int k1, double* n, const double* nOld, const double* Gamma,
@@ -502,146 +559,214 @@ hipError_t launch_time_dep(int Nlevel, int Ns, int k0, int k1, double* n, const 
         return hipErrorInvalidValue;
     const int tb = solve_block_threads(Nlevel);
     const size_t lds = solve_ws_doubles(Nlevel) * sizeof(double) * tb;
-    hipError_t e = solve_set_lds((const void*)time_dep_kernel, lds);
+    hipError_t e = solve_set_lds((const void*)time_dep_kernel<false>, lds);
     if (e != hipSuccess)
         return e;
-    LWHIP_LAUNCH(time_dep_kernel, dim3((Ns + tb - 1) / tb), dim3(tb), lds, stream, Nlevel, Ns, k0, k1, n, nOld, Gamma,
-                       dt, status);
+    LWHIP_LAUNCH(time_dep_kernel<false>, dim3((Ns + tb - 1) / tb), dim3(tb), lds, stream, Nlevel, Ns, k0, k1, n, nOld, Gamma,
+                       dt, status, (const TimeDepArgs*)nullptr);
+    return hipGetLastError();
+}
+
+// all solved atoms of nBatch columns: block size and LDS from the largest atom, as launch_stat_eq (so stat_eq_blocks counts
+// the blocks per atom)
+hipError_t launch_time_dep_list(const TimeDepArgs* list, int Ns, int Natoms, int maxNlevel, int nBatch, hipStream_t stream)
+{
+    if (maxNlevel > 64 || Natoms <= 0 || nBatch < 1 || !list)
+        return hipErrorInvalidValue;
+    const int tb = solve_block_threads(maxNlevel);
+    const size_t lds = solve_ws_doubles(maxNlevel) * sizeof(double) * tb;
+    hipError_t e = solve_set_lds((const void*)time_dep_kernel<true>, lds);
+    if (e != hipSuccess)
+        return e;
+    LWHIP_LAUNCH(time_dep_kernel<true>, dim3((Ns + tb - 1) / tb, Natoms, nBatch), dim3(tb), lds, stream, 0, 0, 0, 0, (double*)nullptr,
+                       (const double*)nullptr, (const double*)nullptr, 0.0, (int*)nullptr, list);
     return hipGetLastError();
 }
 
 // ---- nr_post_update_impl with F / Ftd: Source/UpdatePopulations.cpp:230-394 --------------------------------
-__global__ void nr_post_kernel(const NrArgs a)
+// change: the column's [slots][gridDim.x][2] pairs (listed atom q reports into slot slots[q]), or null: nothing is reported and
+// no barrier is met.  A point outside the depth range, or whose system is singular, keeps its n and ne.
+DEVINL void nr_post_body(const NrArgs& a, double* change, const int32_t* slots)
 {
-    dbg_poison_lds();
     extern __shared__ double lds[];
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     const int Ns = a.Ns;
-    if (k < a.k0 || k >= a.k1)
-        return;
+    const bool inRange = k >= a.k0 && k < a.k1;
     const int Neqn = a.Neqn;
     const SolveWs w(lds, Neqn, blockDim.x, threadIdx.x);
     const LdsVec& dF = w.A;
     const LdsVec& Fg = w.b;
-    for (int i = 0; i < Neqn; ++i)
+    bool ok = false;
+    double ne = 0.0;
+    if (inRange)
     {
-        Fg[i] = 0.0;
-        for (int j = 0; j < Neqn; ++j)
-            dF[i * Neqn + j] = 0.0;
+        for (int i = 0; i < Neqn; ++i)
+        {
+            Fg[i] = 0.0;
+            for (int j = 0; j < Neqn; ++j)
+                dF[i * Neqn + j] = 0.0;
+        }
+        const double theta = 1.0;
+        ne = a.ne[k];
+        Fg[Neqn - 1] = ne;
+        int start = 0;
+        for (int q = 0; q < a.Natoms; ++q)
+        {
+            const NrAtom at = a.atoms[q];
+            const int Nl = at.Nlevel;
+            const double* G = a.Gamma + at.gammaOff;
+            const double* n = a.n + (size_t)at.levelOff * Ns;
+            // F :230-257 / Ftd :259-292
+            for (int l = 0; l < Nl; ++l)
+            {
+                double v = 0.0;
+                if (a.timeDep)
+                {
+                    for (int ll = 0; ll < Nl; ++ll)
+                        v += G[((size_t)l * Nl + ll) * Ns + k] * n[(size_t)ll * Ns + k];
+                    v *= theta * a.dt;
+                    v -= n[(size_t)l * Ns + k] - a.nPrev[(size_t)(at.eqOff + l) * Ns + k];
+                }
+                else
+                {
+                    for (int ll = 0; ll < Nl; ++ll)
+                        v -= G[((size_t)l * Nl + ll) * Ns + k] * n[(size_t)ll * Ns + k];
+                }
+                Fg[start + l] = v;
+            }
+            double nTotCur = 0.0;
+            for (int ll = 0; ll < Nl; ++ll)
+                nTotCur += n[(size_t)ll * Ns + k];
+            Fg[start + Nl - 1] = nTotCur - a.nTotal[(size_t)at.atom * Ns + k];
+            double eleContrib = 0.0;
+            for (int ll = 0; ll < Nl; ++ll)
+                eleContrib += a.stages[at.eqOff + ll] * n[(size_t)ll * Ns + k];
+            Fg[Neqn - 1] -= eleContrib;
+            // Jacobian :322-372
+            for (int l = 0; l < Nl; ++l)
+                for (int ll = 0; ll < Nl; ++ll)
+                    dF[(start + l) * Neqn + start + ll] = -G[((size_t)l * Nl + ll) * Ns + k];
+            if (a.timeDep)
+            {
+                for (int l = 0; l < Nl; ++l)
+                    for (int ll = 0; ll < Nl; ++ll)
+                        dF[(start + l) * Neqn + start + ll] *= -theta * a.dt;
+                for (int l = 0; l < Nl; ++l)
+                    dF[(start + l) * Neqn + start + l] -= 1.0;
+            }
+            const double* Cm = a.Cmat + at.gammaOff;
+            for (int tr = at.trBegin; tr < at.trEnd; ++tr)
+            {
+                if (a.transType[tr] != LWHIP_CONTINUUM)
+                    continue;
+                const int ti = a.transLi[tr], tj = a.transLj[tr];
+                const double preconRji = G[((size_t)ti * Nl + tj) * Ns + k] - a.crsw * Cm[((size_t)ti * Nl + tj) * Ns + k];
+                double entry = -(preconRji / ne) * n[(size_t)tj * Ns + k];
+                if (a.timeDep)
+                    entry *= -theta * a.dt;
+                dF[(start + ti) * Neqn + Neqn - 1] += entry;
+            }
+            if (a.dC)
+            {
+                const double* dC = a.dC + (size_t)at.dcOff * Ns;
+                for (int i = 0; i < Nl; ++i)
+                {
+                    double entry = 0.0;
+                    for (int ll = 0; ll < Nl; ++ll)
+                        entry -= dC[((size_t)i * Nl + ll) * Ns + k] * n[(size_t)ll * Ns + k];
+                    if (a.timeDep)
+                        entry *= -theta * a.dt;
+                    dF[(start + i) * Neqn + Neqn - 1] += entry;
+                }
+            }
+            for (int c = 0; c < Neqn; ++c)
+                dF[(start + Nl - 1) * Neqn + c] = 0.0;
+            for (int ll = 0; ll < Nl; ++ll)
+            {
+                dF[(start + Nl - 1) * Neqn + start + ll] = 1.0;
+                dF[(Neqn - 1) * Neqn + start + ll] = -a.stages[at.eqOff + ll];
+            }
+            start += Nl;
+        }
+        Fg[Neqn - 1] -= a.backgroundNe[k];
+        dF[(Neqn - 1) * Neqn + Neqn - 1] = 1.0;
+        for (int i = 0; i < Neqn; ++i)
+            Fg[i] *= -1.0;
+        ok = d_solve_lin_eq(Neqn, w);
+        if (!ok)
+            atomicExch(a.status, LWHIP_ERR_SINGULAR);
     }
-    const double theta = 1.0;
-    const double ne = a.ne[k];
-    Fg[Neqn - 1] = ne;
+    // n += delta; per listed atom the change of what this thread wrote.  (The loop bounds are the block's; the thread's own
+    // work hangs on `ok`.  Successive reports reuse report_change's shared arrays: a barrier between them.)
     int start = 0;
     for (int q = 0; q < a.Natoms; ++q)
     {
         const NrAtom at = a.atoms[q];
-        const int Nl = at.Nlevel;
-        const double* G = a.Gamma + at.gammaOff;
-        const double* n = a.n + (size_t)at.levelOff * Ns;
-        // F :230-257 / Ftd :259-292
-        for (int l = 0; l < Nl; ++l)
+        double best = 0.0;
+        int bestIdx = 0x7fffffff;
+        if (ok)
         {
-            double v = 0.0;
-            if (a.timeDep)
+            double* n = a.n + (size_t)at.levelOff * Ns;
+            for (int ll = 0; ll < at.Nlevel; ++ll)
             {
-                for (int ll = 0; ll < Nl; ++ll)
-                    v += G[((size_t)l * Nl + ll) * Ns + k] * n[(size_t)ll * Ns + k];
-                v *= theta * a.dt;
-                v -= n[(size_t)l * Ns + k] - a.nPrev[(size_t)(at.eqOff + l) * Ns + k];
-            }
-            else
-            {
-                for (int ll = 0; ll < Nl; ++ll)
-                    v -= G[((size_t)l * Nl + ll) * Ns + k] * n[(size_t)ll * Ns + k];
-            }
-            Fg[start + l] = v;
-        }
-        double nTotCur = 0.0;
-        for (int ll = 0; ll < Nl; ++ll)
-            nTotCur += n[(size_t)ll * Ns + k];
-        Fg[start + Nl - 1] = nTotCur - a.nTotal[(size_t)at.atom * Ns + k];
-        double eleContrib = 0.0;
-        for (int ll = 0; ll < Nl; ++ll)
-            eleContrib += a.stages[at.eqOff + ll] * n[(size_t)ll * Ns + k];
-        Fg[Neqn - 1] -= eleContrib;
-        // Jacobian :322-372
-        for (int l = 0; l < Nl; ++l)
-            for (int ll = 0; ll < Nl; ++ll)
-                dF[(start + l) * Neqn + start + ll] = -G[((size_t)l * Nl + ll) * Ns + k];
-        if (a.timeDep)
-        {
-            for (int l = 0; l < Nl; ++l)
-                for (int ll = 0; ll < Nl; ++ll)
-                    dF[(start + l) * Neqn + start + ll] *= -theta * a.dt;
-            for (int l = 0; l < Nl; ++l)
-                dF[(start + l) * Neqn + start + l] -= 1.0;
-        }
-        const double* Cm = a.Cmat + at.gammaOff;
-        for (int tr = at.trBegin; tr < at.trEnd; ++tr)
-        {
-            if (a.transType[tr] != LWHIP_CONTINUUM)
-                continue;
-            const int ti = a.transLi[tr], tj = a.transLj[tr];
-            const double preconRji = G[((size_t)ti * Nl + tj) * Ns + k] - a.crsw * Cm[((size_t)ti * Nl + tj) * Ns + k];
-            double entry = -(preconRji / ne) * n[(size_t)tj * Ns + k];
-            if (a.timeDep)
-                entry *= -theta * a.dt;
-            dF[(start + ti) * Neqn + Neqn - 1] += entry;
-        }
-        if (a.dC)
-        {
-            const double* dC = a.dC + (size_t)at.dcOff * Ns;
-            for (int i = 0; i < Nl; ++i)
-            {
-                double entry = 0.0;
-                for (int ll = 0; ll < Nl; ++ll)
-                    entry -= dC[((size_t)i * Nl + ll) * Ns + k] * n[(size_t)ll * Ns + k];
-                if (a.timeDep)
-                    entry *= -theta * a.dt;
-                dF[(start + i) * Neqn + Neqn - 1] += entry;
+                const double old = n[(size_t)ll * Ns + k];
+                const double cur = old + Fg[start + ll];
+                n[(size_t)ll * Ns + k] = cur;
+                if (cur != 0.0)
+                {
+                    const double change1 = fabs((cur - old) / cur);
+                    if (change1 > best)
+                    {
+                        best = change1;
+                        bestIdx = ll * Ns + k;
+                    }
+                }
             }
         }
-        for (int c = 0; c < Neqn; ++c)
-            dF[(start + Nl - 1) * Neqn + c] = 0.0;
-        for (int ll = 0; ll < Nl; ++ll)
-        {
-            dF[(start + Nl - 1) * Neqn + start + ll] = 1.0;
-            dF[(Neqn - 1) * Neqn + start + ll] = -a.stages[at.eqOff + ll];
-        }
-        start += Nl;
-    }
-    Fg[Neqn - 1] -= a.backgroundNe[k];
-    dF[(Neqn - 1) * Neqn + Neqn - 1] = 1.0;
-    for (int i = 0; i < Neqn; ++i)
-        Fg[i] *= -1.0;
-    if (!d_solve_lin_eq(Neqn, w))
-    {
-        atomicExch(a.status, LWHIP_ERR_SINGULAR);
-        return;
-    }
-    start = 0;
-    for (int q = 0; q < a.Natoms; ++q)
-    {
-        const NrAtom at = a.atoms[q];
-        double* n = a.n + (size_t)at.levelOff * Ns;
-        for (int ll = 0; ll < at.Nlevel; ++ll)
-            n[(size_t)ll * Ns + k] += Fg[start + ll];
         start += at.Nlevel;
+        if (change)
+        {
+            report_change(best, bestIdx, change + (size_t)slots[q] * 2 * gridDim.x);
+            __syncthreads();
+        }
     }
-    a.ne[k] = ne + Fg[Neqn - 1];
+    if (ok)
+        a.ne[k] = ne + Fg[Neqn - 1];
 }
 
-hipError_t launch_nr_post(const NrArgs& a, hipStream_t stream)
+// BATCH: column batches -- blockIdx.z picks the column's argument block (read through the constant address space)
+template <bool BATCH> __global__ void nr_post_kernel(const NrArgs a0, const NrListArgs* __restrict__ list)
+{
+    dbg_poison_lds();
+    if constexpr (BATCH)
+    {
+        const NrListArgs l = ld_c(CTAB(NrListArgs, list) + blockIdx.z);
+        nr_post_body(l.a, l.change, l.slots);
+    }
+    else
+        nr_post_body(a0, nullptr, nullptr);
+}
+
+int nr_post_blocks(int Ns, int Neqn)
+{
+    const int tb = solve_block_threads(Neqn);
+    return (Ns + tb - 1) / tb;
+}
+
+// list: nBatch argument blocks on the device, `a` the first of them (its Neqn and Ns are every column's)
+hipError_t launch_nr_post(const NrArgs& a, hipStream_t stream, const NrListArgs* list, int nBatch)
 {
     if (a.Neqn > 64)
         return hipErrorInvalidValue;
     const int tb = solve_block_threads(a.Neqn);
     const size_t lds = solve_ws_doubles(a.Neqn) * sizeof(double) * tb;
-    hipError_t e = solve_set_lds((const void*)nr_post_kernel, lds);
+    hipError_t e = solve_set_lds(list ? (const void*)nr_post_kernel<true> : (const void*)nr_post_kernel<false>, lds);
     if (e != hipSuccess)
         return e;
-    LWHIP_LAUNCH(nr_post_kernel, dim3((a.Ns + tb - 1) / tb), dim3(tb), lds, stream, a);
+    if (list)
+        LWHIP_LAUNCH(nr_post_kernel<true>, dim3((a.Ns + tb - 1) / tb, 1, nBatch > 0 ? nBatch : 1), dim3(tb), lds, stream, a, list);
+    else
+        LWHIP_LAUNCH(nr_post_kernel<false>, dim3((a.Ns + tb - 1) / tb), dim3(tb), lds, stream, a, list);
     return hipGetLastError();
 }
 
