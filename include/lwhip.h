@@ -606,11 +606,36 @@ int lwhip_batch_compute_profiles(lwhip_batch* batch);
  *  - with all columns active the launches and copies of the three entry points are what they were before there was an
  *    active set; and with Ng off they are what they were before there was Ng for batches.
  * The time-dependent and charge-conserving updates of a batch (lwhip_batch_time_dep_update, lwhip_batch_nr_post_update, below)
- * follow the active set under the same invariants.  Out of scope for batches: PRD sub-iterations. */
+ * follow the active set under the same invariants, and so do the PRD sub-iterations (lwhip_batch_redistribute_prd, below). */
 int lwhip_batch_stat_equil_report(lwhip_batch* batch, double* dPops /* [n][Natoms] */, int32_t* dPopsMaxIdx /* [n][Natoms] or NULL */);
 int lwhip_batch_conv_records(lwhip_batch* batch, double* records /* [n][2 + 2 Natoms] */, int* stride /* or NULL */);
 int lwhip_batch_set_active(lwhip_batch* batch, const int32_t* columns, int nActive);
 int lwhip_batch_active(lwhip_batch* batch, int32_t* columns /* [n] or NULL */, int* nActive);
+
+/* PRD sub-iterations for column batches: every ACTIVE column gets what lwhip_redistribute_prd(ctx, maxIter, tol, ...) gives it
+ * alone.  It runs its own sub-iterations and stops after the first whose own largest |d rho / rho| over its lines is below tol,
+ * whatever the other columns do: its rho, J and I over the PRD wavelengths and the PRD lines' Rij / Rji are what its own last
+ * sub-iteration left.  Lane-sweep batches (columns up to 256 depths) run one set of launches per sub-iteration for all active
+ * columns -- five in the steady state, whatever the number of columns: scattering integral, PRD rates pass, sums, rates out,
+ * record --; the stopping rule is kept on the device, one word per column, and the sub-iterations are queued in groups of four
+ * with one copy and one wait per group.  Batches on the ray-column march run lwhip_redistribute_prd column by column.
+ * The arrays of `res` are indexed by the ORIGINAL column number: NprdSubIter [n] (required), dRho / dRhoMaxIdx [n][maxIter][Nprd],
+ * dJPrdMax / dJPrdMaxIdx [n][maxIter] (each may be NULL).  Entries of inactive columns, and slots beyond a column's NprdSubIter,
+ * stay as the caller filled them; the device state of inactive columns is not touched.  lwhip_batch_conv_records keeps the formal
+ * solution's dJMax.  Refused before anything is queued: a null batch or result, an active column with a split iteration or
+ * sub-iteration pending or whose PRD atoms have no C (LWHIP_ERR_INVALID); hybrid-PRD columns and columns made with
+ * LWHIP_OPT_PRD_DETAILED (LWHIP_ERR_UNSUPPORTED).  maxIter <= 0 or no PRD line: LWHIP_OK, NprdSubIter = 0 for the active columns.
+ * The gII cache of a PRD line is per column (it depends on the column's aDamp and vBroad): Nspace * 88 * Nlambda(line) * 10 bytes. */
+typedef struct lwhip_batch_prd_result {
+    int32_t  Nprd;          /* out: PRD lines per column */
+    int32_t  _pad;
+    int32_t* NprdSubIter;   /* [n]                  sub-iterations each column ran */
+    double*  dRho;          /* [n][maxIter][Nprd]   may be NULL */
+    int32_t* dRhoMaxIdx;    /* [n][maxIter][Nprd]   may be NULL */
+    double*  dJPrdMax;      /* [n][maxIter]         may be NULL */
+    int32_t* dJPrdMaxIdx;   /* [n][maxIter]         may be NULL */
+} lwhip_batch_prd_result;
+int lwhip_batch_redistribute_prd(lwhip_batch* batch, int maxIter, double tol, lwhip_batch_prd_result* res);
 
 /* Population updates for column batches: lwhip_time_dep_update of every solved atom, and lwhip_nr_post_update, of every ACTIVE
  * column in one launch each, at every depth point (a batch does not follow lwhip_set_depth_range), with the per-column change

@@ -120,6 +120,12 @@ class lwhip_prd_result(C.Structure):
                 ('dJPrdMax', f64p), ('dJPrdMaxIdx', i32p)]
 
 
+class lwhip_batch_prd_result(C.Structure):
+    """lwhip_batch_redistribute_prd: arrays indexed by the original column number, [n], [n][maxIter][Nprd], [n][maxIter]."""
+    _fields_ = [('Nprd', C.c_int32), ('_pad', C.c_int32), ('NprdSubIter', i32p), ('dRho', f64p), ('dRhoMaxIdx', i32p),
+                ('dJPrdMax', f64p), ('dJPrdMaxIdx', i32p)]
+
+
 class lwhip_intersection(C.Structure):
     _fields_ = [('axis', C.c_int32), ('_pad', C.c_int32), ('fracZ', C.c_double), ('fracX', C.c_double),
                 ('distance', C.c_double)]
@@ -264,6 +270,7 @@ SYMBOLS = [
     ('lwhip_batch_active', C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_int)]),
     ('lwhip_batch_time_dep_update', C.c_int, [C.c_void_p, C.POINTER(f64p), f64p, f64p, i32p]),
     ('lwhip_batch_nr_post_update', C.c_int, [C.c_void_p, C.POINTER(lwhip_nr_args), f64p, i32p]),
+    ('lwhip_batch_redistribute_prd', C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(lwhip_batch_prd_result)]),
     ('lwhip_batch_ng_configure', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ('lwhip_batch_ng_accelerate', C.c_int, [C.c_void_p, i32p, f64p, i32p]),
     ('lwhip_batch_ng_state', C.c_int, [C.c_void_p, i32p, i32p, i32p]),

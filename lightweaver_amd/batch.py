@@ -22,7 +22,8 @@ class BatchConvergence:
     """What ColumnBatch.iterate_to_convergence returns, one entry per column."""
     iterations: List[int]     # the value iterate_ctx_se would return for the column (NmaxIter - 1 where it did not converge)
     converged: List[bool]
-    final: List[list]         # [JUpdate, popsUpdate] of the column's stop iteration ([] where it did not converge)
+    final: List[list]         # [JUpdate, popsUpdate] of the column's stop iteration, with prd=True also its prdUpdate ([] where it
+                              # did not converge)
 
 
 def columns_of_rank(ncolumns: int, world: int, rank: int) -> List[int]:
@@ -424,6 +425,45 @@ class ColumnBatch:
             lib, lib.lwhip_batch_nr_post_update(self._batch, arr, dP.ctypes.data_as(abi.f64p), dI.ctypes.data_as(abi.i32p)),
             'lwhip_batch_nr_post_update'))
 
+    # -- PRD sub-iterations: every active column as a lone Context's prd_redistribute ----------------------------------------
+    def prd_redistribute(self, maxIter=3, tol=1e-2):
+        """Context.prd_redistribute(maxIter, tol, deviceResident=True) of every active column: each column runs its own
+        sub-iterations and stops after the first whose own largest |d rho / rho| is below tol, whatever the others do.  Fused:
+        lwhip_batch_redistribute_prd -- one set of launches per sub-iteration for all columns, the stopping rule per column
+        on the device, one copy back per group of four sub-iterations (a batch on the ray-column march: the columns one after
+        the other inside that call).  Not fused: each column's own call.  Returns one IterationUpdate per column with
+        NprdSubIter, dRho [NprdSubIter, Nprd], dRhoMaxIdx, dJPrdMax, dJPrdMaxIdx, dJMax, dJMaxIdx; None for an inactive
+        column."""
+        import numpy as np
+        from .context import IterationUpdate
+        n = len(self.contexts)
+        ups = [None] * n
+        if self._active is not None and not self._active:
+            return ups
+        if self._batch is None:
+            for i in self.active:
+                ups[i] = self.contexts[i].prd_redistribute(maxIter=maxIter, tol=tol, deviceResident=True)
+            return ups
+        lib = self.contexts[0].lib
+        m = max(int(maxIter), 1)
+        Nprd = max(self.contexts[0].Nprd, 1)
+        nSub = np.zeros(n, dtype=np.int32)
+        dRho = np.zeros((n, m, Nprd))
+        dRhoIdx = np.zeros((n, m, Nprd), dtype=np.int32)
+        dJ = np.zeros((n, m))
+        dJIdx = np.zeros((n, m), dtype=np.int32)
+        res = abi.lwhip_batch_prd_result(0, 0, nSub.ctypes.data_as(abi.i32p), dRho.ctypes.data_as(abi.f64p),
+                                         dRhoIdx.ctypes.data_as(abi.i32p), dJ.ctypes.data_as(abi.f64p), dJIdx.ctypes.data_as(abi.i32p))
+        _check(lib, lib.lwhip_batch_redistribute_prd(self._batch, int(maxIter), float(tol), res), 'lwhip_batch_redistribute_prd')
+        k = res.Nprd
+        for i in self.active:
+            it = int(nSub[i])
+            ups[i] = IterationUpdate(updatedRho=it > 0, updatedJ=it > 0, NprdSubIter=it,
+                                     dRho=dRho[i, :it, :k].copy(), dRhoMaxIdx=dRhoIdx[i, :it, :k].copy(),
+                                     dJPrdMax=dJ[i, :it].copy(), dJPrdMaxIdx=dJIdx[i, :it].copy(),
+                                     dJMax=float(dJ[i, it - 1]) if it else 0.0, dJMaxIdx=int(dJIdx[i, it - 1]) if it else 0)
+        return ups
+
     # -- the active set: the columns formal_sol_gamma_matrices and stat_equil advance ---------------------------------------
     @property
     def active(self) -> List[int]:
@@ -451,7 +491,8 @@ class ColumnBatch:
         self._active = cols
 
     def iterate_to_convergence(self, Nscatter: int = 3, NmaxIter: int = 2000, JTol: float = 5e-3, popsTol: float = 1e-3,
-                               retire: bool = True, callback: Optional[Callable] = None, ng: Optional[tuple] = None):
+                               retire: bool = True, callback: Optional[Callable] = None, ng: Optional[tuple] = None,
+                               prd: bool = False, prdIterTol: float = 1e-2, maxPrdSubIter: int = 3, rhoTol: Optional[float] = None):
         """iterate_ctx_se (iterate.py; lightweaver/iterate_ctx.py:85-208) for every column at once, each column judged by its
         own numbers: a column is converged at the first iteration it >= Nscatter whose own dJMax < JTol and max dPops <
         popsTol (DefaultConvergenceCriteria).  retire=True: it leaves the active set at once, so its state stays what that
@@ -465,10 +506,15 @@ class ColumnBatch:
         ng: (Norder, Nperiod, Ndelay) -- configure_ng with them once all columns are active, before the first iteration;
         None leaves the batch as it is configured.  With Ng each column's popsUpdate carries its own ngAccelerated, and a
         retired column's history and call count stay frozen with the rest of its state.
-        No PRD sub-iterations, time-dependent or charge-conserving updates here."""
+        prd: each iteration it >= Nscatter is formal solution, reported solve, then prd_redistribute(maxPrdSubIter, prdIterTol),
+        and each column is judged by DefaultConvergenceCriteria(..., rhoTol).is_converged(J, pops, prdUpdate) as iterate_ctx_se
+        judges it; the `final` of a converged column then carries the PRD update as third element, and the callback gets the
+        per-column PRD updates (None while it < Nscatter) as a fifth argument.
+        No time-dependent or charge-conserving updates here."""
         from .iterate import DefaultConvergenceCriteria
         n = len(self.contexts)
-        convs = [DefaultConvergenceCriteria(c, JTol, popsTol, None) for c in self.contexts]
+        convs = [DefaultConvergenceCriteria(c, JTol, popsTol, rhoTol if prd else None) for c in self.contexts]
+        extra = lambda prdUps: (prdUps,) if prd else ()    # (the callback's trailing argument, only with prd)  # noqa: E731
         out = BatchConvergence(iterations=[max(NmaxIter - 1, 0)] * n, converged=[False] * n, final=[[] for _ in range(n)])
         pending = list(range(n))
         self.set_active(None)
@@ -484,20 +530,22 @@ class ColumnBatch:
                 JUps = self.formal_sol_gamma_matrices(sync_host=want)
                 if not solve:
                     if callback is not None:
-                        callback(it, JUps, None, self.active)
+                        callback(it, JUps, None, self.active, *extra(None))
                     continue
                 recJ, pUps = self._stat_equil_report()
                 if JUps is None:
                     JUps = recJ
-                new = [i for i in pending if convs[i].is_converged(JUps[i], pUps[i], None)]
+                rUps = self.prd_redistribute(maxIter=maxPrdSubIter, tol=prdIterTol) if prd else [None] * n
+                new = [i for i in pending if convs[i].is_converged(JUps[i], pUps[i], rUps[i])]
                 for i in new:
-                    out.iterations[i], out.converged[i], out.final[i] = it, True, [JUps[i], pUps[i]]
+                    out.iterations[i], out.converged[i] = it, True
+                    out.final[i] = [JUps[i], pUps[i]] + ([rUps[i]] if prd else [])
                 if new:
                     pending = [i for i in pending if not out.converged[i]]
                     if retire:
                         self.set_active(pending)
                 if callback is not None:
-                    callback(it, JUps, pUps, self.active)
+                    callback(it, JUps, pUps, self.active, *extra(rUps))
         finally:
             self.set_active(None)
         return out

@@ -1,10 +1,6 @@
 // lwhip_api_prd.hip -- host side of the C ABI (lwhip_host.h): the PRD sub-iterations.
 #include "lwhip_host.h"
 
-namespace
-{
-enum { PRD_PIPE_DEPTH = 4 }; // sub-iterations queued per host round trip (lwhip_redistribute_prd)
-}
 extern "C"
 {
 void prd_read_results(lwhip_context* c, const double* pinned, double* dRho, int32_t* dRhoMaxIdx, double* dJMax, int32_t* dJMaxIdx);
@@ -52,30 +48,24 @@ int lwhip_prd_pack(lwhip_context* c, void** devPtr, size_t* count)
         *count = (size_t)c->prdRowsTot * Ns;
     return LWHIP_OK;
 }
+}
 
-int lwhip_prd_partial(lwhip_context* c)
+// ---- what lwhip_prd_partial and the column batch (lwhip_batch_redistribute_prd) share ----
+namespace lwhip
 {
-    if (!c)
-        return fail(LWHIP_ERR_INVALID, "null context");
-    if (c->partialPending || c->prdPending)
-        return fail(LWHIP_ERR_INVALID, "lwhip_prd_partial inside an unfinished iteration / sub-iteration");
-    HIP_TRY(hipSetDevice(c->device));
-    c->fpJValid = false; // (the rates pass rewrites J at the PRD wavelengths)
-    {
-        const int stp = ensure_profiles(c);
-        if (stp != LWHIP_OK)
-            return stp;
-    }
-    const int Ns = c->Ns;
-    const int Nprd = (int)c->prdLines.size();
-    if (Nprd == 0)
-        return LWHIP_OK;
-    if (c->prdJ.n < (size_t)c->prdRowsTot * Ns)
-        return fail(LWHIP_ERR_INVALID, "lwhip_prd_partial before lwhip_prd_pack");
+int prd_check_collisions(const lwhip_context* c)
+{
     for (int tr : c->prdLines)
         if (!c->atoms[c->trans[tr].atom].C && !c->atoms[c->trans[tr].atom].detailed)
             return fail(LWHIP_ERR_INVALID, "redistribute_prd needs the collisional rates C of atom "
                                            + std::to_string(c->trans[tr].atom));
+    return LWHIP_OK;
+}
+
+int prd_build_line_args(lwhip_context* c, int stopPos, PrdLineArgs* out)
+{
+    const int Ns = c->Ns;
+    const int Nprd = (int)c->prdLines.size();
     if (c->prdChange.n < (size_t)Nprd * Ns * PRD_MAX_SLICES)
     {
         HIP_TRY(c->prdChange.alloc(c->mem, (size_t)Nprd * Ns * PRD_MAX_SLICES));
@@ -87,7 +77,6 @@ int lwhip_prd_partial(lwhip_context* c)
         jtOff[q + 1] = jtOff[q] + (size_t)(c->trans[c->prdLines[q]].t.Nred - c->trans[c->prdLines[q]].t.Nblue) * Ns;
     if (c->prdJt.n < jtOff[Nprd])
         HIP_TRY(c->prdJt.alloc(c->mem, jtOff[Nprd]));
-    std::vector<PrdLineArgs> lineArgs(Nprd);
     // PRD section of the reduce tail: [world][Nprd] x (max |d rho / rho|, flattened index)
     double* prdTail = c->red.p + (size_t)c->Ntrans * 4 * Ns + 2 * (size_t)c->worldSize;
     for (int q = 0; q < Nprd; ++q)
@@ -183,9 +172,39 @@ int lwhip_prd_partial(lwhip_context* c)
         a.world = c->worldSize;
         a.rank = c->worldRank;
         a.q = q;
+        a.stopPos = stopPos;
         a.Nprd = Nprd;
-        lineArgs[q] = a;
+        out[q] = a;
     }
+    return LWHIP_OK;
+}
+}
+extern "C"
+{
+int lwhip_prd_partial(lwhip_context* c)
+{
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, "null context");
+    if (c->partialPending || c->prdPending)
+        return fail(LWHIP_ERR_INVALID, "lwhip_prd_partial inside an unfinished iteration / sub-iteration");
+    HIP_TRY(hipSetDevice(c->device));
+    c->fpJValid = false; // (the rates pass rewrites J at the PRD wavelengths)
+    {
+        const int stp = ensure_profiles(c);
+        if (stp != LWHIP_OK)
+            return stp;
+    }
+    const int Ns = c->Ns;
+    const int Nprd = (int)c->prdLines.size();
+    if (Nprd == 0)
+        return LWHIP_OK;
+    if (c->prdJ.n < (size_t)c->prdRowsTot * Ns)
+        return fail(LWHIP_ERR_INVALID, "lwhip_prd_partial before lwhip_prd_pack");
+    if (const int stc = prd_check_collisions(c); stc != LWHIP_OK)
+        return stc;
+    std::vector<PrdLineArgs> lineArgs(Nprd);
+    if (const int stb = prd_build_line_args(c, 0, lineArgs.data()); stb != LWHIP_OK)
+        return stb;
     // the blocks change only when a buffer moves or a cache is filled: upload on change (stream-ordered copy from a
     // host copy that lives until the next change)
     if (c->prdArgsHost.size() != (size_t)Nprd

@@ -299,6 +299,7 @@ void lwhip_batch_destroy(lwhip_batch* b)
         (void)hipStreamSynchronize(b->ctxs[0]->stream);
         b->tailPinned.release();
         b->popStage.release();
+        b->prdRecPinned.release();
         stokes_batch_release(b->stokes);
         b->stokes = nullptr;
         rays_release(b->rays);
@@ -393,7 +394,7 @@ int lwhip_batch_sweep_instance(lwhip_batch* b, int32_t out[4])
 {
     if (!b || b->ctxs.empty() || !out)
         return fail(LWHIP_ERR_INVALID, "batch_sweep_instance: null argument");
-    // (what lwhip_batch_formal_sol_gamma_matrices passes its one sweep launch; a batch has no PRD rates pass)
+    // (what lwhip_batch_formal_sol_gamma_matrices passes its one sweep launch; out[1] is not reported for a batch)
     const lwhip_context* c0 = b->ctxs[0];
     const bool lanes = c0->laneSweep && c0->tiled;
     bool sw = true;
@@ -667,6 +668,249 @@ int lwhip_batch_nr_post_update(lwhip_batch* b, const lwhip_nr_args* perColumn, d
             if (dPopsMaxIdx)
                 dPopsMaxIdx[(size_t)i * Na + slots[q]] = (int32_t)rec[i * stride + 3 + 2 * slots[q]];
         }
+    return LWHIP_OK;
+}
+
+// ---- PRD sub-iterations of the active columns: lwhip_redistribute_prd of each, in one set of launches per sub-iteration --------
+// Per sub-iteration: scattering integral over the columns' lines back to back -> PRD rates pass (the BATCH lane sweep over the
+// columns' dtargsPrd) -> stage 2 (sums, the pass's dJMax into prdTail) -> apply (the PRD lines' rates out) -> record
+// (batch_prd_conv_kernel).  A column stops by its own changes: its stop word, set by the record launch of the sub-iteration
+// that met the tolerance, makes its slice of every later launch return at once.
+static int batch_prd_lists(lwhip_batch* b, int Nprd)
+{
+    lwhip_context* c0 = b->ctxs[0];
+    const size_t n = b->ctxs.size();
+    if (b->apPrd.full.size() != n)
+    {
+        HIP_TRY(b->apPrd.alloc(c0->mem, n));
+        HIP_TRY(b->rPrd.alloc(c0->mem, n));
+        HIP_TRY(b->aPrd.alloc(c0->mem, n));
+        HIP_TRY(b->prdTail.alloc(c0->mem, 2 * n));
+        for (size_t i = 0; i < n; ++i)
+        {
+            lwhip_context* c = b->ctxs[i];
+            b->apPrd.full[i] = c->dtargsPrd.p;
+            ReduceArgs& r = b->rPrd.full[i] = make_reduce_args(c);
+            r.batchTail = b->prdTail.p + 2 * i; // (b->tail keeps the formal solution's numbers)
+            r.zeroParts = 1;
+            ApplyArgs& ap = b->aPrd.full[i] = make_apply_args(c);
+            ap.crsw = 0.0;
+            ap.prefill = 0;
+            ap.prdOnly = 1;
+        }
+        b->prdAct.clear();
+    }
+    if (b->prdAct != b->act)
+    {
+        HIP_TRY(hipStreamSynchronize(c0->stream)); // (the staged copies of the last set may still be read)
+        HIP_TRY(b->apPrd.refresh(b->act, c0->stream));
+        HIP_TRY(b->rPrd.refresh(b->act, c0->stream));
+        HIP_TRY(b->aPrd.refresh(b->act, c0->stream));
+        b->prdAct = b->act;
+    }
+    if (b->prdRecNprd != Nprd)
+    {
+        const size_t stride = 2 * (size_t)(1 + Nprd);
+        const size_t doubles = (size_t)PRD_PIPE_DEPTH * n * stride + (n + 1) / 2;
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        HIP_TRY(b->prdRec.alloc_zero(c0->mem, doubles));
+        HIP_TRY(b->prdRecPinned.reserve(c0->device, doubles * sizeof(double), c0->stream));
+        b->prdRecNprd = Nprd;
+    }
+    return LWHIP_OK;
+}
+
+int lwhip_batch_redistribute_prd(lwhip_batch* b, int maxIter, double tol, lwhip_batch_prd_result* res)
+{
+    lwhip_context* c0 = nullptr;
+    if (const int st = batch_enter(b, "batch_redistribute_prd: null batch", c0); st != LWHIP_OK)
+        return st;
+    if (!res || !res->NprdSubIter)
+        return fail(LWHIP_ERR_INVALID, "batch_redistribute_prd: null result");
+    // ---- every refusal, before anything is queued ----
+    const int Nprd = (int)c0->prdLines.size();
+    for (const lwhip_context* c : b->ctxs)
+    {
+        if (c->hprd)
+            return fail(LWHIP_ERR_UNSUPPORTED, "batch_redistribute_prd: hybrid-PRD columns iterate as contexts of their own");
+        if (c->prdDetailed)
+            return fail(LWHIP_ERR_UNSUPPORTED, "batch_redistribute_prd: columns made with LWHIP_OPT_PRD_DETAILED iterate as contexts of "
+                                               "their own");
+    }
+    for (const int32_t i : b->act)
+    {
+        const lwhip_context* c = b->ctxs[i];
+        const std::string col = "batch_redistribute_prd: column " + std::to_string(i);
+        if (c->partialPending || c->prdPending)
+            return fail(LWHIP_ERR_INVALID, col + " has a split iteration or sub-iteration pending");
+        if ((int)c->prdLines.size() != Nprd || c->nTileChunksPrd != c0->nTileChunksPrd || c->laneSplitPrd != c0->laneSplitPrd)
+            return fail(LWHIP_ERR_INVALID, col + " does not share the first column's PRD lines");
+        for (int q = 0; q < Nprd; ++q)
+            if (c->trans[c->prdLines[q]].t.Nred - c->trans[c->prdLines[q]].t.Nblue
+                != c0->trans[c0->prdLines[q]].t.Nred - c0->trans[c0->prdLines[q]].t.Nblue)
+                return fail(LWHIP_ERR_INVALID, col + " does not share the first column's PRD lines");
+        if (const int stc = prd_check_collisions(c); stc != LWHIP_OK)
+            return stc;
+    }
+    res->Nprd = Nprd;
+    for (const int32_t i : b->act) // (entries of inactive columns stay as the caller filled them)
+        res->NprdSubIter[i] = 0;
+    if (Nprd == 0 || maxIter <= 0)
+        return LWHIP_OK;
+    const int nAct = (int)b->act.size();
+    auto out = [&](int32_t i, int it, const double* rec) { // the record of column i's sub-iteration `it` into the caller's arrays
+        const size_t row = (size_t)i * maxIter + (it - 1);
+        if (res->dJPrdMax)
+            res->dJPrdMax[row] = rec[0];
+        if (res->dJPrdMaxIdx)
+            res->dJPrdMaxIdx[row] = (int32_t)rec[1];
+        for (int q = 0; q < Nprd; ++q)
+        {
+            const int Nl = c0->trans[c0->prdLines[q]].t.Nred - c0->trans[c0->prdLines[q]].t.Nblue;
+            if (res->dRho)
+                res->dRho[row * Nprd + q] = rec[2 + 2 * q];
+            if (res->dRhoMaxIdx) // (modulo Nlambda, as prd_read_results reports it)
+                res->dRhoMaxIdx[row * Nprd + q] = (int32_t)rec[3 + 2 * q] % Nl;
+        }
+    };
+    if (!c0->laneSweep)
+    {
+        // a batch on the ray-column march (deep columns, LWHIP_SWEEP=march): not fused -- each active column's own loop
+        std::vector<double> dRho((size_t)maxIter * Nprd), dJ(maxIter), rec(2 * (size_t)(1 + Nprd));
+        std::vector<int32_t> dRhoIdx((size_t)maxIter * Nprd), dJIdx(maxIter);
+        for (const int32_t i : b->act)
+        {
+            lwhip_prd_result r1{ 0, 0, dRho.data(), dRhoIdx.data(), dJ.data(), dJIdx.data() };
+            if (const int st = lwhip_redistribute_prd(b->ctxs[i], maxIter, tol, &r1); st != LWHIP_OK)
+                return st;
+            res->NprdSubIter[i] = r1.NprdSubIter;
+            for (int it = 1; it <= r1.NprdSubIter; ++it)
+            {
+                rec[0] = dJ[it - 1];
+                rec[1] = dJIdx[it - 1];
+                for (int q = 0; q < Nprd; ++q)
+                {
+                    rec[2 + 2 * q] = dRho[(size_t)(it - 1) * Nprd + q];
+                    rec[3 + 2 * q] = dRhoIdx[(size_t)(it - 1) * Nprd + q]; // (below Nlambda already)
+                }
+                out(i, it, rec.data());
+            }
+        }
+        return LWHIP_OK;
+    }
+    // ---- the fused route ----
+    if (const int stp = batch_ensure_profiles(b); stp != LWHIP_OK)
+        return stp;
+    if (const int stl = batch_prd_lists(b, Nprd); stl != LWHIP_OK)
+        return stl;
+    const size_t n = b->ctxs.size(), stride = 2 * (size_t)(1 + Nprd);
+    const size_t recDoubles = (size_t)PRD_PIPE_DEPTH * n * stride;
+    int32_t* stop = (int32_t*)(b->prdRec.p + recDoubles);
+    HIP_TRY(hipMemsetAsync(stop, 0, n * sizeof(int32_t), c0->stream));
+    // each column's dJ is zero outside the PRD wavelengths (once per call: every sub-iteration visits the same wavelengths), its
+    // stage-1 buffer clean (the sweep adds into it, stage 2 zeroes what it has summed)
+    HIP_TRY(launch_batch_zero_dj(b->rPrd.dev.p, c0->Nla, nAct, c0->stream));
+    for (const int32_t i : b->act)
+    {
+        lwhip_context* c = b->ctxs[i];
+        c->fpJValid = false; // (the rates pass rewrites J at the PRD wavelengths)
+        c->dJPrdClean = true;
+        if (!c->red8Clean)
+            HIP_TRY(hipMemsetAsync(c->red8.p, 0, c->red8.n * sizeof(double), c0->stream));
+        c->red8Clean = true;
+    }
+    // one sweep launch for all columns: the launch-wide choices over ALL columns, as lwhip_batch_formal_sol_gamma_matrices makes them
+    TileDyn dyn = make_dyn(c0, false, 0);
+    for (size_t q = 0; q < n && dyn.phiSym; ++q)
+        dyn.phiSym = b->ctxs[q]->phiSym ? 1 : 0;
+    for (size_t q = 0; q < n && dyn.phiIso; ++q)
+        dyn.phiIso = (b->ctxs[q]->phiIso && dyn.phiSym) ? 1 : 0;
+    dyn.prdOnly = 1;
+    dyn.stopCtl = stop;
+    bool plain = true;
+    for (const lwhip_context* c : b->ctxs)
+        plain = plain && c->lsPlain && lane_sweep_plain(c->htargsPrd, dyn, c0->prob.formalSolver, true);
+    ReduceArgs r0 = make_reduce_args(c0);
+    r0.zeroParts = 1;
+    r0.stopCtl = stop;
+    ApplyArgs a0 = b->aPrd.full[b->act[0]];
+    a0.prdCtl = stop;
+    BatchPrdConvArgs ca{};
+    ca.tail = b->prdTail.p;
+    ca.cols = batch_cols(b);
+    ca.stop = stop;
+    ca.tol = tol;
+    ca.Nprd = Nprd;
+    std::vector<PrdLineArgs> lines((size_t)nAct * Nprd);
+    std::vector<int> count(nAct, 0);
+    std::vector<char> done(nAct, 0);
+    int iter = 0, nDone = 0;
+    while (iter < maxIter && nDone < nAct)
+    {
+        const int nb = std::min((int)PRD_PIPE_DEPTH, maxIter - iter);
+        for (int j = 0; j < nb; ++j)
+        {
+            const int it = iter + j + 1;
+            // the lines' blocks change only when a buffer moves or a cache is filled: upload on change
+            for (int p = 0; p < nAct; ++p)
+                if (const int stb = prd_build_line_args(b->ctxs[b->act[p]], p, lines.data() + (size_t)p * Nprd); stb != LWHIP_OK)
+                    return stb;
+            if (b->prdLinesHost.size() != lines.size()
+                || std::memcmp(b->prdLinesHost.data(), lines.data(), lines.size() * sizeof(PrdLineArgs)) != 0)
+            {
+                HIP_TRY(hipStreamSynchronize(c0->stream)); // the previous copy may still be read
+                b->prdLinesHost = lines;
+                if (b->prdLines.n < lines.size())
+                    HIP_TRY(b->prdLines.alloc(c0->mem, lines.size(), false));
+                HIP_TRY(hipMemcpyAsync(b->prdLines.p, b->prdLinesHost.data(), lines.size() * sizeof(PrdLineArgs), hipMemcpyHostToDevice,
+                                       c0->stream));
+            }
+            const int stsc = launch_list(c0, b->prdLines, b->prdLinesHost, false,
+                                         [&](const PrdLineArgs* dev, const PrdLineArgs* host, int nl, hipStream_t s) {
+                                             return launch_prd_scatter(dev, host, nl, s, false, stop, it);
+                                         });
+            if (stsc != LWHIP_OK)
+                return stsc;
+            dyn.stopIter = it;
+            HIP_TRY(launch_lane_sweep(c0->dtargsPrd.p, c0->htargsPrd, dyn, c0->prob.formalSolver, true, c0->nTileChunksPrd, c0->tileWaves,
+                                      b->apPrd.dev.p, nAct, c0->stream, plain));
+            r0.stopIter = it;
+            HIP_TRY(launch_reduce_sum(r0, c0->stream, b->rPrd.dev.p, nAct));
+            a0.prdIter = it;
+            if (c0->Natom > 0)
+                HIP_TRY(launch_apply(a0, c0->stream, b->aPrd.dev.p, nAct));
+            ca.lines = b->prdLines.p;
+            ca.rec = b->prdRec.p + (size_t)((it - 1) % PRD_PIPE_DEPTH) * n * stride;
+            ca.iter = it;
+            HIP_TRY(launch_batch_prd_conv(ca, nAct, c0->stream));
+        }
+        // the group's records and the stop words: one copy, one wait
+        HIP_TRY(hipMemcpyAsync(b->prdRecPinned.host, b->prdRec.p, (recDoubles + (n + 1) / 2) * sizeof(double), hipMemcpyDeviceToHost,
+                               c0->stream));
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        const double* rec = b->prdRecPinned.as<double>();
+        const int32_t* stopHost = (const int32_t*)(rec + recDoubles);
+        for (int p = 0; p < nAct; ++p)
+        {
+            if (done[p])
+                continue;
+            for (int j = 0; j < nb; ++j)
+            {
+                const int it = iter + j + 1;
+                out(b->act[p], it, rec + ((size_t)((it - 1) % PRD_PIPE_DEPTH) * n + p) * stride);
+                count[p] = it;
+                if (stopHost[p] == it) // (the sub-iteration that met the tolerance: the later ones did not run for this column)
+                {
+                    done[p] = 1;
+                    ++nDone;
+                    break;
+                }
+            }
+        }
+        iter += nb;
+    }
+    for (int p = 0; p < nAct; ++p)
+        res->NprdSubIter[b->act[p]] = count[p];
     return LWHIP_OK;
 }
 

@@ -874,9 +874,9 @@ inline void profiles_made_on_device(lwhip_context* c)
 }
 // A batch's list of argument blocks goes to `dev` (copy; grown first if need be, once nothing can still read the buffer that is
 // replaced) and is launched in pieces: the launch geometry allows 65 535 entries per grid dimension.
-template <class T>
-int launch_list(lwhip_context* c0, DevBuf<T>& dev, const std::vector<T>& list, bool copy,
-                hipError_t (*launch)(const T*, const T*, int, hipStream_t))
+// (launch: a function or a closure (const T* dev, const T* host, int n, hipStream_t) -> hipError_t)
+template <class T, class F>
+int launch_list(lwhip_context* c0, DevBuf<T>& dev, const std::vector<T>& list, bool copy, F launch)
 {
     if (list.empty())
         return LWHIP_OK;
@@ -893,6 +893,15 @@ int launch_list(lwhip_context* c0, DevBuf<T>& dev, const std::vector<T>& list, b
 }
 // lwhip_api2d.hip
 int run_2d(lwhip_context* c, int lambdaIterate, int mode = 0);
+// lwhip_api_prd.hip
+enum { PRD_PIPE_DEPTH = 4 }; // sub-iterations queued per host round trip (lwhip_redistribute_prd, lwhip_batch_redistribute_prd)
+// redistribute_prd needs the collisional rates C of every atom with a PRD line: the refusal of both entry points
+int prd_check_collisions(const lwhip_context* c);
+// The argument blocks of the context's PRD lines for one sub-iteration, out[Nprd] -- the scratch buffers of the scattering
+// integral (grown first), the slices, the gII cache (made, or "recompute" where it cannot be allocated; a line whose block says
+// gIIFill is marked filled: the launch that follows fills it) and the change buffers.  stopPos: PrdLineArgs::stopPos of every
+// line.  A lone context launches its own list (lwhip_prd_partial), a column batch the columns' lists back to back.
+int prd_build_line_args(lwhip_context* c, int stopPos, PrdLineArgs* out);
 }
 
 // ---- 1.5D column batches: one iteration of n structurally identical contexts in one set of launches (lwhip_batch.hip;
@@ -951,6 +960,20 @@ struct lwhip_batch
     int nrBlocks = 0;                    // Newton-Raphson blocks per column (the block size follows Neqn, not seMaxNl)
     DevBuf<double> nrChange;             // [n][Natoms][nrBlocks][2]; zero in the slots of solved atoms the call does not list
     std::vector<int32_t> nrListed;       // the atom list those zeros are right for
+    // lwhip_batch_redistribute_prd: the lists of the PRD rates pass, made by the first call and refreshed
+    // by a call that finds another active set than the last one did (prdAct); the lines' argument blocks of the active
+    // columns back to back, position-major, uploaded when they change; the PRD pass's own (dJMax, idx) tail; the records of a
+    // group of sub-iterations [PRD_PIPE_DEPTH][n][2 (1 + Nprd)] with the int32 stop words [n] behind them -- one copy per group
+    ColList<const TileArgs*> apPrd;      // the columns' dtargsPrd
+    ColList<ReduceArgs> rPrd;            // stage 2 with batchTail -> prdTail
+    ColList<ApplyArgs> aPrd;             // the PRD lines' rates out (prdOnly)
+    std::vector<int32_t> prdAct;         // the set those lists' device copies hold
+    DevBuf<double> prdTail;              // [n][2]
+    DevBuf<PrdLineArgs> prdLines;
+    std::vector<PrdLineArgs> prdLinesHost; // what the device copy holds
+    DevBuf<double> prdRec;
+    int prdRecNprd = -1;                 // the line count prdRec was sized for
+    PinnedBlock prdRecPinned;
     NgState ng;                                // lwhip_batch_ng_configure: Ng acceleration of every column
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments

@@ -414,6 +414,10 @@ struct ReduceArgs
     int32_t zeroParts;             // stage 2 zeroes the parts it has summed (they were accumulated by atomics)
     int32_t nParts;                // parts per transition in red8: LWHIP_REDUCE_SPLIT, or -- fixed-order mode -- the LWHIP_DET_SEG
                                    // segment sums of the slab reduce (red8 then points at them)
+    // PRD sub-iterations of a column batch, read from the LAUNCH's block (a0) only: the stop words by list position, and the
+    // sub-iteration this launch belongs to -- the slice of a column that stopped earlier returns at once (TileDyn::stopCtl)
+    int32_t stopIter;
+    const int32_t* stopCtl;
 };
 
 struct ApplyArgs
@@ -457,6 +461,9 @@ struct ApplyArgs
     // pipelined PRD sub-iterations: prdCtl = { number of the first sub-iteration whose max |d rho / rho| was below prdTol (0:
     // none yet), lines below the tolerance so far, lines reduced so far, sub-iterations run }.  The launch does nothing if
     // an earlier sub-iteration stopped the loop; its last PRD-line workgroup records whether THIS one does
+    // Column batches (the list form of the launch): prdCtl of the LAUNCH's block (a0) is the batch's stop words, one per list
+    // position -- the slice of a column whose word is non-zero and below prdIter returns at once; the words are set by
+    // batch_prd_conv_kernel, not here
     int32_t* prdCtl;
     double prdTol;
     int32_t prdIter;
@@ -555,7 +562,8 @@ struct PrdLineArgs
     int32_t gi, gj;         // global level rows
     int32_t lj;             // local upper level
     int32_t trBegin, trEnd; // global transition range of the line's atom
-    int32_t slices, _padS;  // workgroups per depth point (slices of the emission wavelengths)
+    int32_t slices;         // workgroups per depth point (slices of the emission wavelengths)
+    int32_t stopPos;        // which stop word of the launch is this line's: its column's list position in a column batch; a lone context: 0
     int32_t laLo, laHi;     // emission wavelengths handled here (the shard's part of the line), own-grid indices
     int32_t world, rank, q, Nprd; // where the line's (max change, index) goes in the reduce tail
     double* tail;           // [world][Nprd][2]
@@ -641,6 +649,24 @@ struct BatchConvArgs
     int32_t Natoms, nBlocks;
 };
 hipError_t launch_batch_conv(const BatchConvArgs& a, int nActive, hipStream_t stream);
+// column batches, PRD sub-iterations: the record of one sub-iteration for every active column, one wavefront per list position.
+// It reduces the column's lines (prd_change_reduce), takes the (dJMax, idx) its slice of the PRD pass's stage 2 left, writes
+// rec[position] = { dJMax, idx, (max |d rho / rho|, flattened index) per line } and, when the largest change is below tol, sets
+// the column's stop word to `iter`.  A column whose word is set already (non-zero, below iter) is left alone.
+struct BatchPrdConvArgs
+{
+    const PrdLineArgs* lines; // [nActive][Nprd] the batch's concatenated line list
+    const double* tail;       // [n][2] (dJMax, idx) of the PRD rates pass, by column
+    const int32_t* cols;      // [nActive] original column numbers, or null: position p is column p
+    double* rec;              // [nActive][2 (1 + Nprd)] this sub-iteration's slot of the group's records
+    int32_t* stop;            // [nActive]
+    double tol;
+    int32_t Nprd, iter;
+};
+hipError_t launch_batch_prd_conv(const BatchPrdConvArgs& a, int nActive, hipStream_t stream);
+// ... and in front of a call's first sub-iteration: dJ of every listed column to zero (the PRD rates pass writes its own
+// wavelengths only; list: the columns' stage-2 blocks, whose dJ and Nla are used)
+hipError_t launch_batch_zero_dj(const ReduceArgs* list, int maxNla, int nActive, hipStream_t stream);
 hipError_t launch_peer_publish(const PeerPublishArgs& a, hipStream_t stream);
 // self-test of the exchange: fill `buf` with the rank's pattern / wait for the world's flags (bounded by spinLimit polls) and
 // compare every slot with its rank's pattern; *result = 0 ok, 1 a flag never came, 2 a slot holds something else

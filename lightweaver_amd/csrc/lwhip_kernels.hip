@@ -155,7 +155,16 @@ __global__ void __launch_bounds__(512) reduce_stage2_kernel(const ReduceArgs a0,
 {
     dbg_poison_lds();
     if constexpr (BATCH)
+    {
+        // (PRD sub-iterations of a column batch: a column that stopped at an earlier sub-iteration is left as it is)
+        if (a0.stopCtl)
+        {
+            const int s = *(const volatile int32_t*)(a0.stopCtl + blockIdx.z);
+            if (s != 0 && s < a0.stopIter)
+                return;
+        }
         reduce_stage2_kernel_body(CTAB(ReduceArgs, list)[blockIdx.z]);
+    }
     else
         reduce_stage2_kernel_body(a0);
 }
@@ -578,7 +587,16 @@ __global__ void __launch_bounds__(APPLY_T) apply_kernel(const ApplyArgs a0, cons
 {
     dbg_poison_lds();
     if constexpr (BATCH)
+    {
+        // (PRD sub-iterations of a column batch: a0.prdCtl holds one stop word per list position, see ApplyArgs)
+        if (a0.prdCtl)
+        {
+            const int s = *(const volatile int32_t*)(a0.prdCtl + blockIdx.z);
+            if (s != 0 && s < a0.prdIter)
+                return;
+        }
         apply_kernel_body<K>(CTAB(ApplyArgs, list)[blockIdx.z]);
+    }
     else
         apply_kernel_body<K>(a0);
 }

@@ -3227,7 +3227,8 @@ __global__ void __launch_bounds__(LS_MAX_WAVES * 64) __attribute__((amdgpu_waves
     if (dyn.stopCtl)
     {
         // (the PRD rates pass of a pipelined sub-iteration: an earlier sub-iteration met the tolerance -- nothing to do)
-        const int stopAt = __builtin_amdgcn_readfirstlane(*(const volatile int32_t*)dyn.stopCtl);
+        // (a column batch: one stop word per column of the list, each column stops by its own changes)
+        const int stopAt = __builtin_amdgcn_readfirstlane(*(const volatile int32_t*)(dyn.stopCtl + (BATCH ? (int)blockIdx.y : 0)));
         if (stopAt != 0 && stopAt < dyn.stopIter)
             return;
     }

@@ -221,20 +221,22 @@ DEVINL void prd_store_change(const PrdLineArgs& a, const int k, double best, int
 // J(Nblue : Nred, :) -> Jt[k][la]: the scattering integral reads J along wavelength at fixed depth
 // (stopCtl / stopIter: the pipelined sub-iterations of lwhip_redistribute_prd -- a launch of a sub-iteration that comes after
 // the one that met the tolerance does nothing)
-DEVINL bool prd_stopped(const int32_t* stopCtl, const int stopIter)
+// (pos: the line's stop word -- PrdLineArgs::stopPos, the list position of its column in a column batch, whose columns stop each
+// by its own changes; 0 for a lone context)
+DEVINL bool prd_stopped(const int32_t* stopCtl, const int pos, const int stopIter)
 {
     if (!stopCtl)
         return false;
-    const int s = *(const volatile int32_t*)stopCtl;
+    const int s = *(const volatile int32_t*)(stopCtl + pos);
     return s != 0 && s < stopIter;
 }
 
 __global__ void prd_transpose_kernel(const PrdLineArgs* __restrict__ list, const int32_t* stopCtl, const int stopIter)
 {
     dbg_poison_lds();
-    if (prd_stopped(stopCtl, stopIter))
-        return;
     const PrdLineArgs a = ld_c(CTAB(PrdLineArgs, list) + blockIdx.z);
+    if (prd_stopped(stopCtl, a.stopPos, stopIter))
+        return;
     const double* J = a.J;
     double* Jt = a.Jt;
     const int Nblue = a.Nblue, Nl = a.Nl, Ns = a.Ns;
@@ -263,9 +265,9 @@ __global__ void __launch_bounds__(128) prd_scatter_kernel(const PrdLineArgs* __r
 {
     dbg_poison_lds();
     extern __shared__ double sm[];
-    if (prd_stopped(stopCtl, stopIter))
-        return;
     const PrdLineArgs a = ld_c(CTAB(PrdLineArgs, list) + blockIdx.z);
+    if (prd_stopped(stopCtl, a.stopPos, stopIter))
+        return;
     if (a.laHi <= a.laLo || (int)blockIdx.y >= a.slices)
         return;
     const int k = blockIdx.x;
@@ -408,9 +410,9 @@ __global__ void __launch_bounds__(128) prd_scatter_cached_kernel(const PrdLineAr
 {
     dbg_poison_lds();
     extern __shared__ double sm[];
-    if (prd_stopped(stopCtl, stopIter))
-        return;
     const PrdLineArgs a = ld_c(CTAB(PrdLineArgs, list) + blockIdx.z);
+    if (prd_stopped(stopCtl, a.stopPos, stopIter))
+        return;
     if (a.laHi <= a.laLo || (int)blockIdx.y >= a.slices)
         return;
     const int k = blockIdx.x;
@@ -481,6 +483,65 @@ __global__ void prd_change_kernel(const PrdLineArgs* __restrict__ list)
     dbg_poison_lds();
     const PrdLineArgs a = ld_c(CTAB(PrdLineArgs, list) + blockIdx.x);
     prd_change_reduce(a, (int)threadIdx.x);
+}
+
+// ---- column batches: one sub-iteration's record per active column, and the column's stop word (BatchPrdConvArgs) ----------------
+__global__ void __launch_bounds__(64) batch_prd_conv_kernel(const BatchPrdConvArgs a)
+{
+    dbg_poison_lds();
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int s = *(const volatile int32_t*)(a.stop + p);
+    if (s != 0 && s < a.iter)
+        return;
+    const int col = a.cols ? a.cols[p] : p;
+    const int stride = 2 * (1 + a.Nprd);
+    double* rec = a.rec + (size_t)p * stride;
+    double worst = 0.0;
+    for (int q = 0; q < a.Nprd; ++q)
+    {
+        const PrdLineArgs l = ld_c(CTAB(PrdLineArgs, a.lines) + ((size_t)p * a.Nprd + q));
+        const double best = prd_change_reduce(l, lane); // (every lane holds it; lane 0 has stored (value, index) in the line's slot)
+        worst = fmax(worst, best);
+        if (lane == 0)
+        {
+            const double* slot = l.tail + ((size_t)l.rank * l.Nprd + l.q) * 2;
+            rec[2 + 2 * q] = slot[0];
+            rec[3 + 2 * q] = slot[1];
+        }
+    }
+    if (lane == 0)
+    {
+        rec[0] = a.tail[2 * (size_t)col];
+        rec[1] = a.tail[2 * (size_t)col + 1];
+        // the loop of redistribute_prd (PrdTemplates.hpp:250-275) stops after the sub-iteration whose largest change over the
+        // column's lines is below the tolerance: the launches of the later sub-iterations, queued already, skip this column
+        if (worst < a.tol)
+            a.stop[p] = a.iter;
+    }
+}
+hipError_t launch_batch_prd_conv(const BatchPrdConvArgs& a, int nActive, hipStream_t stream)
+{
+    if (nActive <= 0)
+        return hipSuccess;
+    LWHIP_LAUNCH(batch_prd_conv_kernel, dim3(nActive), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) batch_zero_dj_kernel(const ReduceArgs* __restrict__ list)
+{
+    dbg_poison_lds();
+    const ReduceArgs r = ld_c(CTAB(ReduceArgs, list) + blockIdx.y);
+    const int la = blockIdx.x * blockDim.x + threadIdx.x;
+    if (la < r.Nla)
+        const_cast<double*>(r.dJ)[la] = 0.0;
+}
+hipError_t launch_batch_zero_dj(const ReduceArgs* list, int maxNla, int nActive, hipStream_t stream)
+{
+    if (nActive <= 0 || maxNla <= 0)
+        return hipSuccess;
+    for (int off = 0; off < nActive; off += 32768) // (the launch geometry allows 65 535 entries per grid dimension)
+        LWHIP_LAUNCH(batch_zero_dj_kernel, dim3((maxNla + 255) / 256, std::min(32768, nActive - off)), dim3(256), 0, stream, list + off);
+    return hipGetLastError();
 }
 
 hipError_t launch_prd_scatter(const PrdLineArgs* devList, const PrdLineArgs* hostList, int nLines, hipStream_t stream, bool reduceChange,
