@@ -341,6 +341,22 @@ int lwhip_create_like(const lwhip_problem* prob, const lwhip_options* opts, lwhi
 /* Free everything lwhip_create allocated.  Replaces free_global_scratch. */
 int lwhip_destroy(lwhip_context* ctx);
 
+/* The hybrid PRD tables of a problem, built on the device: configure_hprd_coeffs (Source/Prd.cpp:697-946; what
+ * LwContext(hprd=True) calls at construction and again whenever the velocity field changes, Source/LwMiddleLayer.pyx:3686-3720).
+ * *out receives a library-owned lwhip_hprd -- exactly what lwhip_create takes through lwhip_options.hprd, the reference's
+ * tables bit for bit (the build needs only correctly rounded fp64 multiply, divide, add and compare) -- whose JRest is its own
+ * zeroed [NprdLambda, Nspace] array.  Contexts borrow the tables: free them with lwhip_hprd_free after those contexts are
+ * destroyed (NULL is a no-op; tables from anywhere else are left alone).
+ * The lines: every LWHIP_LINE with prd and rhoPrd, active atoms first, with includeDetailed followed by those of the detailed
+ * atoms (:712-735).  A problem without such a line: LWHIP_OK and *out = NULL (the reference returns early and stays plain PRD).
+ * Of `opts` only device and stream are read (NULL: device 0, a stream of the library's).  Refused before the device is
+ * touched, *out = NULL: a null prob or out, an ABI version mismatch, a problem without vlosMu or wavelength, a PRD line with
+ * fewer than 2 wavelengths (LWHIP_ERR_INVALID); a 2D problem (LWHIP_ERR_UNSUPPORTED).  Without a HIP device: LWHIP_ERR_DEVICE,
+ * there is no CPU path.  On the stream: one upload of the inputs (both grids, vlosMu, a few KB), the launches, and three waits
+ * -- for the per-wavelength flags the layout depends on, for the 8-byte total that sizes jCoeffs, for the tables. */
+int lwhip_hprd_build(const lwhip_problem* prob, const lwhip_options* opts, int includeDetailed, lwhip_hprd** out);
+void lwhip_hprd_free(lwhip_hprd* tables);
+
 /* Copy the host arrays named by `mask` (LWHIP_* bits) from the descriptor given at create
  * into HBM / back out of it.  Synchronous with respect to the host buffers. */
 int lwhip_upload(lwhip_context* ctx, uint32_t mask);

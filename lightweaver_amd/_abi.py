@@ -229,6 +229,9 @@ SYMBOLS = [
     ('lwhip_create', C.c_int, [C.POINTER(lwhip_problem), C.POINTER(lwhip_options), C.POINTER(ctx_p)]),
     ('lwhip_create_like', C.c_int, [C.POINTER(lwhip_problem), C.POINTER(lwhip_options), ctx_p, C.POINTER(ctx_p)]),
     ('lwhip_destroy', C.c_int, [ctx_p]),
+    ('lwhip_hprd_build', C.c_int, [C.POINTER(lwhip_problem), C.POINTER(lwhip_options), C.c_int,
+                                   C.POINTER(C.POINTER(lwhip_hprd))]),
+    ('lwhip_hprd_free', None, [C.POINTER(lwhip_hprd)]),
     ('lwhip_upload', C.c_int, [ctx_p, C.c_uint32]),
     ('lwhip_download', C.c_int, [ctx_p, C.c_uint32]),
     ('lwhip_gamma_prefill_from_C', C.c_int, [ctx_p, C.c_double]),

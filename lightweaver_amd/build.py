@@ -16,7 +16,7 @@ REF_SRC = os.environ.get('LW_REFERENCE_SOURCE', '/root/reference/Source')
 
 HIP_SOURCES = ['lwhip_api.hip', 'lwhip_tables.hip', 'lwhip_state.hip', 'lwhip_api2d.hip', 'lwhip_batch.hip', 'lwhip_api_prd.hip',
                'lwhip_kernels.hip', 'lwhip_raymarch.hip', 'lwhip_lanesweep.hip', 'lwhip_voigt.hip', 'lwhip_prd.hip', 'lwhip_pops.hip', 'lwhip_fs2d.hip', 'lwhip_2d.hip', 'lwhip_geom2d.hip', 'lwhip_stokes.hip',
-               'lwhip_stokes_batch.hip', 'lwhip_stokes_fs.hip', 'lwhip_rays.hip', 'lwhip_rays2d.hip']
+               'lwhip_stokes_batch.hip', 'lwhip_stokes_fs.hip', 'lwhip_rays.hip', 'lwhip_rays2d.hip', 'lwhip_hprd.hip']
 HIP_HEADERS = ['lwhip_internal.h', 'lwhip_device.h', 'lwhip_host.h', 'lwhip_lu.h', 'lwhip_voigt_dev.h', os.path.join('..', '..', 'include', 'lwhip.h')]
 
 

@@ -106,7 +106,9 @@ class Context:
         hprd: hybrid PRD -- the tables configure_hprd_coeffs leaves in the reference's Context
         (Source/Prd.cpp:697-946), as a ctypes pointer to lwhip_hprd or any object with such a `.ptr` (what
         LwContext(hprd=True) sets up, Source/LwMiddleLayer.pyx:2822-2826); borrowed for the life of the context.
-        JRest comes back with download(J)."""
+        hprd=True: the context builds them on the device for the problem's vlosMu (hprd.build_hprd, with the detailed atoms'
+        PRD lines when prdDetailed), owns them and frees them in close() after the context; a problem without PRD lines stays
+        plain PRD.  Either way they are `hprd_tables`, and JRest comes back with download(J)."""
         self.lib = load_library(lib_path)
         self.prob = prob
         self._desc = prob.descriptor()
@@ -119,6 +121,14 @@ class Context:
         opts.flags = (min(max(int(batchHint), 0), 0xffff) | (abi.OPT_PRD_DETAILED if prdDetailed else 0)
                       | (abi.OPT_DETERMINISTIC if deterministic else 0))
         self.prdDetailed = bool(prdDetailed)
+        self._hprdOwned = None
+        if hprd is True:
+            # tables of this context's own, for the problem's current velocities (never borrowed, `like` or not); None: the
+            # problem has no PRD line and the context stays plain PRD, as the reference's does
+            from .hprd import build_from_descriptor
+            hprd = self._hprdOwned = build_from_descriptor(self.lib, self._desc, prob, device, self.prdDetailed, stream)
+        elif hprd is False:
+            hprd = None
         self._hprd = hprd   # keep the tables alive
         if hprd is not None:
             opts.hprd = getattr(hprd, 'ptr', hprd)
@@ -158,12 +168,21 @@ class Context:
             if like is not None and like._pending:
                 like._pending = False
                 like.close()
+        owned, self._hprdOwned = getattr(self, '_hprdOwned', None), None
+        if owned is not None:   # (hprd=True: the context is gone, or was never made; its tables go after it)
+            owned.close()
+            self._hprd = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    @property
+    def hprd_tables(self):
+        """The hybrid PRD tables in use: the ones given, or the HprdTables hprd=True built (None: plain PRD)."""
+        return self._hprd
 
     def __enter__(self):
         return self

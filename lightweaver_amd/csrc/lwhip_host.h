@@ -11,6 +11,7 @@
 //     lwhip_api_prd.hip  PRD sub-iterations
 //     lwhip_rays.hip     emergent spectra along observer rays
 //     lwhip_rays2d.hip   ... of a 2D context
+//     lwhip_hprd.hip     the hybrid-PRD interpolation tables, built on the device (needs no context)
 //
 // There is no CPU fallback: without a HIP device every compute entry point fails with LWHIP_ERR_DEVICE.
 #pragma once
