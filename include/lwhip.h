@@ -581,7 +581,11 @@ int lwhip_formal_solver_2d(int device, const lwhip_grid2d* grid, double waveleng
  * solver and device; own atmospheres, profiles, populations -- advance together, one grid slice per column, on the
  * first column's stream (the others are moved onto it),
  * so a batch of short columns fills the device the way one long wavelength grid does.  Columns never exchange
- * radiation (the reference runs them as separate Contexts: README.md:9); results[i] receives column i's dJMax. */
+ * radiation (the reference runs them as separate Contexts: README.md:9); results[i] receives column i's dJMax.
+ * Hybrid-PRD columns (lwhip_options.hprd, each with tables for its own velocity field): all columns or none
+ * (LWHIP_ERR_INVALID for a mix).  Their tile lists follow their velocities, so on the lane sweep they may differ in their
+ * workgroup counts: the one sweep launch takes the largest count and every workgroup checks its own column's
+ * (lwhip_batch_sweep_shape); each column's JRest is cleared in front of every pass that rebuilds it. */
 typedef struct lwhip_batch lwhip_batch;
 int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out);
 void lwhip_batch_destroy(lwhip_batch* batch);
@@ -633,14 +637,16 @@ int lwhip_batch_active(lwhip_batch* batch, int32_t* columns /* [n] or NULL */, i
  * whatever the other columns do: its rho, J and I over the PRD wavelengths and the PRD lines' Rij / Rji are what its own last
  * sub-iteration left.  Lane-sweep batches (columns up to 256 depths) run one set of launches per sub-iteration for all active
  * columns -- five in the steady state, whatever the number of columns: scattering integral, PRD rates pass, sums, rates out,
- * record --; the stopping rule is kept on the device, one word per column, and the sub-iterations are queued in groups of four
+ * record; six for hybrid-PRD columns, whose JRest is cleared between the integral that reads it and the pass that rebuilds it
+ * (a column that has stopped keeps the JRest of its own stop) --; the stopping rule is kept on the device, one word per column, and the sub-iterations are queued in groups of four
  * with one copy and one wait per group.  Batches on the ray-column march run lwhip_redistribute_prd column by column.
  * The arrays of `res` are indexed by the ORIGINAL column number: NprdSubIter [n] (required), dRho / dRhoMaxIdx [n][maxIter][Nprd],
  * dJPrdMax / dJPrdMaxIdx [n][maxIter] (each may be NULL).  Entries of inactive columns, and slots beyond a column's NprdSubIter,
  * stay as the caller filled them; the device state of inactive columns is not touched.  lwhip_batch_conv_records keeps the formal
  * solution's dJMax.  Refused before anything is queued: a null batch or result, an active column with a split iteration or
- * sub-iteration pending or whose PRD atoms have no C (LWHIP_ERR_INVALID); hybrid-PRD columns and columns made with
- * LWHIP_OPT_PRD_DETAILED (LWHIP_ERR_UNSUPPORTED).  maxIter <= 0 or no PRD line: LWHIP_OK, NprdSubIter = 0 for the active columns.
+ * sub-iteration pending or whose PRD atoms have no C (LWHIP_ERR_INVALID); columns made with LWHIP_OPT_PRD_DETAILED, and
+ * hybrid-PRD columns that borrow one and the same lwhip_hprd -- they share one host JRest, so each column needs tables of
+ * its own -- (LWHIP_ERR_UNSUPPORTED).  maxIter <= 0 or no PRD line: LWHIP_OK, NprdSubIter = 0 for the active columns.
  * The gII cache of a PRD line is per column (it depends on the column's aDamp and vBroad): Nspace * 88 * Nlambda(line) * 10 bytes. */
 typedef struct lwhip_batch_prd_result {
     int32_t  Nprd;          /* out: PRD lines per column */
@@ -988,6 +994,11 @@ int lwhip_layout_1d(lwhip_context* ctx, int32_t out[10]);
  * lwhip_batch_sweep_instance: the same of a column batch's one sweep launch, plain only if every column's would be (out[1] = 0). */
 int lwhip_sweep_instance(lwhip_context* ctx, int32_t out[4]);
 int lwhip_batch_sweep_instance(lwhip_batch* batch, int32_t out[4]);
+/* The shape of a column batch's sweep launches; launches nothing, changes nothing.  perColumn [n][2]: each column's workgroup
+ * count in the full sweep and in the PRD rates pass (0 without one); launch[0], launch[1]: gridDim.x of the batch's one launch
+ * of either for the current active set (launch[1] = 0 on the ray-column march, whose PRD pass is not fused).  Equal for every
+ * column except in hybrid-PRD batches, where the launch takes the largest.  LWHIP_ERR_INVALID for a null argument. */
+int lwhip_batch_sweep_shape(lwhip_batch* batch, int32_t* perColumn /* [n][2] */, int32_t launch[2]);
 /* A fingerprint of what lwhip_create planned for this context; launches nothing, copies nothing:
  *   out[0]          folds the element count and content fingerprint of every structure-table buffer, in the order the
  *                   library lists them (a context made with lwhip_create_like reports its owner's words)

@@ -304,6 +304,7 @@ SYMBOLS = [
     ('lwhip_layout_1d', C.c_int, [ctx_p, i32p]),
     ('lwhip_sweep_instance', C.c_int, [ctx_p, i32p]),
     ('lwhip_batch_sweep_instance', C.c_int, [C.c_void_p, i32p]),
+    ('lwhip_batch_sweep_shape', C.c_int, [C.c_void_p, i32p, i32p]),
     ('lwhip_tables_signature', C.c_int, [ctx_p, C.POINTER(C.c_uint64)]),
     ('lwhip_set_stokes', C.c_int, [ctx_p, C.POINTER(lwhip_stokes)]),
     ('lwhip_compute_polarised_profiles', C.c_int, [ctx_p]),

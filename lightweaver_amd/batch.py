@@ -26,6 +26,17 @@ class BatchConvergence:
                               # did not converge)
 
 
+def _hprd_key(tables):
+    """What identifies a hybrid-PRD table set given as Context's `hprd`: the address of its lwhip_hprd, whether it comes as an object
+    with `.ptr` or as a ctypes pointer (two pointer objects to one lwhip_hprd are one set)."""
+    import ctypes
+    ptr = getattr(tables, 'ptr', tables)
+    try:
+        return ctypes.cast(ptr, ctypes.c_void_p).value
+    except (TypeError, ctypes.ArgumentError):
+        return id(tables)
+
+
 def columns_of_rank(ncolumns: int, world: int, rank: int) -> List[int]:
     """Round-robin column ownership; no data-path communication between ranks."""
     if not (0 <= rank < world):
@@ -77,8 +88,14 @@ class ColumnBatch:
     _ng = None         # (Norder, Nperiod, Ndelay) in effect, Ndelay after the max rule -- configure_ng; None: no Ng acceleration
 
     def __init__(self, problems: Sequence[Problem], device: int = 0, stream: Optional[int] = None,
-                 device_profiles: bool = True, streams: Optional[Sequence[int]] = None, fused: bool = True):
-        """`fused` (default): the columns advance in ONE set of launches per iteration (lwhip_batch_*: one grid
+                 device_profiles: bool = True, streams: Optional[Sequence[int]] = None, fused: bool = True, hprd=None):
+        """hprd: hybrid PRD for every column.  True: each column builds the tables for its own velocity field on the device
+        (Context(p, hprd=True)) and owns them -- close() frees them after the contexts.  A list: one table set per column (as
+        Context's `hprd`), borrowed; a set given twice raises ValueError (columns on one set would share one JRest).  Either way
+        they are `hprd_tables`, one entry per column, and download() brings each column's JRest into its own.  The columns'
+        tile lists follow their velocities, so the fused launches take the largest workgroup count (sweep_shape).  A hybrid
+        batch that the library refuses to fuse is reported with a RuntimeWarning: see `fused`.
+        `fused` (default): the columns advance in ONE set of launches per iteration (lwhip_batch_*: one grid
         slice per column), which is what fills the device when a single column's wavelength grid does not;
         it needs structurally identical columns on one stream and falls back to per-column launches otherwise.
         `streams`: optional HIP streams (handles) the columns are dealt to round-robin in the per-column mode, so
@@ -86,8 +103,21 @@ class ColumnBatch:
         self.problems = list(problems)
         self._batch = None
         self._active = None     # (None: every column; else the increasing list of active columns -- set_active)
+        if hprd is None or hprd is False:
+            hp = lambda i: None     # noqa: E731
+        elif hprd is True:
+            hp = lambda i: True     # noqa: E731
+        else:
+            given = list(hprd)
+            if len(given) != len(self.problems):
+                raise ValueError('ColumnBatch: hprd needs one table set per column')
+            keys = [_hprd_key(t) for t in given]
+            if len(set(keys)) != len(keys):
+                raise ValueError('ColumnBatch: a hybrid-PRD table set is given to more than one column; each column needs tables of '
+                                 'its own (they hold its JRest)')
+            hp = lambda i: given[i]     # noqa: E731
         if streams:
-            self.contexts = [Context(p, device=device, stream=streams[i % len(streams)])
+            self.contexts = [Context(p, device=device, stream=streams[i % len(streams)], hprd=hp(i))
                              for i, p in enumerate(self.problems)]
         else:
             # (the columns of a fused batch share their structure: all but the first borrow the first one's tables)
@@ -96,7 +126,10 @@ class ColumnBatch:
             # the library's create path shares nothing writable between contexts (the donor's borrower count is atomic, the
             # error text is per thread).  LWHIP_CREATE_THREADS=1 creates them one after the other (default 16).
             hint = len(self.problems) if fused else 0
-            self.contexts = [Context(self.problems[0], device=device, stream=stream, batchHint=hint)] if self.problems else []
+            # (hprd=True: every column builds its own tables inside its create, also concurrently -- lwhip_hprd_build keeps its
+            # buffers in locals, takes its stream from the library's locked pool and leaves the error text per thread)
+            self.contexts = ([Context(self.problems[0], device=device, stream=stream, batchHint=hint, hprd=hp(0))]
+                             if self.problems else [])
             donor = self.contexts[0] if (fused and self.contexts) else None
             rest = self.problems[1:]
             # (round 6, tools/create_threads_time.py: 64 borrowers take 5.8 / 1.8 / 1.35 / 0.99 ms each on 1 / 4 / 8 / 16 threads --
@@ -104,7 +137,8 @@ class ColumnBatch:
             nthr = max(1, min(int(os.environ.get('LWHIP_CREATE_THREADS', '16')), os.cpu_count() or 1, len(rest)))
             if os.environ.get('LWHIP_DEBUG') and any(os.environ.get(k) for k in ('LWHIP_PAD_SENTINEL', 'LWHIP_TRACE_ALLOC')):
                 nthr = 1    # (those diagnoses number the allocations in creation order: one creating thread)
-            make = lambda p: Context(p, device=device, stream=stream, batchHint=hint, like=donor)  # noqa: E731
+            make = lambda ip: Context(ip[1], device=device, stream=stream, batchHint=hint, like=donor, hprd=hp(ip[0]))  # noqa: E731
+            rest = list(enumerate(rest, 1))
             if nthr > 1:
                 from concurrent.futures import ThreadPoolExecutor
                 with ThreadPoolExecutor(max_workers=nthr) as ex:
@@ -130,11 +164,39 @@ class ColumnBatch:
             h = C.c_void_p()
             if lib.lwhip_batch_create(arr, len(self.contexts), C.byref(h)) == abi.OK:
                 self._batch = h
+            elif hprd is not None and hprd is not False:
+                import warnings
+                warnings.warn('ColumnBatch: the hybrid-PRD columns are not fused (%s): they advance by per-column launches'
+                              % lib.lwhip_last_error().decode(errors='replace'), RuntimeWarning, stacklevel=2)
         if device_profiles:
             self.compute_profiles()
 
     def __len__(self):
         return len(self.contexts)
+
+    @property
+    def fused(self) -> bool:
+        """Whether the columns advance in one set of launches (lwhip_batch_create accepted them)."""
+        return self._batch is not None
+
+    @property
+    def hprd_tables(self):
+        """Each column's hybrid-PRD tables (Context.hprd_tables; None for plain PRD), in column order."""
+        return [c.hprd_tables for c in self.contexts]
+
+    def sweep_shape(self):
+        """{'columns': [(workgroups of the full sweep, of the PRD rates pass)] per column, 'launch': the two gridDim.x values
+        the fused batch launches with for the current active set} (lwhip_batch_sweep_shape).  Hybrid-PRD columns differ in their
+        counts and the launch takes the largest; every other batch has equal counts."""
+        if self._batch is None:
+            raise RuntimeError('sweep_shape: the batch is not fused')
+        import numpy as np
+        lib = self.contexts[0].lib
+        per = np.zeros((len(self.contexts), 2), dtype=np.int32)
+        launch = np.zeros(2, dtype=np.int32)
+        _check(lib, lib.lwhip_batch_sweep_shape(self._batch, per.ctypes.data_as(abi.i32p), launch.ctypes.data_as(abi.i32p)),
+               'lwhip_batch_sweep_shape')
+        return {'columns': [(int(a), int(b)) for a, b in per], 'launch': (int(launch[0]), int(launch[1]))}
 
     def compute_profiles(self):
         """phi / wphi of every line of every column on the device (lwhip_batch_compute_profiles: one launch pair for
@@ -162,7 +224,9 @@ class ColumnBatch:
         if self._batch is not None:
             self.contexts[0].lib.lwhip_batch_destroy(self._batch)
             self._batch = None
-        for c in reversed(self.contexts):  # (borrowers of the first column's tables before the first column)
+        # (borrowers of the first column's tables before the first column; a column made with hprd=True frees its own hybrid-PRD
+        # tables behind its context, the first column's once its last borrower is gone)
+        for c in reversed(self.contexts):
             c.close()
         self.contexts = []
 

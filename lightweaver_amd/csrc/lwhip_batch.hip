@@ -40,6 +40,25 @@ static bool batch_plain_ok(const lwhip_batch* b, const TileDyn& dyn)
     return true;
 }
 
+// the geometry of the batch's one lane-sweep launch (prd: of the PRD rates pass): gridDim.x and the dynamic LDS.  Hybrid
+// columns differ in both: the largest of the active columns' (TileArgs::nWg ends a column's surplus workgroups; each column lays
+// out its LDS from its own maxCT).  Otherwise the first column's, which lwhip_batch_create has compared the others with.
+static void batch_sweep_geom(const lwhip_batch* b, bool prd, const std::vector<int32_t>& cols, int& wg, size_t& lds)
+{
+    const lwhip_context* c0 = b->ctxs[0];
+    wg = prd ? c0->nTileChunksPrd : c0->nTileChunks;
+    lds = 0;
+    if (!b->hybrid)
+        return;
+    wg = 0;
+    for (const int32_t i : cols)
+    {
+        const lwhip_context* c = b->ctxs[i];
+        wg = std::max(wg, prd ? c->nTileChunksPrd : c->nTileChunks);
+        lds = std::max(lds, lane_sweep_lds_bytes(prd ? c->htargsPrd : c->htargs, c->tileWaves));
+    }
+}
+
 // the argument lists of the active set (lwhip_batch_set_active; all columns: lwhip_batch_create) go to the device, ordered on the
 // batch's stream behind the launches that read the last set.  (The apply blocks follow in the next
 // lwhip_batch_formal_sol_gamma_matrices: aValid is off.)
@@ -50,6 +69,8 @@ static int batch_refresh_lists(lwhip_batch* b)
     HIP_TRY(b->r.refresh(b->act, c0->stream));
     HIP_TRY(b->se.refresh(b->act, c0->stream));
     HIP_TRY(b->seRep.refresh(b->act, c0->stream));
+    if (b->hybrid)
+        HIP_TRY(b->zr.refresh(b->act, c0->stream));
     HIP_TRY(hipMemcpyAsync(b->colsAct.p, b->act.data(), b->act.size() * sizeof(int32_t), hipMemcpyHostToDevice, c0->stream));
     HIP_TRY(hipStreamSynchronize(c0->stream)); // (what the copies read changes with the next set; a change of set is rare)
     return LWHIP_OK;
@@ -205,13 +226,20 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
         if (c->deterministic)
             return fail(LWHIP_ERR_UNSUPPORTED, "batch_create: the fused batch sums by atomics (a context made with LWHIP_OPT_DETERMINISTIC "
                                                "iterates on its own)");
-        if (c->device != c0->device || c->Ns != c0->Ns || c->Nla != c0->Nla
-            || c->Nrays != c0->Nrays || c->Ntrans != c0->Ntrans || c->Natom != c0->Natom || c->nTiles != c0->nTiles
-            || c->nTileChunks != c0->nTileChunks || c->nPostChunks != c0->nPostChunks || c->tileCap != c0->tileCap
-            || c->tileFuse != c0->tileFuse || c->tileWaves != c0->tileWaves || c->maxCTTile != c0->maxCTTile
-            || c->laneSweep != c0->laneSweep
-            || c->maxL != c0->maxL || c->maxC != c0->maxC
-            || c->NlevTot != c0->NlevTot || c->prob.formalSolver != c0->prob.formalSolver)
+        // what the one launch fixes for every column ...
+        const bool launchDiffers = c->device != c0->device || c->Ns != c0->Ns || c->Nla != c0->Nla || c->Nrays != c0->Nrays
+                                   || c->Ntrans != c0->Ntrans || c->Natom != c0->Natom || c->tileCap != c0->tileCap
+                                   || c->tileFuse != c0->tileFuse || c->tileWaves != c0->tileWaves || c->laneSweep != c0->laneSweep
+                                   || c->maxL != c0->maxL || c->maxC != c0->maxC || c->NlevTot != c0->NlevTot
+                                   || c->prob.formalSolver != c0->prob.formalSolver;
+        // ... and the counts that follow a hybrid column's own velocity field (hasPrd of its wavelength headers is part of a
+        // tile's identity): free when every column is hybrid and on the lane sweep, whose workgroups know their column's count
+        const bool countsDiffer = c->nTiles != c0->nTiles || c->nTileChunks != c0->nTileChunks || c->nPostChunks != c0->nPostChunks
+                                  || c->maxCTTile != c0->maxCTTile;
+        if ((c->hprd != nullptr) != (c0->hprd != nullptr))
+            return fail(LWHIP_ERR_INVALID, "batch_create: hybrid-PRD columns (lwhip_options.hprd) and plain ones do not share a "
+                                           "batch: the sweep launch runs one instance for every column");
+        if (launchDiffers || (countsDiffer && !(c0->hprd && c0->laneSweep)))
             return fail(LWHIP_ERR_INVALID, "batch_create: the columns must share device, model atoms, wavelength grid "
                                            "and solver");
     }
@@ -231,6 +259,16 @@ int lwhip_batch_create(lwhip_context* const* ctxs, int n, lwhip_batch** out)
     auto b = std::make_unique<lwhip_batch>();
     b->ctxs.assign(ctxs, ctxs + n);
     b->ownStreams = before;
+    b->hybrid = c0->hprd != nullptr && c0->laneSweep;
+    if (b->hybrid)
+    {
+        HIP_TRY(b->zr.alloc(c0->mem, (size_t)n));
+        for (int i = 0; i < n; ++i)
+        {
+            b->zr.full[i] = ZeroArgs{ ctxs[i]->JRest.p, (uint64_t)ctxs[i]->JRest.n };
+            b->zrMax = std::max<uint64_t>(b->zrMax, ctxs[i]->JRest.n);
+        }
+    }
     HIP_TRY(b->ap.alloc(c0->mem, (size_t)n));
     HIP_TRY(b->r.alloc(c0->mem, (size_t)n));
     HIP_TRY(b->a.alloc(c0->mem, (size_t)n));
@@ -353,8 +391,16 @@ int lwhip_batch_formal_sol_gamma_matrices(lwhip_batch* b, int lambdaIterate, dou
     if (!c0->laneSweep) // (the lane sweep's tasks do their own pre-pass)
         HIP_TRY(launch_tile_pre(c0->dtargs.p, c0->htargs, c0->nTiles, apL, nAct, c0->stream));
     if (c0->laneSweep)
-        HIP_TRY(launch_lane_sweep(c0->dtargs.p, c0->htargs, dyn, c0->prob.formalSolver, true, c0->nTileChunks, c0->tileWaves, apL, nAct,
-                                  c0->stream, batch_plain_ok(b, dyn)));
+    {
+        // hybrid PRD: the rest-frame mean intensity is rebuilt by every pass that updates J (run_sweep of a lone context)
+        if (b->hybrid)
+            HIP_TRY(launch_batch_zero_jrest(b->zr.dev.p, b->zrMax, nAct, c0->stream));
+        int wg = 0;
+        size_t lds = 0;
+        batch_sweep_geom(b, false, b->act, wg, lds);
+        HIP_TRY(launch_lane_sweep(c0->dtargs.p, c0->htargs, dyn, c0->prob.formalSolver, true, wg, c0->tileWaves, apL, nAct, c0->stream,
+                                  batch_plain_ok(b, dyn), lds));
+    }
     else
     {
         HIP_TRY(launch_tile_sweep(c0->dtargs.p, c0->htargs, dyn, c0->prob.formalSolver, c0->tileCap, true, fuse, c0->nTileChunks,
@@ -404,6 +450,27 @@ int lwhip_batch_sweep_instance(lwhip_batch* b, int32_t out[4])
     out[1] = 0;
     out[2] = lanes ? 1 : 0;
     out[3] = sw ? 1 : 0;
+    return LWHIP_OK;
+}
+
+int lwhip_batch_sweep_shape(lwhip_batch* b, int32_t* perColumn, int32_t launch[2])
+{
+    if (!b || b->ctxs.empty() || !perColumn || !launch)
+        return fail(LWHIP_ERR_INVALID, "batch_sweep_shape: null argument");
+    const lwhip_context* c0 = b->ctxs[0];
+    const bool lanes = c0->laneSweep && c0->tiled;
+    for (size_t i = 0; i < b->ctxs.size(); ++i)
+    {
+        perColumn[2 * i] = b->ctxs[i]->nTileChunks;
+        perColumn[2 * i + 1] = b->ctxs[i]->nTileChunksPrd;
+    }
+    // (what the active set's launches pass as gridDim.x; the fused PRD pass exists on the lane sweep only)
+    size_t lds = 0;
+    int wg = 0, wgPrd = 0;
+    batch_sweep_geom(b, false, b->act, wg, lds);
+    batch_sweep_geom(b, true, b->act, wgPrd, lds);
+    launch[0] = wg;
+    launch[1] = lanes ? wgPrd : 0;
     return LWHIP_OK;
 }
 
@@ -672,7 +739,7 @@ int lwhip_batch_nr_post_update(lwhip_batch* b, const lwhip_nr_args* perColumn, d
 }
 
 // ---- PRD sub-iterations of the active columns: lwhip_redistribute_prd of each, in one set of launches per sub-iteration --------
-// Per sub-iteration: scattering integral over the columns' lines back to back -> PRD rates pass (the BATCH lane sweep over the
+// Per sub-iteration: scattering integral over the columns' lines back to back -> (hybrid columns: their JRest to zero) -> PRD rates pass (the BATCH lane sweep over the
 // columns' dtargsPrd) -> stage 2 (sums, the pass's dJMax into prdTail) -> apply (the PRD lines' rates out) -> record
 // (batch_prd_conv_kernel).  A column stops by its own changes: its stop word, set by the record launch of the sub-iteration
 // that met the tolerance, makes its slice of every later launch return at once.
@@ -729,13 +796,18 @@ int lwhip_batch_redistribute_prd(lwhip_batch* b, int maxIter, double tol, lwhip_
         return fail(LWHIP_ERR_INVALID, "batch_redistribute_prd: null result");
     // ---- every refusal, before anything is queued ----
     const int Nprd = (int)c0->prdLines.size();
-    for (const lwhip_context* c : b->ctxs)
+    for (size_t i = 0; i < b->ctxs.size(); ++i)
     {
-        if (c->hprd)
-            return fail(LWHIP_ERR_UNSUPPORTED, "batch_redistribute_prd: hybrid-PRD columns iterate as contexts of their own");
+        const lwhip_context* c = b->ctxs[i];
         if (c->prdDetailed)
             return fail(LWHIP_ERR_UNSUPPORTED, "batch_redistribute_prd: columns made with LWHIP_OPT_PRD_DETAILED iterate as contexts of "
                                                "their own");
+        // (columns on one table set share ONE host JRest: their results cannot both be delivered)
+        for (size_t j = 0; c->hprd && j < i; ++j)
+            if (b->ctxs[j]->hprd == c->hprd)
+                return fail(LWHIP_ERR_UNSUPPORTED, "batch_redistribute_prd: columns " + std::to_string(j) + " and " + std::to_string(i)
+                                                       + " share one set of hybrid-PRD tables (lwhip_hprd) and with it one JRest: each "
+                                                         "column needs tables of its own");
     }
     for (const int32_t i : b->act)
     {
@@ -743,7 +815,9 @@ int lwhip_batch_redistribute_prd(lwhip_batch* b, int maxIter, double tol, lwhip_
         const std::string col = "batch_redistribute_prd: column " + std::to_string(i);
         if (c->partialPending || c->prdPending)
             return fail(LWHIP_ERR_INVALID, col + " has a split iteration or sub-iteration pending");
-        if ((int)c->prdLines.size() != Nprd || c->nTileChunksPrd != c0->nTileChunksPrd || c->laneSplitPrd != c0->laneSplitPrd)
+        // (hybrid columns: their PRD passes differ in workgroup count and split, which each workgroup reads from its own column)
+        if ((int)c->prdLines.size() != Nprd
+            || (!b->hybrid && (c->nTileChunksPrd != c0->nTileChunksPrd || c->laneSplitPrd != c0->laneSplitPrd)))
             return fail(LWHIP_ERR_INVALID, col + " does not share the first column's PRD lines");
         for (int q = 0; q < Nprd; ++q)
             if (c->trans[c->prdLines[q]].t.Nred - c->trans[c->prdLines[q]].t.Nblue
@@ -841,6 +915,9 @@ int lwhip_batch_redistribute_prd(lwhip_batch* b, int maxIter, double tol, lwhip_
     ca.stop = stop;
     ca.tol = tol;
     ca.Nprd = Nprd;
+    int wgPrd = 0;
+    size_t ldsPrd = 0;
+    batch_sweep_geom(b, true, b->act, wgPrd, ldsPrd);
     std::vector<PrdLineArgs> lines((size_t)nAct * Nprd);
     std::vector<int> count(nAct, 0);
     std::vector<char> done(nAct, 0);
@@ -872,8 +949,11 @@ int lwhip_batch_redistribute_prd(lwhip_batch* b, int maxIter, double tol, lwhip_
             if (stsc != LWHIP_OK)
                 return stsc;
             dyn.stopIter = it;
-            HIP_TRY(launch_lane_sweep(c0->dtargsPrd.p, c0->htargsPrd, dyn, c0->prob.formalSolver, true, c0->nTileChunksPrd, c0->tileWaves,
-                                      b->apPrd.dev.p, nAct, c0->stream, plain));
+            // hybrid PRD: the scatter launch has read JRest, the rates pass rebuilds it (a stopped column keeps its own)
+            if (b->hybrid)
+                HIP_TRY(launch_batch_zero_jrest(b->zr.dev.p, b->zrMax, nAct, c0->stream, stop, it));
+            HIP_TRY(launch_lane_sweep(c0->dtargsPrd.p, c0->htargsPrd, dyn, c0->prob.formalSolver, true, wgPrd, c0->tileWaves,
+                                      b->apPrd.dev.p, nAct, c0->stream, plain, ldsPrd));
             r0.stopIter = it;
             HIP_TRY(launch_reduce_sum(r0, c0->stream, b->rPrd.dev.p, nAct));
             a0.prdIter = it;

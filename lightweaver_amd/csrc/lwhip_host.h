@@ -975,6 +975,12 @@ struct lwhip_batch
     DevBuf<double> prdRec;
     int prdRecNprd = -1;                 // the line count prdRec was sized for
     PinnedBlock prdRecPinned;
+    // hybrid PRD (every column made with lwhip_options.hprd, or none): the columns' wavelength headers and with them their tile
+    // lists follow their own velocity fields, so their sweep launches differ in their workgroup counts (batch_sweep_geom); zr:
+    // each column's JRest, cleared in one launch in front of every pass that rebuilds it
+    bool hybrid = false;
+    ColList<ZeroArgs> zr;
+    uint64_t zrMax = 0;                  // the longest JRest, in doubles
     NgState ng;                                // lwhip_batch_ng_configure: Ng acceleration of every column
     DevBuf<VoigtLineArgs> voigtList; // lines of the columns whose profiles are being recomputed
     DevBuf<RetileArgs> retileList;   // ... and their retile arguments

@@ -304,7 +304,9 @@ struct TileArgs
     int32_t laneD, laneLR, laneR, laneLRD;
     const int32_t* chunkOrder;     // lane sweep: workgroup -> chunk (dispatch order), or null
     const int32_t* chunkSplit;     // lane sweep: per chunk the split factor of its tiles' rays (overrides laneSplit), or null
-    int32_t laneSplit, _padLS;      // S = 1, 2, 4: a tile's rays are split over S wavefronts of its workgroup (small problems)
+    int32_t laneSplit;             // S = 1, 2, 4: a tile's rays are split over S wavefronts of its workgroup (small problems)
+    int32_t nWg;                   // lane sweep: workgroups of this list's own launch = entries of laneWg (a column batch launches
+                                   // the largest count of its columns; a column's workgroups beyond its own return at once)
     const double* phi;             // [line][lt][Nmu][2][Ns] pool (the caller's layout)
     const double* geoT;            // [4][laneLRD + 2], entry k + 1: |h_k - h_k+1|, its reciprocal, 1 / (|h_k-1 - h_k| + |h_k - h_k+1|), 1 / T_k
     const DevPostProg* postProg;   // [nTiles]
@@ -383,8 +385,11 @@ inline size_t lane_dep_arena_doubles(int NlevTot, int Nline, int Ncont, int Ns, 
 }
 // plainOk: the launch may take the plain instance (no depth data, no z-plane rows, no CALLABLE boundary compiled in) if
 // lane_sweep_plain says its argument block and flags qualify; a fused batch passes true only if every column qualifies
+// A batch whose columns differ in their workgroup counts (hybrid PRD): nChunks is the largest count (TileArgs::nWg of each column
+// ends its surplus workgroups) and ldsBytes the largest lane_sweep_lds_bytes of the columns; 0: hostArgs' own.
 hipError_t launch_lane_sweep(const TileArgs* devArgs, const TileArgs& hostArgs, const TileDyn& dyn, int solver, bool rates,
-                             int nChunks, int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream, bool plainOk);
+                             int nChunks, int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream, bool plainOk,
+                             size_t ldsBytes = 0);
 bool lane_sweep_plain(const TileArgs& hostArgs, const TileDyn& dyn, int solver, bool rates);
 // Diagnosis (LWHIP_DEBUG=1 LWHIP_SCRATCH_POISON=1): fills every wavefront slot's private-segment ("scratch") memory with a
 // finite pattern in front of a kernel launch (lwhip_lanesweep.hip: scratch_poison_kernel).  Nothing otherwise.
@@ -667,6 +672,15 @@ hipError_t launch_batch_prd_conv(const BatchPrdConvArgs& a, int nActive, hipStre
 // ... and in front of a call's first sub-iteration: dJ of every listed column to zero (the PRD rates pass writes its own
 // wavelengths only; list: the columns' stage-2 blocks, whose dJ and Nla are used)
 hipError_t launch_batch_zero_dj(const ReduceArgs* list, int maxNla, int nActive, hipStream_t stream);
+// hybrid-PRD batches: the rest-frame mean intensity of every active column to zero in one launch, in front of the pass that
+// rebuilds it (a lone context: the fill in run_sweep); a column whose stop word says it has stopped keeps its JRest
+struct ZeroArgs
+{
+    double* p;
+    uint64_t n; // doubles
+};
+hipError_t launch_batch_zero_jrest(const ZeroArgs* list, uint64_t maxN, int nActive, hipStream_t stream, const int32_t* stopCtl = nullptr,
+                                   int stopIter = 0);
 hipError_t launch_peer_publish(const PeerPublishArgs& a, hipStream_t stream);
 // self-test of the exchange: fill `buf` with the rank's pattern / wait for the world's flags (bounded by spinLimit polls) and
 // compare every slot with its rank's pattern; *result = 0 ok, 1 a flag never came, 2 a slot holds something else

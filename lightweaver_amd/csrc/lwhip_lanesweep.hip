@@ -3232,11 +3232,15 @@ __global__ void __launch_bounds__(LS_MAX_WAVES * 64) __attribute__((amdgpu_waves
         if (stopAt != 0 && stopAt < dyn.stopIter)
             return;
     }
+    const TileArgs* __restrict__ ap = BATCH ? apList[blockIdx.y] : ap0;
+    const CONST_AS TileArgs& a = *(const CONST_AS TileArgs*)ap;
+    // (a batch of hybrid-PRD columns launches the largest workgroup count of its columns: this column has fewer -- nothing to
+    // do.  Only the instances with the hybrid paths can meet such a launch; the others are compiled without the compare.)
+    if (BATCH && (MODE & 2) != 0 && (int)blockIdx.x >= __builtin_amdgcn_readfirstlane(a.nWg))
+        return;
     LS_T(tk0);
     constexpr bool RATES = (MODE & 1) != 0;
     extern __shared__ double lds[];
-    const TileArgs* __restrict__ ap = BATCH ? apList[blockIdx.y] : ap0;
-    const CONST_AS TileArgs& a = *(const CONST_AS TileArgs*)ap;
     const int Ns = a.Ns, LRD = a.laneLRD;
     const int maxCT = a.maxCT;
     const int t = threadIdx.x;
@@ -3455,9 +3459,10 @@ namespace
 {
 template <int SOLVER, int D, int MODE>
 hipError_t launch_ls_t(const TileArgs* devArgs, const TileArgs& a, const TileDyn& dyn, int nChunks, int waves,
-                       const TileArgs* const* apList, int nBatch, hipStream_t stream)
+                       const TileArgs* const* apList, int nBatch, hipStream_t stream, size_t ldsBytes)
 {
-    const size_t lds = lane_sweep_lds_bytes(a, waves);
+    // (ldsBytes: the largest need among a batch's columns -- each lays out its own offsets from its own maxCT)
+    const size_t lds = std::max(lane_sweep_lds_bytes(a, waves), ldsBytes);
     if (lds > 48 * 1024)
     {
         // (once per kernel instance, device and size: the call is a driver round trip of a microsecond or two in front of
@@ -3537,7 +3542,7 @@ bool lane_sweep_plain(const TileArgs& a, const TileDyn& dyn, int solver, bool ra
 
 #ifndef LS_ISA_ONLY
 hipError_t launch_lane_sweep(const TileArgs* devArgs, const TileArgs& a, const TileDyn& dyn, int solver, bool rates, int nChunks,
-                             int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream, bool plainOk)
+                             int waves, const TileArgs* const* apList, int nBatch, hipStream_t stream, bool plainOk, size_t ldsBytes)
 {
     if (nChunks <= 0)
         return hipSuccess;
@@ -3545,22 +3550,22 @@ hipError_t launch_lane_sweep(const TileArgs* devArgs, const TileArgs& a, const T
         return hipErrorInvalidValue;
     // (plainOk: the caller's switch, and for a fused batch that every column qualifies; `a` is then column 0's block)
     if (plainOk && lane_sweep_plain(a, dyn, solver, rates))
-        return launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 5>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream);
+        return launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 5>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes);
     // (the linear and BESSER solvers: one instance each per rates / no rates, with the hybrid-PRD paths compiled in)
     if (solver == LWHIP_FS_LINEAR_1D)
-        return rates ? launch_ls_t<LWHIP_FS_LINEAR_1D, 4, 3>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream)
-                     : launch_ls_t<LWHIP_FS_LINEAR_1D, 4, 2>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream);
+        return rates ? launch_ls_t<LWHIP_FS_LINEAR_1D, 4, 3>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes)
+                     : launch_ls_t<LWHIP_FS_LINEAR_1D, 4, 2>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes);
     if (solver == LWHIP_FS_BESSER_1D)
-        return rates ? launch_ls_t<LWHIP_FS_BESSER_1D, 4, 3>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream)
-                     : launch_ls_t<LWHIP_FS_BESSER_1D, 4, 2>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream);
+        return rates ? launch_ls_t<LWHIP_FS_BESSER_1D, 4, 3>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes)
+                     : launch_ls_t<LWHIP_FS_BESSER_1D, 4, 2>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes);
     if (solver != LWHIP_FS_BEZIER3_1D)
         return hipErrorInvalidValue;
     const bool hprd = a.hRho != nullptr || a.hJOff != nullptr;
     if (rates)
-        return hprd ? launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 3>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream)
-                    : launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 1>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream);
-    return hprd ? launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 2>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream)
-                : launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 0>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream);
+        return hprd ? launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 3>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes)
+                    : launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 1>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes);
+    return hprd ? launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 2>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes)
+                : launch_ls_t<LWHIP_FS_BEZIER3_1D, 4, 0>(devArgs, a, dyn, nChunks, waves, apList, nBatch, stream, ldsBytes);
 }
 #endif
 }

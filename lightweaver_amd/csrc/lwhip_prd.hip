@@ -544,6 +544,41 @@ hipError_t launch_batch_zero_dj(const ReduceArgs* list, int maxNla, int nActive,
     return hipGetLastError();
 }
 
+// Hybrid-PRD batches: JRest of the column at list position blockIdx.y to zero, 16 bytes per store (one double in front where
+// the buffer starts on an odd double, one behind where an odd count is left).  The column's stop word as in every launch of a
+// sub-iteration: a column that stopped earlier keeps the JRest of its own stop -- nothing would rebuild it.
+__global__ void __launch_bounds__(256) batch_zero_jrest_kernel(const ZeroArgs* __restrict__ list, const int32_t* stopCtl, const int stopIter)
+{
+    dbg_poison_lds();
+    if (prd_stopped(stopCtl, blockIdx.y, stopIter))
+        return;
+    const ZeroArgs z = ld_c(CTAB(ZeroArgs, list) + blockIdx.y);
+    if (!z.p || z.n == 0)
+        return;
+    const uint64_t head = ((uintptr_t)z.p >> 3) & 1;
+    double2* v = reinterpret_cast<double2*>(z.p + head);
+    const uint64_t nv = (z.n - head) >> 1; // (elements head .. head + 2 nv - 1 <= n - 1)
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (uint64_t)gridDim.x * blockDim.x)
+        v[i] = make_double2(0.0, 0.0);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+    {
+        if (head)
+            z.p[0] = 0.0;
+        if ((z.n - head) & 1)
+            z.p[z.n - 1] = 0.0;
+    }
+}
+hipError_t launch_batch_zero_jrest(const ZeroArgs* list, uint64_t maxN, int nActive, hipStream_t stream, const int32_t* stopCtl, int stopIter)
+{
+    if (nActive <= 0 || maxN == 0)
+        return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((maxN / 2 + 255) / 256 + 1, 256);
+    for (int off = 0; off < nActive; off += 32768) // (the launch geometry allows 65 535 entries per grid dimension)
+        LWHIP_LAUNCH(batch_zero_jrest_kernel, dim3(blocks, std::min(32768, nActive - off)), dim3(256), 0, stream, list + off,
+                     stopCtl ? stopCtl + off : nullptr, stopIter);
+    return hipGetLastError();
+}
+
 hipError_t launch_prd_scatter(const PrdLineArgs* devList, const PrdLineArgs* hostList, int nLines, hipStream_t stream, bool reduceChange,
                               const int32_t* stopCtl, int stopIter)
 {

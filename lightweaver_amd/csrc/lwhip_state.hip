@@ -462,6 +462,7 @@ int build_tile_args(lwhip_context* c)
         a.laneR = c->laneR;
         a.laneLRD = c->laneLR * c->laneD;
         a.laneSplit = c->laneSplit;
+        a.nWg = c->nTileChunks;
         a.phi = c->phi.p;
         a.geoT = c->geoT.p;
         a.postProg = c->postProg.p;
@@ -524,6 +525,7 @@ int build_tile_args(lwhip_context* c)
         a.chunkOrder = nullptr;
         a.chunkSplit = nullptr;
         a.laneSplit = c->laneSplitPrd;
+        a.nWg = c->nTileChunksPrd;
         a.slotTr = c->tileSlotTrPrd.p;
         a.postChunkTile = c->postChunkTilePrd.p;
         a.laneWg = c->laneWgPrd.p;
