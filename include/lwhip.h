@@ -824,7 +824,8 @@ typedef struct lwhip_rays {
     double* depthEta;       /* what DepthData holds for the to-observer direction                                   */
     double* depthI;
 } lwhip_rays;
-/* Refusals, before anything is queued: no device LWHIP_ERR_DEVICE; a 2D context, hybrid PRD tables, another formal solver
+/* Refusals, before anything is queued: no device LWHIP_ERR_DEVICE; a 2D context, hybrid PRD tables (served by
+ * lwhip_compute_rays_hprd below), another formal solver
  * than piecewise_bezier3_1d, Nmu above LWHIP_RAYS_MAX_MU: LWHIP_ERR_UNSUPPORTED; a direction
  * cosine outside (0, 1], a range outside the context's rows, a CALLABLE lower boundary without lowerBc, a line without aDamp,
  * neither vz nor vlosMu, one or two of the three depth arrays: LWHIP_ERR_INVALID.  The call returns when the outputs are
@@ -848,7 +849,8 @@ int lwhip_batch_compute_rays(lwhip_batch* batch, const lwhip_rays* perColumn);
  *   - the background and the continuum cross-sections on the new grid come from the model layer: here they are inputs.
  * Then chi, S and the piecewise_bezier3_1d march of lwhip_compute_rays (the same kernel, reading the request's rows).  Nothing of
  * the context changes, nothing is created; the request crosses in one copy, the outputs come back in one.  All pointers are host
- * pointers.  Not served: Stokes, 2D, wavelength shards, hybrid PRD, a PRD refinement on the new grid. */
+ * pointers.  Not served: Stokes, 2D, wavelength shards, a PRD refinement on the new grid; hybrid PRD by
+ * lwhip_compute_rays_grid_hprd below. */
 typedef struct lwhip_rays_grid {
     lwhip_rays rays;              /* Nmu, muz, vz, I, the depth arrays as for lwhip_compute_rays with Nla = Nwave (lowerBc
                                    * [Nwave, Nmu], I [Nwave, Nmu], depth arrays [Nwave, Nmu, Nspace]); laStart = laEnd = 0 */
@@ -873,6 +875,30 @@ int lwhip_compute_rays_grid(lwhip_context* ctx, const lwhip_rays_grid* rays);
  * depth arrays are those of column 0 (LWHIP_ERR_INVALID otherwise, the column named); the backgrounds, cross-sections,
  * directions, vz and lowerBc are each column's own.  Each column's results are the bits of lwhip_compute_rays_grid on it. */
 int lwhip_batch_compute_rays_grid(lwhip_batch* batch, const lwhip_rays_grid* perColumn);
+
+/* ---- observer rays of a hybrid-PRD context (1D) ------------------------------------------------------------------------------
+ * The four calls above refuse a context made with lwhip_options.hprd: rho of a line of its hybrid list (lwhip_hprd.lineAtom /
+ * lineTrans) is not the row's.  The reference's second context runs configure_hprd_coeffs on the new rays' vlosMu
+ * (LwMiddleLayer.pyx:2822-2826, Prd.cpp:899-939) and Transition::uv interpolates the rest-frame rhoPrd for each ray
+ * (LwTransition.hpp:116-127).  These four do that where they gather, as they do phi -- no table is built or stored.  For a line of
+ * the hybrid list at its own-grid index lt, direction m and depth k, with w [nlt] the line's own grid:
+ *     lambdaRest = w[lt] * (1 + muz[m] v_z[k] / c)
+ *     (i0, i1, frac): lambdaRest <= w[0]: (0, 1, 0); lambdaRest >= w[nlt - 1]: (nlt - 2, nlt - 1, 1); else i0 the last node
+ *                     <= lambdaRest, i1 = i0 + 1, frac = (lambdaRest - w[i0]) / (w[i1] - w[i0])
+ *     rho = (1 - frac) rhoPrd(i0, k) + frac rhoPrd(i1, k),    Vji = (gij Vij) rho
+ * every operation rounded once (no fused multiply-add), so the coefficient is the bits of the table entry the reference would
+ * hold.  A PRD line outside the hybrid list keeps rho by row.  On a new grid w is the request's grid (nlt = Nwave) and rhoPrd the
+ * rho interpolated onto it, which is what the reference's second context holds.
+ * Requests, staging, launch shape, outputs and depth arrays are those of the plain calls; nothing of the context changes (I, J,
+ * rho, JRest, the tables, phi, the tile lists).  The stored-grid call serves a wavelength shard for its own rows: under hybrid
+ * PRD every shard holds rho of each line's whole grid.
+ * Refusals, before anything is queued and with the outputs untouched: what the corresponding plain call refuses, except the
+ * hybrid tables; a context (or a column, which is named) WITHOUT hybrid tables: LWHIP_ERR_INVALID.
+ * Not served: full Stokes, a PRD refinement on the new grid, 2D. */
+int lwhip_compute_rays_hprd(lwhip_context* ctx, const lwhip_rays* rays);
+int lwhip_batch_compute_rays_hprd(lwhip_batch* batch, const lwhip_rays* perColumn);
+int lwhip_compute_rays_grid_hprd(lwhip_context* ctx, const lwhip_rays_grid* rays);
+int lwhip_batch_compute_rays_grid_hprd(lwhip_batch* batch, const lwhip_rays_grid* perColumn);
 
 /* ---- full Stokes along observer rays (1D) --------------------------------------------------------------------------------
  * LwContext.compute_rays(mus, stokes=True) (Source/LwMiddleLayer.pyx:3898-4002) from the state resident on the device: for

@@ -316,6 +316,10 @@ SYMBOLS = [
     ('lwhip_rays_grid_active', C.c_int, [ctx_p, f64p, C.c_int, i32p]),
     ('lwhip_compute_rays_grid', C.c_int, [ctx_p, C.POINTER(lwhip_rays_grid)]),
     ('lwhip_batch_compute_rays_grid', C.c_int, [C.c_void_p, C.POINTER(lwhip_rays_grid)]),
+    ('lwhip_compute_rays_hprd', C.c_int, [ctx_p, C.POINTER(lwhip_rays)]),
+    ('lwhip_batch_compute_rays_hprd', C.c_int, [C.c_void_p, C.POINTER(lwhip_rays)]),
+    ('lwhip_compute_rays_grid_hprd', C.c_int, [ctx_p, C.POINTER(lwhip_rays_grid)]),
+    ('lwhip_batch_compute_rays_grid_hprd', C.c_int, [C.c_void_p, C.POINTER(lwhip_rays_grid)]),
     ('lwhip_compute_stokes_rays', C.c_int, [ctx_p, C.POINTER(lwhip_stokes_rays)]),
     ('lwhip_batch_compute_stokes_rays', C.c_int, [C.c_void_p, C.POINTER(lwhip_stokes_rays)]),
     ('lwhip_compute_rays_2d', C.c_int, [ctx_p, C.POINTER(lwhip_rays2d)]),

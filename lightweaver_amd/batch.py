@@ -688,26 +688,11 @@ class ColumnBatch:
         from .context import RaysResult
         n = len(self.contexts)
         per = lambda a, i: None if a is None else a[i]  # noqa: E731
-        if wavelengths is not None:
-            if stokes:
-                raise ValueError('compute_rays: stokes=True is not served on a new wavelength grid')
-            if laStart or laEnd:
-                raise ValueError('compute_rays: laStart / laEnd select rows of the context\'s own grid: leave them 0 with wavelengths')
-            if background is None or len(background) != n or (contAlpha is not None and len(contAlpha) != n):
-                raise ValueError('compute_rays: wavelengths needs background and contAlpha per column')
-            reqs = [c._rays_grid_request(mus, wavelengths, background[i], per(contAlpha, i), per(vz, i), per(lowerBc, i),
-                                         depthData) for i, c in enumerate(self.contexts)]
-            if self._batch is not None:
-                lib = self.contexts[0].lib
-                arr = (abi.lwhip_rays_grid * n)(*[q for q, _, _ in reqs])
-                _check(lib, lib.lwhip_batch_compute_rays_grid(self._batch, arr), 'lwhip_batch_compute_rays_grid')
-            else:
-                for c, (q, _, _) in zip(self.contexts, reqs):
-                    _check(c.lib, c.lib.lwhip_compute_rays_grid(c._h, C.byref(q)), 'lwhip_compute_rays_grid')
-            return self._stack_rays([o for _, o, _ in reqs], depthData)
-        if background is not None or contAlpha is not None:
-            raise ValueError('compute_rays: background / contAlpha go with wavelengths')
         if stokes:
+            if wavelengths is not None:
+                raise ValueError('compute_rays: stokes=True is not served on a new wavelength grid')
+            if background is not None or contAlpha is not None:
+                raise ValueError('compute_rays: background / contAlpha go with wavelengths')
             if depthData:
                 raise ValueError('compute_rays: no depthData with stokes=True')
             reqs = [c._stokes_rays_request(mus, laStart, laEnd, per(vz, i), per(lowerBc, i), mux, muy)
@@ -720,15 +705,42 @@ class ColumnBatch:
                 for c, (q, _, _) in zip(self.contexts, reqs):
                     _check(c.lib, c.lib.lwhip_compute_stokes_rays(c._h, C.byref(q)), 'lwhip_compute_stokes_rays')
             return np.stack([o for _, o, _ in reqs]) if reqs else np.zeros((0, 4, 0, 0))
-        reqs = [c._rays_request(mus, laStart, laEnd, per(vz, i), per(lowerBc, i), depthData)
-                for i, c in enumerate(self.contexts)]
+        return self._rays_call('', mus, laStart, laEnd, vz, lowerBc, depthData, wavelengths, background, contAlpha)
+
+    def compute_rays_hprd(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False, wavelengths=None,
+                          background=None, contAlpha=None):
+        """Context.compute_rays_hprd of every column of a batch made with hprd=True, which compute_rays refuses
+        (lwhip_batch_compute_rays_hprd / lwhip_batch_compute_rays_grid_hprd; an unfused batch runs the columns one after
+        the other).  Arguments, per-column lists and results are compute_rays's; each column's rho is interpolated for its
+        own velocity field.  A column retired with set_active is served from the state of its stop iteration."""
+        return self._rays_call('_hprd', mus, laStart, laEnd, vz, lowerBc, depthData, wavelengths, background, contAlpha)
+
+    def _rays_call(self, sfx, mus, laStart, laEnd, vz, lowerBc, depthData, wavelengths, background, contAlpha):
+        """compute_rays (sfx '') / compute_rays_hprd (sfx '_hprd') of every column, on the stored grid or a new one."""
+        import ctypes as C
+        n = len(self.contexts)
+        per = lambda a, i: None if a is None else a[i]  # noqa: E731
+        if wavelengths is not None:
+            if laStart or laEnd:
+                raise ValueError('compute_rays: laStart / laEnd select rows of the context\'s own grid: leave them 0 with wavelengths')
+            if background is None or len(background) != n or (contAlpha is not None and len(contAlpha) != n):
+                raise ValueError('compute_rays: wavelengths needs background and contAlpha per column')
+            kind, one, many = abi.lwhip_rays_grid, 'lwhip_compute_rays_grid' + sfx, 'lwhip_batch_compute_rays_grid' + sfx
+            reqs = [c._rays_grid_request(mus, wavelengths, background[i], per(contAlpha, i), per(vz, i), per(lowerBc, i),
+                                         depthData) for i, c in enumerate(self.contexts)]
+        else:
+            if background is not None or contAlpha is not None:
+                raise ValueError('compute_rays: background / contAlpha go with wavelengths')
+            kind, one, many = abi.lwhip_rays, 'lwhip_compute_rays' + sfx, 'lwhip_batch_compute_rays' + sfx
+            reqs = [c._rays_request(mus, laStart, laEnd, per(vz, i), per(lowerBc, i), depthData)
+                    for i, c in enumerate(self.contexts)]
         if self._batch is not None:
             lib = self.contexts[0].lib
-            arr = (abi.lwhip_rays * n)(*[r for r, _, _ in reqs])
-            _check(lib, lib.lwhip_batch_compute_rays(self._batch, arr), 'lwhip_batch_compute_rays')
+            arr = (kind * n)(*[q for q, _, _ in reqs])
+            _check(lib, getattr(lib, many)(self._batch, arr), many)
         else:
-            for c, (r, _, _) in zip(self.contexts, reqs):
-                _check(c.lib, c.lib.lwhip_compute_rays(c._h, C.byref(r)), 'lwhip_compute_rays')
+            for c, (q, _, _) in zip(self.contexts, reqs):
+                _check(c.lib, getattr(c.lib, one)(c._h, C.byref(q)), one)
         return self._stack_rays([o for _, o, _ in reqs], depthData)
 
     @staticmethod

@@ -603,31 +603,46 @@ class Context:
         interpolated linearly in wavelength on the device from the resident arrays (numpy.interp, end values held).  What the
         reference's model layer supplies is an input here: background = (chi, eta, sca), each [Nwave, Nspace], and
         contAlpha = {(atomIdx, transIdx): alpha [Nwave]} for every active continuum.  laStart / laEnd must stay 0; lowerBc is
-        [Nwave, Nmu]; the results have Nwave for Nla.  Not with stokes=True, not on a shard, a 2D or hybrid-PRD context."""
-        if wavelengths is not None:
-            if stokes:
-                raise ValueError('compute_rays: stokes=True is not served on a new wavelength grid')
-            if laStart or laEnd:
-                raise ValueError('compute_rays: laStart / laEnd select rows of the context\'s own grid: leave them 0 with wavelengths')
-            q, out, keep = self._rays_grid_request(mus, wavelengths, background, contAlpha, vz, lowerBc, depthData)
-            _check(self.lib, self.lib.lwhip_compute_rays_grid(self._h, C.byref(q)), 'lwhip_compute_rays_grid')
-            del keep
-            if squeeze and np.ndim(mus) == 0:
-                out.I = out.I[:, 0]
-                if depthData:
-                    out.chi, out.eta, out.Idepth = out.chi[:, 0], out.eta[:, 0], out.Idepth[:, 0]
-            return out if depthData else out.I
-        if background is not None or contAlpha is not None:
-            raise ValueError('compute_rays: background / contAlpha go with wavelengths')
+        [Nwave, Nmu]; the results have Nwave for Nla.  Not with stokes=True, not on a shard or a 2D context.
+        A hybrid-PRD context (hprd=True) is refused here and served by compute_rays_hprd."""
         if stokes:
+            if wavelengths is not None:
+                raise ValueError('compute_rays: stokes=True is not served on a new wavelength grid')
+            if background is not None or contAlpha is not None:
+                raise ValueError('compute_rays: background / contAlpha go with wavelengths')
             if depthData:
                 raise ValueError('compute_rays: no depthData with stokes=True')
             q, out, keep = self._stokes_rays_request(mus, laStart, laEnd, vz, lowerBc, mux, muy)
             _check(self.lib, self.lib.lwhip_compute_stokes_rays(self._h, C.byref(q)), 'lwhip_compute_stokes_rays')
             del keep
             return out[:, :, 0] if squeeze and np.ndim(mus) == 0 else out
-        r, out, keep = self._rays_request(mus, laStart, laEnd, vz, lowerBc, depthData)
-        _check(self.lib, self.lib.lwhip_compute_rays(self._h, C.byref(r)), 'lwhip_compute_rays')
+        return self._rays_call('', mus, laStart, laEnd, vz, lowerBc, depthData, squeeze, wavelengths, background, contAlpha)
+
+    def compute_rays_hprd(self, mus=1.0, laStart=0, laEnd=0, vz=None, lowerBc=None, depthData=False, squeeze=True,
+                          wavelengths=None, background=None, contAlpha=None):
+        """compute_rays of a context made with hprd=True (lwhip_compute_rays_hprd / lwhip_compute_rays_grid_hprd), which
+        compute_rays refuses: rho of a line of the hybrid list is not the row's but, for every ray and depth, the rest-frame
+        rho of the line interpolated at lambda (1 + mu v_z / c) -- the coefficient configure_hprd_coeffs would tabulate for
+        the new rays (Prd.cpp:899-939), formed inside the kernel as the profile is, and applied as Transition::uv applies it
+        (LwTransition.hpp:116-127).  A PRD line outside the list (a detailed atom's without prdDetailed) keeps rho by row.
+        Arguments and results are compute_rays's; with `wavelengths` the line's grid is the new one and rho the one
+        interpolated onto it, as in the reference's second context.  A wavelength shard serves its own rows on the stored
+        grid.  Nothing of the context changes.  Refuses a context without hybrid tables; no stokes, no refinePrd, no 2D."""
+        return self._rays_call('_hprd', mus, laStart, laEnd, vz, lowerBc, depthData, squeeze, wavelengths, background, contAlpha)
+
+    def _rays_call(self, sfx, mus, laStart, laEnd, vz, lowerBc, depthData, squeeze, wavelengths, background, contAlpha):
+        """compute_rays (sfx '') / compute_rays_hprd (sfx '_hprd') on the stored grid or a new one."""
+        if wavelengths is not None:
+            if laStart or laEnd:
+                raise ValueError('compute_rays: laStart / laEnd select rows of the context\'s own grid: leave them 0 with wavelengths')
+            name = 'lwhip_compute_rays_grid' + sfx
+            q, out, keep = self._rays_grid_request(mus, wavelengths, background, contAlpha, vz, lowerBc, depthData)
+        else:
+            if background is not None or contAlpha is not None:
+                raise ValueError('compute_rays: background / contAlpha go with wavelengths')
+            name = 'lwhip_compute_rays' + sfx
+            q, out, keep = self._rays_request(mus, laStart, laEnd, vz, lowerBc, depthData)
+        _check(self.lib, getattr(self.lib, name)(self._h, C.byref(q)), name)
         del keep
         if squeeze and np.ndim(mus) == 0:
             out.I = out.I[:, 0]

@@ -89,6 +89,45 @@ DEVINL double d_planck(double T, double lambda)
     return (x <= 150.0) ? twohnu3_c2 / (exp(x) - 1.0) : 0.0;
 }
 
+// The hybrid-PRD rho coefficient of lambdaRest in a line's own grid w[0, nlt), nlt >= 2 (configure_hprd_coeffs, Prd.cpp:906-939):
+// the two clamped ends, else upper_bound - 1 by bisection.  A difference and a quotient, each rounded once: nothing here can
+// contract, whatever the including unit's setting.  Shared by the table build (lwhip_hprd.hip) and the observer rays, which
+// form the coefficient of a new direction where they gather (lwhip_rays.hip).
+DEVINL void d_hprd_rho_coeff(const double* __restrict__ w, int nlt, double lambdaRest, int& i0, int& i1, double& frac)
+{
+    if (lambdaRest <= w[0])
+    {
+        frac = 0.0;
+        i0 = 0;
+        i1 = 1;
+    }
+    else if (lambdaRest >= w[nlt - 1])
+    {
+        frac = 1.0;
+        i0 = nlt - 2;
+        i1 = nlt - 1;
+    }
+    else
+    {
+        // std::upper_bound - 1: the last element <= lambdaRest
+        int lo = 0, hi = nlt;
+        while (lo < hi)
+        {
+            const int mid = (lo + hi) / 2;
+            if (w[mid] <= lambdaRest)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        // (w[0] < lambdaRest < w[nlt - 1] here, so 0 <= lo - 1 <= nlt - 2; the clamp keeps a NaN velocity inside the grid)
+        const int below = lo - 1 > 0 ? lo - 1 : 0;
+        const int it = below < nlt - 2 ? below : nlt - 2;
+        frac = (lambdaRest - w[it]) / (w[it + 1] - w[it]);
+        i0 = it;
+        i1 = it + 1;
+    }
+}
+
 // besser_control_point_1d: FormalScalar.cpp:327-363
 DEVINL double d_besser_control_point(double hM, double hP, double yM, double yO, double yP)
 {

@@ -503,6 +503,10 @@ struct RayTrans
     int32_t prd, row, atom, ltStart; // row: aDamp row (lines) / ratio row (continua); ltStart: own-grid index of Nblue
     int64_t parOff, rhoOff, waveOff; // (rhoOff: of the row of Nblue)
     double lambda0;
+    // a line of the context's hybrid-PRD list (lwhip_hprd.lineAtom / lineTrans), read by the hybrid gather alone: its own grid is
+    // nlt wavelengths at waveOff, rho of the whole of it [nlt, Ns] at rho0Off (plan_hybrid_prd keeps it resident on every shard)
+    int32_t hybrid, nlt;
+    int64_t rho0Off;
 };
 
 // The structure tables of the gather and the staging of a call.  The tables depend on the structure alone: a context made with
@@ -999,5 +1003,8 @@ int batch_retile(lwhip_batch* b, const std::vector<lwhip_context*>& cols); // ti
 int check_stokes_batch(lwhip_batch* b, const char* what);
 // Every refusal of an observer-ray request, before anything is queued (lwhip_rays.hip); la0 / la1: the rows of the global grid it
 // asks for.  anySolver: the full-Stokes observer rays, which like lwhip_full_stokes_fs ignore the context's formal solver.
-int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, bool anySolver, int& la0, int& la1);
+// hybrid: the calls that serve hybrid-PRD contexts (lwhip_compute_rays_hprd and its kin) -- they need the tables every other
+// call refuses.
+int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, bool anySolver, int& la0, int& la1,
+               bool hybrid = false);
 }

@@ -281,38 +281,13 @@ __global__ __launch_bounds__(HPRD_THREADS) void hprd_rho_kernel(HprdIn a, const 
     const double* __restrict__ w = lineWave + L.waveOff;
     const int nlt = L.nlt;
     const double lambdaRest = w[lt] * hprd_fac(a, mu, toObs, k);
+    int i0, i1;
+    double frac;
+    d_hprd_rho_coeff(w, nlt, lambdaRest, i0, i1, frac);
     lwhip_rho_coeff c;
-    if (lambdaRest <= w[0])
-    {
-        c.frac = 0.0;
-        c.i0 = 0;
-        c.i1 = 1;
-    }
-    else if (lambdaRest >= w[nlt - 1])
-    {
-        c.frac = 1.0;
-        c.i0 = nlt - 2;
-        c.i1 = nlt - 1;
-    }
-    else
-    {
-        // std::upper_bound - 1: the last element <= lambdaRest
-        int lo = 0, hi = nlt;
-        while (lo < hi)
-        {
-            const int mid = (lo + hi) / 2;
-            if (w[mid] <= lambdaRest)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        // (w[0] < lambdaRest < w[nlt - 1] here, so 0 <= lo - 1 <= nlt - 2; the clamp keeps a NaN velocity inside the grid)
-        const int below = lo - 1 > 0 ? lo - 1 : 0;
-        const int it = below < nlt - 2 ? below : nlt - 2;
-        c.frac = (lambdaRest - w[it]) / (w[it + 1] - w[it]);
-        c.i0 = it;
-        c.i1 = it + 1;
-    }
+    c.frac = frac;
+    c.i0 = i0;
+    c.i1 = i1;
     out[cell] = c;
 }
 

@@ -25,6 +25,10 @@
 // lwhip_compute_rays_grid / lwhip_batch_compute_rays_grid: the same on a wavelength grid of the caller's choice.  The kernel's
 // row sources are pointers of the column's record; for a new grid they point at the request's rows (staged background, par and
 // transition records; J and rho interpolated on the device by rays_grid_rows_kernel) instead of the context's.
+//
+// lwhip_compute_rays_hprd and its three kin: the same four calls for contexts with hybrid-PRD tables, which the plain ones refuse.
+// The reference's second context runs configure_hprd_coeffs on the new rays; rays_kernel<true> forms that coefficient where it
+// gathers (d_hprd_rho_coeff, lwhip_device.h) and interpolates the line's rest-frame rho with it.  Same driver, same staging.
 #include "lwhip_host.h"
 #include "lwhip_device.h"
 // H(a, v) under the same contraction setting as the stored profiles' unit: the same argument gives the same bits
@@ -84,7 +88,12 @@ struct RaysArgs
     int32_t R, blocksPerCol;
 };
 
-__global__ void __launch_bounds__(RAYS_THREADS) rays_kernel(const RaysArgs g)
+// HYBRID: the context carries hybrid-PRD tables (lwhip_compute_rays_hprd and its kin).  rho of a line of the hybrid list is then
+// not the row's but what Transition::uv (LwTransition.hpp:116-127) interpolates from the line's rest-frame rho, with the
+// coefficient configure_hprd_coeffs (Prd.cpp:899-939) forms for this direction and depth -- formed here, where it is used,
+// like phi.  The line's grid is read from global memory: a few hundred doubles that every lane of the launch shares.  The
+// false instance reads nothing of this.
+template <bool HYBRID> __global__ void __launch_bounds__(RAYS_THREADS) rays_kernel(const RaysArgs g)
 {
     dbg_poison_lds();
     extern __shared__ double lds[];
@@ -144,9 +153,26 @@ __global__ void __launch_bounds__(RAYS_THREADS) rays_kernel(const RaysArgs g)
                     const double phi = d_voigt_H(aDamp[(size_t)t.row * Ns + k], vk) / (sqrtPi * vb);
                     Vij = p[0] * phi;
                     double gij = p[2];
-                    if (t.prd)
-                        gij *= a->rho[t.rhoOff + (size_t)l0 * Ns + k];
-                    Vji = gij * Vij;
+                    if (HYBRID && t.hybrid)
+                    {
+                        // (gij stays Bji / Bij, LwAtom.hpp:118-123; rho multiplies Vji, LwTransition.hpp:118-126)
+                        // lambdaRest of the line's own-grid point for this ray (toObs = 1), in the reference's order
+                        const double* w = lineWave + t.waveOff;
+                        const double lambdaRest = w[t.ltStart + l0] * (1.0 + vlos * 1.0 / CLight);
+                        int i0, i1;
+                        double frac;
+                        d_hprd_rho_coeff(w, t.nlt, lambdaRest, i0, i1, frac);
+                        const double* rho0 = a->rho + t.rho0Off + k;
+                        const double rho = (1.0 - frac) * rho0[(size_t)i0 * Ns] + frac * rho0[(size_t)i1 * Ns];
+                        Vji = gij * Vij;
+                        Vji *= rho;
+                    }
+                    else
+                    {
+                        if (t.prd)
+                            gij *= a->rho[t.rhoOff + (size_t)l0 * Ns + k];
+                        Vji = gij * Vij;
+                    }
                     Uji = p[3] * Vji;
                 }
                 else
@@ -327,7 +353,7 @@ void rays_release(RaysState* s)
 
 // Every refusal of a request, before anything is queued.  la0 / la1: the rows of the global grid.  (Shared with the full-Stokes
 // observer rays, lwhip_stokes_fs.hip: anySolver.)
-int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, bool anySolver, int& la0, int& la1)
+int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, bool anySolver, int& la0, int& la1, bool hybrid)
 {
     if (!c)
         return fail(LWHIP_ERR_INVALID, what + ": null context");
@@ -335,8 +361,12 @@ int rays_check(lwhip_context* c, const lwhip_rays* r, const std::string& what, b
         return fail(LWHIP_ERR_INVALID, what + ": null request");
     if (c->is2d)
         return fail(LWHIP_ERR_UNSUPPORTED, what + ": observer rays are 1D plane-parallel only");
-    if (c->hprd)
-        return fail(LWHIP_ERR_UNSUPPORTED, what + ": not with hybrid PRD tables (rho there is tied to the quadrature rays)");
+    if (c->hprd && !hybrid)
+        return fail(LWHIP_ERR_UNSUPPORTED, what + ": not with hybrid PRD tables (rho there is tied to the quadrature rays; the "
+                                               "_hprd form of this call interpolates it for the new ones)");
+    if (!c->hprd && hybrid)
+        return fail(LWHIP_ERR_INVALID, what + ": the context has no hybrid PRD tables (lwhip_options.hprd); its observer rays are "
+                                           "those of the call without _hprd");
     if (!anySolver && c->prob.formalSolver != LWHIP_FS_BEZIER3_1D)
         return fail(LWHIP_ERR_UNSUPPORTED, what + ": piecewise_bezier3_1d contexts only");
     if (c->Ns < 3)
@@ -393,6 +423,12 @@ hipError_t rays_init_table(int device)
     return e;
 }
 
+// transition `tr` is in the context's hybrid line list (what configure_hprd_coeffs covered: plan_hybrid_prd); a PRD line outside
+// it keeps rho by row, as Transition::uv does where hPrdCoeffs is empty
+bool rays_hybrid_line(const lwhip_context* c, size_t tr)
+{
+    return c->hprd && tr < c->hRhoOffHost.size() && c->hRhoOffHost[tr] >= 0;
+}
 } // namespace
 
 // the gather tables of `o` (a table owner), made on first use
@@ -423,6 +459,13 @@ int rays_tables(lwhip_context* o, RaysState*& out)
         t.rhoOff = h.rhoOff >= 0 ? h.rhoOff + (int64_t)(h.ltStart - h.rhoLt0) * Ns : 0;
         t.waveOff = ev[i].waveOff;
         t.lambda0 = ev[i].lambda0;
+        if (t.prd && rays_hybrid_line(o, i))
+        {
+            // (rho of a hybrid line is resident for its whole grid, rhoLt0 = 0: plan_transition_list)
+            t.hybrid = 1;
+            t.nlt = h.t.Nred - h.t.Nblue;
+            t.rho0Off = h.rhoOff;
+        }
     }
     std::vector<int32_t> laOff, laTr;
     active_trans_lists(o->trans, o->Nla, true, laOff, laTr);
@@ -448,7 +491,7 @@ size_t rays_out_bytes(size_t nRayCol, int Ns, bool depth) { return (nRayCol + (d
 // column's outputs into its request's arrays.  `pre`: queued between the copy and the launch (the rows a new grid needs).
 template <typename Pre>
 int rays_launch_fetch(lwhip_context* c0, RaysState& st, const std::vector<const lwhip_rays*>& reqs, int Ns, int Nmu, int la0,
-                      int nla, size_t inBytes, const std::string& what, Pre pre)
+                      int nla, size_t inBytes, const std::string& what, bool hybrid, Pre pre)
 {
     const int n = (int)reqs.size();
     const bool depth = reqs[0]->depthI != nullptr;
@@ -473,7 +516,10 @@ int rays_launch_fetch(lwhip_context* c0, RaysState& st, const std::vector<const 
     const size_t nBlk = (size_t)n * g.blocksPerCol;
     if (nBlk > 0x7fffffffu)
         return fail(LWHIP_ERR_UNSUPPORTED, what + ": too many rays for one launch");
-    LWHIP_LAUNCH(rays_kernel, dim3((unsigned)nBlk), dim3(RAYS_THREADS), ldsBytes, c0->stream, g);
+    if (hybrid)
+        LWHIP_LAUNCH(rays_kernel<true>, dim3((unsigned)nBlk), dim3(RAYS_THREADS), ldsBytes, c0->stream, g);
+    else
+        LWHIP_LAUNCH(rays_kernel<false>, dim3((unsigned)nBlk), dim3(RAYS_THREADS), ldsBytes, c0->stream, g);
     HIP_TRY(hipGetLastError());
     // ---- one copy back, one wait -------------------------------------------------------------------------------------------------
     unsigned char* hout = st.outPinned.as<unsigned char>();
@@ -622,9 +668,10 @@ struct Stage
 };
 
 // The call: cols[i] with request reqs[i], everything on cols[0]'s stream, staged through `st`.  grids: empty, or the new-grid
-// requests reqs[i] is embedded in -- then the rows the kernel reads are the request's, not the context's.
+// requests reqs[i] is embedded in -- then the rows the kernel reads are the request's, not the context's.  hybrid: every column
+// carries hybrid-PRD tables, and rho of the lines of its hybrid list is interpolated for the new rays (rays_kernel<true>).
 int rays_run(lwhip_context* const* cols, int n, const std::vector<const lwhip_rays*>& reqs,
-             const std::vector<const lwhip_rays_grid*>& grids, RaysState*& slot, const std::string& what)
+             const std::vector<const lwhip_rays_grid*>& grids, RaysState*& slot, const std::string& what, bool hybrid)
 {
     const bool grid = !grids.empty();
     int la0 = 0, la1 = 0;
@@ -638,7 +685,7 @@ int rays_run(lwhip_context* const* cols, int n, const std::vector<const lwhip_ra
             return fail(LWHIP_ERR_INVALID, what + ": laStart and laEnd must be 0 with a wavelength grid (they select rows of the "
                                                "context's own)" + (n > 1 ? " (column " + std::to_string(i) + ")" : ""));
         int a0 = 0, a1 = 0;
-        const int chk = rays_check(cols[i], reqs[i], what, false, a0, a1);
+        const int chk = rays_check(cols[i], reqs[i], what, false, a0, a1, hybrid);
         if (chk != LWHIP_OK)
             return named(chk);
         if (i == 0)
@@ -677,6 +724,11 @@ int rays_run(lwhip_context* const* cols, int n, const std::vector<const lwhip_ra
     for (int i = 0; i < n && !grid; ++i)
     {
         lwhip_context* o = cols[i]->tablesFrom ? cols[i]->tablesFrom : cols[i];
+        // (the tables are the owner's: its hybrid list is this column's, as its rho layout is -- both follow the structure)
+        for (size_t t = 0; hybrid && t < cols[i]->trans.size(); ++t)
+            if (rays_hybrid_line(o, t) != rays_hybrid_line(cols[i], t))
+                return fail(LWHIP_ERR_INVALID, what + ": the hybrid PRD line list differs from that of the context whose tables "
+                                                   "this one shares" + (n > 1 ? " (column " + std::to_string(i) + ")" : ""));
         const int stp = rays_tables(o, tabs[i]);
         if (stp != LWHIP_OK)
             return stp;
@@ -818,6 +870,14 @@ int rays_run(lwhip_context* const* cols, int n, const std::vector<const lwhip_ra
                     if (++nPrd > prdLines.size())
                         break;
                     t.rhoOff = (int64_t)(nPrd * rowLen);
+                    if (hybrid && rays_hybrid_line(c, (size_t)act[k]))
+                    {
+                        // the line's own grid is the request's, and rho' [Nwave, Ns] is its rho (what the reference's second
+                        // context holds after subset_configuration)
+                        t.hybrid = 1;
+                        t.nlt = nla;
+                        t.rho0Off = t.rhoOff;
+                    }
                     jobs[nPrd] = InterpJob{ c->lineWave.p + h.waveOff + h.rhoLt0, c->rho.p + h.rhoOff, rowsDev + nPrd * rowLen,
                                             h.rhoRows, 0 };
                 }
@@ -868,7 +928,7 @@ int rays_run(lwhip_context* const* cols, int n, const std::vector<const lwhip_ra
         hc[i] = a;
     }
     if (!grid)
-        return rays_launch_fetch(c0, st, reqs, Ns, Nmu, la0 - c0->laStart, nla, inBytes, what, [] { return LWHIP_OK; });
+        return rays_launch_fetch(c0, st, reqs, Ns, Nmu, la0 - c0->laStart, nla, inBytes, what, hybrid, [] { return LWHIP_OK; });
     // the rows of the new grid first, on the same stream
     InterpArgs ia{};
     ia.jobs = (const InterpJob*)(st.in.p + jobsOff);
@@ -881,14 +941,14 @@ int rays_run(lwhip_context* const* cols, int n, const std::vector<const lwhip_ra
     const unsigned bx = (unsigned)std::min<size_t>(((size_t)nla * Ns + RAYS_THREADS - 1) / RAYS_THREADS, 4096);
     const unsigned by = (unsigned)std::min<size_t>((size_t)n * jobsPerCol, 65535);
     hipStream_t stream = c0->stream;
-    return rays_launch_fetch(c0, st, reqs, Ns, Nmu, 0, nla, inBytes, what, [&]() -> int {
+    return rays_launch_fetch(c0, st, reqs, Ns, Nmu, 0, nla, inBytes, what, hybrid, [&]() -> int {
         LWHIP_LAUNCH(rays_grid_rows_kernel, dim3(bx, by), dim3(RAYS_THREADS), 0, stream, ia);
         HIP_TRY(hipGetLastError());
         return LWHIP_OK;
     });
 }
 
-int rays_run_plain(lwhip_context* const* cols, int n, const lwhip_rays* reqs, RaysState*& slot, const char* whatC)
+int rays_run_reqs(lwhip_context* const* cols, int n, const lwhip_rays* reqs, RaysState*& slot, const char* whatC, bool hybrid)
 {
     const std::string what(whatC);
     if (lwhip_device_count() <= 0)
@@ -898,10 +958,10 @@ int rays_run_plain(lwhip_context* const* cols, int n, const lwhip_rays* reqs, Ra
     std::vector<const lwhip_rays*> ptrs(n);
     for (int i = 0; i < n; ++i)
         ptrs[i] = reqs + i;
-    return rays_run(cols, n, ptrs, {}, slot, what);
+    return rays_run(cols, n, ptrs, {}, slot, what, hybrid);
 }
 
-int rays_run_grid(lwhip_context* const* cols, int n, const lwhip_rays_grid* reqs, RaysState*& slot, const char* whatC)
+int rays_run_reqs(lwhip_context* const* cols, int n, const lwhip_rays_grid* reqs, RaysState*& slot, const char* whatC, bool hybrid)
 {
     const std::string what(whatC);
     if (lwhip_device_count() <= 0)
@@ -915,30 +975,46 @@ int rays_run_grid(lwhip_context* const* cols, int n, const lwhip_rays_grid* reqs
         grids[i] = reqs + i;
         ptrs[i] = &reqs[i].rays;
     }
-    return rays_run(cols, n, ptrs, grids, slot, what);
+    return rays_run(cols, n, ptrs, grids, slot, what, hybrid);
+}
+
+// The entry points: one context or the columns of a batch, the stored grid (lwhip_rays) or a new one (lwhip_rays_grid), plain or
+// for hybrid-PRD contexts.
+template <typename Req> int rays_ctx(lwhip_context* c, const Req* rays, bool hybrid, const char* what)
+{
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, std::string(what) + ": no gfx950 device");
+    if (!c)
+        return fail(LWHIP_ERR_INVALID, std::string(what) + ": null context");
+    lwhip_context* cols[1] = { c };
+    return rays_run_reqs(cols, 1, rays, c->rays, what, hybrid);
+}
+
+template <typename Req> int rays_batch(lwhip_batch* b, const Req* perColumn, bool hybrid, const char* what)
+{
+    if (lwhip_device_count() <= 0)
+        return fail(LWHIP_ERR_DEVICE, std::string(what) + ": no gfx950 device");
+    if (!b || b->ctxs.empty())
+        return fail(LWHIP_ERR_INVALID, std::string(what) + ": null batch");
+    return rays_run_reqs(b->ctxs.data(), (int)b->ctxs.size(), perColumn, b->rays, what, hybrid);
 }
 } // namespace
 } // namespace lwhip
 
 extern "C"
 {
-int lwhip_compute_rays(lwhip_context* c, const lwhip_rays* rays)
-{
-    if (lwhip_device_count() <= 0)
-        return fail(LWHIP_ERR_DEVICE, "lwhip_compute_rays: no gfx950 device");
-    if (!c)
-        return fail(LWHIP_ERR_INVALID, "lwhip_compute_rays: null context");
-    lwhip_context* cols[1] = { c };
-    return rays_run_plain(cols, 1, rays, c->rays, "lwhip_compute_rays");
-}
+int lwhip_compute_rays(lwhip_context* c, const lwhip_rays* rays) { return rays_ctx(c, rays, false, "lwhip_compute_rays"); }
 
 int lwhip_batch_compute_rays(lwhip_batch* b, const lwhip_rays* perColumn)
 {
-    if (lwhip_device_count() <= 0)
-        return fail(LWHIP_ERR_DEVICE, "lwhip_batch_compute_rays: no gfx950 device");
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "lwhip_batch_compute_rays: null batch");
-    return rays_run_plain(b->ctxs.data(), (int)b->ctxs.size(), perColumn, b->rays, "lwhip_batch_compute_rays");
+    return rays_batch(b, perColumn, false, "lwhip_batch_compute_rays");
+}
+
+int lwhip_compute_rays_hprd(lwhip_context* c, const lwhip_rays* rays) { return rays_ctx(c, rays, true, "lwhip_compute_rays_hprd"); }
+
+int lwhip_batch_compute_rays_hprd(lwhip_batch* b, const lwhip_rays* perColumn)
+{
+    return rays_batch(b, perColumn, true, "lwhip_batch_compute_rays_hprd");
 }
 
 int lwhip_rays_grid_active(lwhip_context* c, const double* wavelength, int Nwave, int32_t* active)
@@ -953,20 +1029,21 @@ int lwhip_rays_grid_active(lwhip_context* c, const double* wavelength, int Nwave
 
 int lwhip_compute_rays_grid(lwhip_context* c, const lwhip_rays_grid* rays)
 {
-    if (lwhip_device_count() <= 0)
-        return fail(LWHIP_ERR_DEVICE, "lwhip_compute_rays_grid: no gfx950 device");
-    if (!c)
-        return fail(LWHIP_ERR_INVALID, "lwhip_compute_rays_grid: null context");
-    lwhip_context* cols[1] = { c };
-    return rays_run_grid(cols, 1, rays, c->rays, "lwhip_compute_rays_grid");
+    return rays_ctx(c, rays, false, "lwhip_compute_rays_grid");
 }
 
 int lwhip_batch_compute_rays_grid(lwhip_batch* b, const lwhip_rays_grid* perColumn)
 {
-    if (lwhip_device_count() <= 0)
-        return fail(LWHIP_ERR_DEVICE, "lwhip_batch_compute_rays_grid: no gfx950 device");
-    if (!b || b->ctxs.empty())
-        return fail(LWHIP_ERR_INVALID, "lwhip_batch_compute_rays_grid: null batch");
-    return rays_run_grid(b->ctxs.data(), (int)b->ctxs.size(), perColumn, b->rays, "lwhip_batch_compute_rays_grid");
+    return rays_batch(b, perColumn, false, "lwhip_batch_compute_rays_grid");
+}
+
+int lwhip_compute_rays_grid_hprd(lwhip_context* c, const lwhip_rays_grid* rays)
+{
+    return rays_ctx(c, rays, true, "lwhip_compute_rays_grid_hprd");
+}
+
+int lwhip_batch_compute_rays_grid_hprd(lwhip_batch* b, const lwhip_rays_grid* perColumn)
+{
+    return rays_batch(b, perColumn, true, "lwhip_batch_compute_rays_grid_hprd");
 }
 }
